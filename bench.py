@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: Tanimoto top-1000 scan of synthetic 1024-bit tables.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` (N > 1) without a launcher starts its own N ranks (one process per GPU, 127.0.0.1
@@ -289,6 +289,48 @@ def compact_line(out, detail_path):
     return text
 
 
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def last_step_outputs(hits, counts, approx):
+    """What a caller of the timed path received for the last step's queries -- HIT_DTYPE hits [nq, k], hit counts,
+    approx -- as float arrays for --dump-outputs (slots past a query's count: row -1, score NaN).  Above DUMP_CAP_BYTES a
+    fixed, seeded sample of the queries; `query_slot` names each dumped query's place in the step."""
+    nq, k = hits.shape
+    slot = np.arange(nq)
+    per_query = k * (8 + 4 + 4 + 4) + 4 * 8
+    if nq * per_query > DUMP_CAP_BYTES:
+        slot = np.sort(np.random.default_rng(0).choice(nq, size=max(1, DUMP_CAP_BYTES // per_query), replace=False))
+    hits, counts, approx = hits[slot], np.asarray(counts)[slot], np.asarray(approx)[slot]
+    valid = np.arange(k)[None, :] < counts[:, None].astype(np.int64)
+    return {
+        "hits_row": np.where(valid, hits["row"].astype(np.float64), -1.0),
+        "hits_score": np.where(valid, hits["score"], np.float32("nan")).astype(np.float32),
+        "hits_common": np.where(valid, hits["common"], 0).astype(np.float32),
+        "hits_popc_db": np.where(valid, hits["popc_db"], 0).astype(np.float32),
+        "hit_count": counts.astype(np.float64),
+        "approx": approx.astype(np.float64),
+        "query_slot": slot.astype(np.float64),
+    }
+
+
+def results_as_buffers(results, k):
+    """[(hits, approx, flags)] of the gather + merge objects -> the (hits, counts, approx) buffers of the C ABI."""
+    from gpusimilarity_amd import capi
+    hits = np.zeros((len(results), max(k, 1)), dtype=capi.HIT_DTYPE)
+    counts = np.zeros(len(results), dtype=np.uint32)
+    approx = np.zeros(len(results), dtype=np.uint64)
+    for i, (h, a, _) in enumerate(results):
+        hits[i, :len(h)], counts[i], approx[i] = h, len(h), a
+    return hits, counts, approx
+
+
+def dump_outputs(outputs, dirname):
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def emit(out, json_fd, detail_name="bench_detail.json"):
     """Write the full record to bench_detail.json (beside bench.py; and under gpurun_out/ when that directory exists, so that a
     gpurun call brings it home) and the contract line to stdout."""
@@ -310,8 +352,11 @@ def emit(out, json_fd, detail_name="bench_detail.json"):
 # GPU runs
 # ---------------------------------------------------------------------------------------------
 
-def time_queries(ctx, table, total_rows, R, fp_bits, kind, k, steps, warmup, qps, sharded, barrier=True, first_row=0):
-    """steps x qps single queries (after warmup x qps), barrier + synchronize on both sides, max over ranks."""
+def time_queries(ctx, table, total_rows, R, fp_bits, kind, k, steps, warmup, qps, sharded, barrier=True, first_row=0,
+                 keep_outputs=False):
+    """steps x qps single queries (after warmup x qps), barrier + synchronize on both sides, max over ranks.
+    keep_outputs: res["outputs"] holds the last timed step's results (last_step_outputs; the N > 1 path: its last
+    `depth` queries, what the gather + merge objects still hold)."""
     import torch
     import torch.distributed as dist
     from gpusimilarity_amd.sharded import ShardedSearch
@@ -374,6 +419,14 @@ def time_queries(ctx, table, total_rows, R, fp_bits, kind, k, steps, warmup, qps
     if dist.is_initialized() and barrier:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    outputs = None
+    if keep_outputs:
+        if sharded:
+            tail = range(max(0, qps - depth), qps)  # query j of the step went through pair[j % depth]
+            outputs = last_step_outputs(*results_as_buffers([pair[j % depth].result() for j in tail], k))
+            outputs["query_slot"] += tail[0]
+        else:
+            outputs = last_step_outputs(*bufs)
     if ctx["world"] > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=ctx["dev"] if ctx["backend"] == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -422,6 +475,7 @@ def time_queries(ctx, table, total_rows, R, fp_bits, kind, k, steps, warmup, qps
     achieved = algo / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
     res = {
         "seconds": elapsed, "queries": steps * qps, "ms_per_query": 1e3 * elapsed / (steps * qps), "sync_latency": sync, "phases": phases,
+        "outputs": outputs,
         "fingerprints_per_s": total_rows * steps * qps / elapsed,
         "whole_path_hbm_frac": (total_rows * (fp_bits // 8) / (elapsed / (steps * qps))) / (HBM_PEAK_GBS * 1e9 * ctx["world"]),
         "roofline": {
@@ -496,10 +550,11 @@ def issue_roofline(W, frac, dense=False):
     return out
 
 
-def time_batches(ctx, table, total_rows, R, fp_bits, kind, k, Q, steps, warmup, sharded, cutoff=0.0):
+def time_batches(ctx, table, total_rows, R, fp_bits, kind, k, Q, steps, warmup, sharded, cutoff=0.0, keep_outputs=False):
     """BASELINE configs[4]: Tversky(0.3, 0.7), Q-query batches, top-k per query; a step = one batch.
     Rows shard over the ranks, every rank scores all Q queries against its shard (the matrix-core
-    pass), ONE all-gather of Q result blocks per step, one merge launch."""
+    pass), ONE all-gather of Q result blocks per step, one merge launch.
+    keep_outputs: res["outputs"] holds the last timed batch's results (last_step_outputs)."""
     import torch
     import torch.distributed as dist
     from gpusimilarity_amd import capi
@@ -537,6 +592,9 @@ def time_batches(ctx, table, total_rows, R, fp_bits, kind, k, Q, steps, warmup, 
     if dist.is_initialized():
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    outputs = None
+    if keep_outputs:
+        outputs = last_step_outputs(*(results_as_buffers(sb.results(), k) if sharded else bufs))
     if ctx["world"] > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=ctx["dev"] if ctx["backend"] == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -549,7 +607,7 @@ def time_batches(ctx, table, total_rows, R, fp_bits, kind, k, Q, steps, warmup, 
     tf_kernel = flops / (kms * 1e-3) / 1e12 if kms > 0 else 0.0
     return {
         "seconds": elapsed, "batches": steps, "ms_per_batch": 1e3 * per, "pairs_per_s": Q * total_rows / per,
-        "queries_per_s": Q / per,
+        "queries_per_s": Q / per, "outputs": outputs,
         "roofline": {"kernel": "batch_mfma_kernel<%d> (MX-FP4 contraction of the packed bits, f32 accumulate: exact)" % W,
                      "bound": "mfma", "achieved": tf_kernel, "peak": MFMA_FP4_PEAK_TFLOPS, "unit": "TFLOP/s",
                      "frac": tf_kernel / MFMA_FP4_PEAK_TFLOPS, "traffic": None, "kernel_ms_avg": kms,
@@ -617,6 +675,8 @@ def in_process(args):
     routes = {}
     routes["host_merge"], ref = run(table, total)
     assert int(ref[1][-1]) == min(k, total) and int(ref[2][-1]) == total and ref[0][-1]["score"][0] == 1.0, "self hit missing"
+    if args.dump_outputs:
+        dump_outputs(last_step_outputs(*ref), args.dump_outputs)
     comm = None
     try:
         comm = capi.Comm(list(range(table.shard_count())))
@@ -713,7 +773,13 @@ def main():
     ap.add_argument("--no-torch-route", action="store_true", help="--in-process: skip the torch.distributed child run")
     ap.add_argument("--force-sharded-path", action="store_true",
                     help="run the N>1 code path (device result blocks, all-gather, device merge) even at N=1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (hits of its queries, counts, approx) as "
+                         "DIR/<name>.npy, float32/float64, at most 64 MB (a fixed, seeded sample of the queries above that); "
+                         "rank 0 only.  The inputs are the same from run to run, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.pmc_child:
         pmc_child(args.rows_per_gpu or 100_000_000, args.fp_bits, {"sparse": 0, "dense": 1, "morgan": 2}[args.kind], args.k)
@@ -792,7 +858,10 @@ def main():
     table = make_table(R, args.fp_bits, rank * R)
     if args.batch_queries:
         Q = args.batch_queries
-        res = time_batches(ctx, table, total_rows, R, args.fp_bits, kind, k, Q, args.steps, args.warmup, sharded, cutoff=np.float32(args.cutoff))
+        res = time_batches(ctx, table, total_rows, R, args.fp_bits, kind, k, Q, args.steps, args.warmup, sharded, cutoff=np.float32(args.cutoff),
+                           keep_outputs=bool(args.dump_outputs))
+        if args.dump_outputs and rank == 0:
+            dump_outputs(res["outputs"], args.dump_outputs)
         out = {
             "metric": "(query, fingerprint) pairs scored/sec (%d-bit Tversky(0.3,0.7), %d-query batches, top-%d)" % (args.fp_bits, Q, k),
             "value": res["pairs_per_s"], "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -814,7 +883,10 @@ def main():
         return
 
     qps = max(1, args.queries_per_step)
-    res, _ss = time_queries(ctx, table, total_rows, R, args.fp_bits, kind, k, args.steps, args.warmup, qps, sharded)
+    res, _ss = time_queries(ctx, table, total_rows, R, args.fp_bits, kind, k, args.steps, args.warmup, qps, sharded,
+                            keep_outputs=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res["outputs"], args.dump_outputs)
     if sharded:
         # what each rank's own phases cost (HIP events on its stream) and -- the N = 1 twin -- what the same shard answers
         # alone through the synchronous single-GPU path: the 1 -> N curve then decomposes into scan / gather / merge / copy

@@ -9,8 +9,8 @@
 #                                    real Qt 5.9 headers and libraries; `-include QElapsedTimer` for gpusim.cpp: Qt 5.9 lacks the
 #                                    transitive include its newer Qt had) + docs/fingerprintdb_hip.cpp + -lgsim_hip instead of
 #                                    fingerprintdb_cuda.cu (reference CMakeLists.txt:60-67) -> <dir>/refserver_hip, a SCRATCH binary:
-#                                    never committed, never shipped, never sent to the GPU box (tests/test_host_cpp.py replays the
-#                                    golden protocol frames against it with --cpu_only and removes it)
+#                                    never committed, never shipped, never sent to the GPU box (start it --cpu_only and replay
+#                                    tests/golden/protocol_frames.json against it)
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 REF="${GSIM_REFERENCE_DIR:-/root/reference}"

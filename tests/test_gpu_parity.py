@@ -539,8 +539,19 @@ def test_attach_device_rows_borrowed_torch_tensor():
     assert (t.row(39_999) == db[39_999]).all()
 
 
-@pytest.mark.skipif(capi.device_count() < 2, reason="needs >= 2 GPUs in one process")
 def test_in_process_multi_device_shards():
+    """One handle sharded over every device of the process.  Fewer than two GPUs: the same test in a child process on the
+    test-hooks build with two logical devices on GPU 0 (GSIM_TEST_ALIAS_DEVICES=2: every shard its own stream, state and
+    scratch, as on two GPUs)."""
+    if capi.device_count() < 2:
+        import subprocess
+        import sys
+        from conftest import hooks_env
+        assert not os.environ.get("GSIM_TEST_ALIAS_DEVICES"), "two logical devices asked for, %d seen" % capi.device_count()
+        p = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-q", "-x", "-m", "gpu", "-k",
+                            "test_in_process_multi_device_shards"], env=hooks_env(GSIM_TEST_ALIAS_DEVICES="2"), capture_output=True, timeout=900)
+        assert p.returncode == 0 and b"1 passed" in p.stdout, p.stdout.decode("utf-8", "replace")[-3000:]
+        return
     db = O.synth_rows(0x5AAD, 0, 0, 300_001, 32)
     t = make_table(db, device=0, ndevices=0)
     assert t.shard_count() == capi.device_count()
