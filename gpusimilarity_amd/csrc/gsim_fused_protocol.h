@@ -1,14 +1,15 @@
 // gsim_fused_protocol.h -- the single launch (gsim_fused.hip): what it is, its constants, its LDS layout, its checkpoint schedule, and --
 // "THE EDGES", at the end of the opening comment -- the contract of every place where one workgroup depends on another, each written once.
-// Included by gsim_fused.hip only, inside namespace gsim { namespace {.  The kernel itself is split by phase:
-//   gsim_fused.hip              prologue + phase 1 (the streaming loop, gsim_scan_inl.h) + the launchers
+// Included by gsim_fused.hip only, inside namespace gsim { namespace {.  The kernel and its pieces:
+//   gsim_fused.hip              fused_kernel: prologue, phase 1 (the streaming loop, gsim_scan_inl.h), phase 3 (publish) and phase 4
+//                               (select) in its body, then FusedCtx::close; FusedCtx (what the stamps and close read); the launchers
 //   gsim_fused_thresholds.inl   phase 2: in-loop thresholds (FusedFilter, the election, the forwarder and poller waves)
-//   gsim_fused_publish.inl      phase 3: a workgroup publishes its survivors, its report and its header      (body of fused_kernel)
-//   gsim_fused_select.inl       phase 4: every workgroup selects: headers, final threshold, finalists, ranks (body of fused_kernel)
-//   gsim_fused_close.inl        phase 5: tickets, the result header, the per-query state's reset              (body of fused_kernel)
+//   gsim_fused_close.inl        phase 5: tickets, the result header, the per-query state's reset (FusedCtx::close, rezero_exchange)
 //   gsim_fused_largek.inl       behind a publishing launch: fused_handoff_kernel, fused_binsort_kernel
-// The .inl files of phases 3-5 are consecutive pieces of ONE function body (fused_kernel): they share its locals.  The split moved
-// text, not tokens: the generated code is identical to the one-file form's (checked when it was made, round 6).
+// Publish and select stay in the kernel's body: as __forceinline__ functions of their own, the gfx950 code of every fused_kernel
+// instantiation changes (select: 190-203 VGPRs instead of 104-201; publish: 4-8 more SGPR spills, most +1 VGPR).  With both, and the
+// prologue and scan, as functions, configs[2] fused_kernel<8,8> measured 1.8201 / 1.8202 ms against 1.8038 / 1.8017 ms (two
+// alternating bench.py runs each, 20 steps of 128 queries).
 #pragma once
 
 // ---------------------------------------------------------------------------
@@ -78,7 +79,7 @@
 //          except tables of a few trips (FusedSchedule::late), which wait for `need()` elections with a bound (wait_ticks) and hand
 //          the query back when it runs out (kRedoElectionWait).
 //
-//   E2  publish -> select: regions, headers, tags            W: gsim_fused_publish.inl   R: gsim_fused_select.inl
+//   E2  publish -> select: regions, headers, tags            W, R: fused_kernel (publish, select)
 //       W  workgroup b writes its survivors into ITS region (FusedArgs::pub + b * kFusedRegion entries of 16 bytes:
 //          {key lo, key hi, popcounts, TAG}) with 16-byte sc1 stores, then -- behind a workgroup barrier, WITHOUT waiting for the
 //          entries' acknowledgements -- ONE 16-byte sc1 store of its header (FusedArgs::hdr[b]: {entries | order, bucket shift |
@@ -91,7 +92,7 @@
 //          a region is written by exactly one workgroup per launch and read only after its header; lists are in an order a reader can
 //          stop in (canonical up to kFusedSortCap rows, bucket order above).  Regions are zero when allocated (tag 0 = never valid).
 //
-//   E3  the final threshold                                   gsim_fused_select.inl
+//   E3  the final threshold                                   fused_kernel (select)
 //       Every selector computes it FOR ITSELF from the 256 reports in the headers (no exchange): a report with at least r - 1 larger
 //       ones, r = ceil(k / Mw).  Contract: the computation is a pure function of the headers' contents, so all selectors agree; the
 //       row -> selector assignment is a hash of the row index, so every finalist is ranked by exactly one selector.
@@ -108,7 +109,7 @@
 //          does not rely on it: it verifies the checksum against the hits it reads and re-runs a block that stays wrong
 //          (capi_query.cpp finish_query_sync; gsim_timing.blocks_rechecked / blocks_torn).
 //
-//   E5  a publishing launch (large k) -> the kernels behind it    W: gsim_fused_publish.inl   R: gsim_fused_largek.inl, gsim_select.hip
+//   E5  a publishing launch (large k) -> the kernels behind it    W: fused_kernel (publish)   R: gsim_fused_largek.inl, gsim_select.hip
 //       W  as E2, plus the published rows counted per coarse bin into QueryState::ghist (device atomics) and a two-level count-in
 //          (FusedArgs::arrive); nobody waits: the LAST workgroup to count in tidies up the exchange state.
 //       R  fused_handoff_kernel / fused_binsort_kernel run behind the launch on the SAME stream: kernel-boundary ordering makes
