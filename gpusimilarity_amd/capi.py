@@ -38,6 +38,11 @@ class GsimTiming(C.Structure):
                 ("rerun_behind", C.c_uint64), ("rerun_torn", C.c_uint64), ("lane_queries", C.c_uint64), ("backoff_skips", C.c_uint64)]
 
 
+class GsimGraphStats(C.Structure):
+    _fields_ = [("launches", C.c_uint64), ("launches_rerun", C.c_uint64), ("pairs", C.c_uint64), ("tile_ms", C.c_double),
+                ("csr_ms", C.c_double), ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -56,6 +61,7 @@ EXPORTS = [
     "gsim_merge_device_batch", "gsim_merge_host",
     "gsim_comm_create", "gsim_comm_destroy", "gsim_comm_size", "gsim_rccl_info", "gsim_db_set_comm", "gsim_db_set_comm_root",
     "gsim_db_enable_timing",
+    "gsim_db_neighbors", "gsim_graph_shape", "gsim_graph_copy", "gsim_graph_get_stats", "gsim_graph_destroy", "gsim_butina",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -131,6 +137,12 @@ def load():
         "gsim_debug_sort_desc": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32]),
         "gsim_debug_prefilter_constants": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint32, C.c_int, C.c_float,
                                                       C.POINTER(C.c_float)]),
+        "gsim_db_neighbors": (C.c_int, [vp, C.c_float, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
+        "gsim_graph_shape": (C.c_int, [vp, u64p, u64p]),
+        "gsim_graph_copy": (C.c_int, [vp, u64p, u32p, C.POINTER(C.c_float)]),
+        "gsim_graph_get_stats": (C.c_int, [vp, C.POINTER(GsimGraphStats)]),
+        "gsim_graph_destroy": (C.c_int, [vp]),
+        "gsim_butina": (C.c_int, [u64p, u32p, C.c_uint64, u32p, u32p, u64p]),
         "gsim_last_error": (C.c_char_p, []),
         "gsim_version": (C.c_char_p, []),
     }
@@ -272,6 +284,30 @@ class Table:
                                      approx.ctypes.data_as(C.POINTER(C.c_uint64))))
         return [hits[i, :counts[i]].copy() for i in range(nq)], approx
 
+    def neighbors(self, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, row_begin=0, row_end=None, stats=None):
+        """gsim_db_neighbors: every row j != i with score(row i, row j) >= cutoff, for the rows i of [row_begin, row_end)
+        -> CSR (indptr uint64 [n + 1], indices uint32 (+ row base), scores float32), each row's list by column.
+        `stats`: a dict that receives the call's gsim_graph_stats."""
+        if row_end is None:
+            row_end = self.count()
+        g = C.c_void_p()
+        check(self._L.gsim_db_neighbors(self._h, cutoff, metric, alpha, beta, row_begin, row_end, C.byref(g)))
+        try:
+            n, nnz = C.c_uint64(0), C.c_uint64(0)
+            check(self._L.gsim_graph_shape(g, C.byref(n), C.byref(nnz)))
+            indptr = np.empty(n.value + 1, dtype=np.uint64)
+            indices = np.empty(nnz.value, dtype=np.uint32)
+            scores = np.empty(nnz.value, dtype=np.float32)
+            check(self._L.gsim_graph_copy(g, indptr.ctypes.data_as(C.POINTER(C.c_uint64)), _u32(indices),
+                                          scores.ctypes.data_as(C.POINTER(C.c_float))))
+            if stats is not None:
+                st = GsimGraphStats()
+                check(self._L.gsim_graph_get_stats(g, C.byref(st)))
+                stats.update({f: getattr(st, f) for f, _ in GsimGraphStats._fields_})
+        finally:
+            self._L.gsim_graph_destroy(g)
+        return indptr, indices, scores
+
     def make_search_buffers(self, nq, k):
         """Preallocated outputs for :meth:`search_into` (latency-sensitive callers)."""
         return (np.zeros((nq, max(k, 1)), dtype=HIT_DTYPE), np.zeros(nq, dtype=np.uint32),
@@ -351,6 +387,22 @@ class Table:
         w = C.c_uint32(0)
         check(self._L.gsim_debug_query_flags(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8)), n, C.byref(w)))
         return out[:w.value]
+
+
+def butina(indptr, indices):
+    """gsim_butina (host code): Taylor-Butina clustering of a symmetric CSR graph -> (cluster_of uint32 [n],
+    centroids uint32 [nclusters]); cluster ids follow creation order (include/gpusim_hip.h states the rule)."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.uint64)
+    indices = np.ascontiguousarray(indices, dtype=np.uint32)
+    n = len(indptr) - 1
+    if n < 0:
+        raise GsimError(-1, "indptr needs at least one entry")
+    cluster_of = np.empty(n, dtype=np.uint32)
+    centroids = np.empty(max(n, 1), dtype=np.uint32)
+    nc = C.c_uint64(0)
+    check(load().gsim_butina(indptr.ctypes.data_as(C.POINTER(C.c_uint64)), _u32(indices), n, _u32(cluster_of),
+                             _u32(centroids), C.byref(nc)))
+    return cluster_of, centroids[:nc.value].copy()
 
 
 def litmus(test: int, workgroups: int = 256, iterations: int = 100000, device: int = 0) -> dict:

@@ -185,6 +185,10 @@ struct Shard {
     size_t merged_bytes = 0;
     hipEvent_t gather_ev = nullptr;    // loop-back comm (aliased devices): "this shard's block is in its slot"
     hipEvent_t cev[3] = {};            // first shard, timing: scan done / gather done / merge done
+    // gsim_db_neighbors: the pair buffer (sort keys + scores), grown to what a call needed and kept for the next one
+    unsigned long long* d_nbr_keys = nullptr;
+    float* d_nbr_vals = nullptr;
+    uint64_t nbr_cap = 0;
 };
 
 } // namespace gsim_host

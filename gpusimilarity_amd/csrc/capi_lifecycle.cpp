@@ -123,6 +123,8 @@ int free_shard(Shard& s)
     if (s.d_large) (void) hipFree(s.d_large);
     if (s.d_lk) (void) hipFree(s.d_lk);
     if (s.d_bincur) (void) hipFree(s.d_bincur);
+    if (s.d_nbr_keys) (void) hipFree(s.d_nbr_keys);
+    if (s.d_nbr_vals) (void) hipFree(s.d_nbr_vals);
     for (auto& sl : s.slot)
         if (sl.ev) (void) hipEventDestroy(sl.ev);
     if (s.d_pub) (void) hipFree(s.d_pub);

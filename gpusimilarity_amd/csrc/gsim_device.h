@@ -322,6 +322,35 @@ hipError_t launch_prefilter_table(int tversky, float alpha, float beta, uint32_t
                                   float* d_out, hipStream_t s);
 void prefilter_table_host(int tversky, float alpha, float beta, uint32_t max_qa, int has_cutoff, float cutoff, float* out);
 
+// ---- all-pairs neighbour lists (gsim_neighbors.hip, gsim_db_neighbors) --------------------------------------------------
+constexpr int kNbrTile = 256;      // left rows x right rows of one workgroup's tile
+constexpr int kNbrBlock = 256;     // 4 waves, 64 right rows each
+constexpr uint32_t kNbrMaxWords = 128; // 4096-bit rows
+struct NbrArgs {
+    const uint32_t* rows;        // nrows x WP words, 16-byte aligned (the table itself when W == WP, else a zero-padded copy)
+    const uint32_t* pop;         // popc of every row
+    uint64_t nrows;
+    uint64_t row_begin, row_end; // left rows
+    uint32_t WP;                 // words per row as the kernel reads them (4, 8, ... 128)
+    int tri;                     // 1: full-table call, upper triangle, every pair appended under both rows
+    int metric;
+    float alpha, beta, cutoff;
+    unsigned long long* keys;    // ((left row - row_begin) << 32) | right row
+    float* vals;                 // score
+    unsigned long long* cursor;  // entries appended so far (keeps counting past cap)
+    uint64_t cap;                // entries keys / vals hold
+    unsigned long long* clk;     // this launch's {s_memtime, wall clock} at the start and end of one tile (nullptr: none)
+};
+uint32_t nbr_padded_words(uint32_t W); // 0: wider than kNbrMaxWords
+hipError_t launch_nbr_prepare(const void* rows, uint64_t nrows, uint32_t W, uint32_t WP, uint32_t* pad, uint32_t* pop, hipStream_t s);
+// tiles (rt0 .. rt0+nrt-1) x (ct0 .. ct0+nct-1), tile row rt = left rows row_begin + rt * kNbrTile ..
+hipError_t launch_nbr_tiles(const NbrArgs& a, uint32_t rt0, uint32_t nrt, uint32_t ct0, uint32_t nct, hipStream_t s);
+hipError_t launch_nbr_snap(const unsigned long long* cursor, unsigned long long* snap, hipStream_t s);
+hipError_t nbr_sort_bytes(uint64_t n, uint32_t end_bit, size_t* bytes);
+hipError_t launch_nbr_csr(void* tmp, size_t tmp_bytes, const unsigned long long* keys, const float* vals, unsigned long long* keys_sorted,
+                          float* vals_sorted, uint64_t n, uint32_t end_bit, uint64_t nrows_out, uint32_t row_base, uint64_t* indptr,
+                          uint32_t* indices, hipStream_t s);
+
 hipError_t launch_generate(void* rows, uint64_t seed, int kind, uint64_t first_row, uint64_t nrows,
                            uint32_t W, hipStream_t s);
 

@@ -107,6 +107,23 @@ class FingerprintDB:
                                           float(similarity_cutoff), **kw)
         return hits[0], int(approx[0])
 
+    def neighbors(self, cutoff: float, metric: int = capi.METRIC_TANIMOTO, alpha: float = 1.0, beta: float = 1.0,
+                  row_begin: int = 0, row_end=None):
+        """Every pair of rows at or above `cutoff` (gsim_db_neighbors) -> CSR (indptr, indices, scores) for the rows
+        [row_begin, row_end), each row's list sorted by column.  No counterpart in the reference."""
+        return self._table.neighbors(float(cutoff), metric, alpha, beta, row_begin, row_end)
+
+    def butina(self, cutoff: float, metric: int = capi.METRIC_TANIMOTO, alpha: float = 1.0, beta: float = 1.0):
+        """Taylor-Butina clustering at `cutoff` -> one tuple per cluster in creation order: the centroid first, then
+        its members ascending (the shape of RDKit's Butina.ClusterData result)."""
+        indptr, indices, _ = self.neighbors(cutoff, metric, alpha, beta)
+        cluster_of, centroids = capi.butina(indptr, indices)
+        members = [[] for _ in range(len(centroids))]
+        for r, c in enumerate(cluster_of.tolist()):
+            if r != centroids[c]:
+                members[c].append(r)
+        return [(int(c),) + tuple(m) for c, m in zip(centroids.tolist(), members)]
+
     def search_cpu(self, query, dbkey: str, max_return_count: int, similarity_cutoff: float
                    ) -> Tuple[List[bytes], List[bytes], List[float]]:
         """fingerprintdb_cuda.cpp:20-54 (cutoff ignored, approx not produced)."""

@@ -313,6 +313,54 @@ int gsim_db_set_comm(gsim_db* db, gsim_comm* comm);
  * device holds all blocks, so any of them can). */
 int gsim_db_set_comm_root(gsim_db* db, int shard);
 
+/* ---- all-pairs neighbour lists (similarity self-join) and Taylor-Butina clustering ---------------------------------------------- */
+/* gsim_db_neighbors: every pair of rows whose similarity is at or above `cutoff` (no counterpart in the reference, which only
+ * answers top-k queries).  Single-shard, unfolded handles only (GSIM_ERR_STATE otherwise: multi-shard handles, folded tables, a
+ * table not yet on a GPU); tables from gsim_db_generate and gsim_db_attach_device_rows work, no host copy is needed.  For the rows
+ * [row_begin, row_end) of a handle with N rows:
+ *   - row i's list holds every row j != i with score(query = row i, row j) >= cutoff, where the score is bit for bit the `score`
+ *     gsim_db_search returns for that pair.  Tanimoto 0/0 is NaN, so an all-zero row is nobody's neighbour; identical rows
+ *     (score 1.0) are neighbours;
+ *   - cutoff must be in (0, 1] (cutoff <= 0 would be N^2 output): GSIM_ERR_INVALID otherwise;
+ *   - metrics: GSIM_METRIC_TANIMOTO, and GSIM_METRIC_TVERSKY with alpha == beta (symmetric; 0.5 / 0.5 is Dice).  Asymmetric
+ *     Tversky is GSIM_ERR_INVALID;  rows of up to 4096 bits (wider: GSIM_ERR_INVALID);
+ *   - the result is CSR: indptr[row_end - row_begin + 1] (uint64), indices (uint32: the row plus the handle's row base, as in
+ *     gsim_hit.row), scores (float).  Each row's list is sorted by column, ascending; the output is byte-identical from run to run;
+ *   - a full-table call (0, N) computes each unordered pair once (the upper triangle) and lists it under both rows: exact for both
+ *     metrics, because swapping the rows swaps a + b (Tanimoto) or the two Tversky terms (alpha == beta) and f32 addition commutes.
+ *     Any other range computes the rectangle [row_begin, row_end) x [0, N); pieces of a table give the full call's lists.
+ * Runs on the handle's stream under the handle's one-call-at-a-time rule, and leaves the search state as it was.  The handle keeps
+ * its pair buffer (12 bytes per listed pair) for the next call. */
+typedef struct gsim_graph gsim_graph;
+typedef struct {
+    uint64_t launches;       /* tile-kernel launches of the call (each covers a bounded piece of the pair space)             */
+    uint64_t launches_rerun; /* ... run once more because the pair buffer overflowed (it grows to the exact size first)     */
+    uint64_t pairs;          /* pairs found: unordered pairs for a full-table call, listed entries for a range              */
+    double tile_ms;          /* HIP events on the handle's stream: all tile-kernel launches, reruns included                */
+    double csr_ms;           /* sort by (row, column) + row offsets, on the device                                          */
+    double d2h_ms;           /* CSR into host memory                                                                        */
+    double wall_ms;          /* the whole call, host clock                                                                  */
+    double clock_mhz;        /* shader clock the tile kernel ran at: s_memtime cycles over the 100 MHz wall clock, summed over
+                                one full tile of every launch                                                                */
+} gsim_graph_stats;
+int gsim_db_neighbors(gsim_db* db, float cutoff, int metric, float alpha, float beta, uint64_t row_begin, uint64_t row_end,
+                      gsim_graph** out);
+int gsim_graph_shape(const gsim_graph* g, uint64_t* nrows, uint64_t* nnz);
+/* indptr: nrows + 1 entries; indices, scores: nnz entries (either may be NULL) */
+int gsim_graph_copy(const gsim_graph* g, uint64_t* indptr, uint32_t* indices, float* scores);
+int gsim_graph_get_stats(const gsim_graph* g, gsim_graph_stats* out);
+int gsim_graph_destroy(gsim_graph* g);
+/* Taylor-Butina clustering of a symmetric CSR graph (host code, no device; e.g. gsim_db_neighbors' output with row base 0).
+ * Rule (RDKit's Butina.ClusterData order: it sorts (count, index) tuples in reverse):
+ *   - candidates are taken in order of (neighbour count descending, row index descending);
+ *   - a candidate that is already assigned is skipped;
+ *   - otherwise it becomes a centroid, and it and all its still-unassigned neighbours form the next cluster;
+ *   - cluster ids follow creation order.
+ * cluster_of[nrows] receives each row's cluster id, centroids[0 .. *nclusters) the centroid of each cluster (capacity nrows).
+ * GSIM_ERR_INVALID for a malformed graph (indptr not starting at 0 or decreasing, a column >= nrows). */
+int gsim_butina(const uint64_t* indptr, const uint32_t* indices, uint64_t nrows, uint32_t* cluster_of, uint32_t* centroids,
+                uint64_t* nclusters);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
