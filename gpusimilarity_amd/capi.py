@@ -43,6 +43,11 @@ class GsimGraphStats(C.Structure):
                 ("csr_ms", C.c_double), ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
 
 
+class GsimMaxMinStats(C.Structure):
+    _fields_ = [("picks", C.c_uint64), ("launches", C.c_uint64), ("rows_updated", C.c_uint64), ("kernel_ms", C.c_double),
+                ("d2h_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -62,6 +67,7 @@ EXPORTS = [
     "gsim_comm_create", "gsim_comm_destroy", "gsim_comm_size", "gsim_rccl_info", "gsim_db_set_comm", "gsim_db_set_comm_root",
     "gsim_db_enable_timing",
     "gsim_db_neighbors", "gsim_graph_shape", "gsim_graph_copy", "gsim_graph_get_stats", "gsim_graph_destroy", "gsim_butina",
+    "gsim_db_maxmin",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -143,6 +149,8 @@ def load():
         "gsim_graph_get_stats": (C.c_int, [vp, C.POINTER(GsimGraphStats)]),
         "gsim_graph_destroy": (C.c_int, [vp]),
         "gsim_butina": (C.c_int, [u64p, u32p, C.c_uint64, u32p, u32p, u64p]),
+        "gsim_db_maxmin": (C.c_int, [vp, C.c_uint32, u32p, C.c_uint32, C.c_int, C.c_float, C.c_float, C.c_float, u32p,
+                                     C.POINTER(C.c_float), u32p, C.POINTER(C.c_float), u32p, C.POINTER(GsimMaxMinStats)]),
         "gsim_last_error": (C.c_char_p, []),
         "gsim_version": (C.c_char_p, []),
     }
@@ -307,6 +315,29 @@ class Table:
         finally:
             self._L.gsim_graph_destroy(g)
         return indptr, indices, scores
+
+    def maxmin(self, npicks, seeds=(), metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, max_score=1.0, assign=False, stats=None):
+        """gsim_db_maxmin: MaxMin diversity picking, one pass over the table per pick -> (picks uint32 (+ row base),
+        pick_scores float32), both of length npicked; assign=True also returns (row_score float32 [N], nearest uint32 [N]).
+        `stats`: a dict that receives the call's gsim_maxmin_stats."""
+        sd = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+        picks = np.zeros(max(npicks, 1), dtype=np.uint32)
+        scores = np.zeros(max(npicks, 1), dtype=np.float32)
+        n = C.c_uint32(0)
+        fp = C.POINTER(C.c_float)
+        row_score = nearest = None
+        if assign:
+            row_score = np.empty(self.count(), dtype=np.float32)
+            nearest = np.empty(self.count(), dtype=np.uint32)
+        st = GsimMaxMinStats()
+        check(self._L.gsim_db_maxmin(self._h, npicks, _u32(sd) if len(sd) else None, len(sd), metric, alpha, beta, max_score,
+                                     _u32(picks), scores.ctypes.data_as(fp), C.byref(n),
+                                     row_score.ctypes.data_as(fp) if assign else None, _u32(nearest) if assign else None,
+                                     C.byref(st)))
+        if stats is not None:
+            stats.update({f: getattr(st, f) for f, _ in GsimMaxMinStats._fields_})
+        out = (picks[:n.value].copy(), scores[:n.value].copy())
+        return out + (row_score, nearest) if assign else out
 
     def make_search_buffers(self, nq, k):
         """Preallocated outputs for :meth:`search_into` (latency-sensitive callers)."""

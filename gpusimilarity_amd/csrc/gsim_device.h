@@ -351,6 +351,39 @@ hipError_t launch_nbr_csr(void* tmp, size_t tmp_bytes, const unsigned long long*
                           float* vals_sorted, uint64_t n, uint32_t end_bit, uint64_t nrows_out, uint32_t row_base, uint64_t* indptr,
                           uint32_t* indices, hipStream_t s);
 
+// ---- MaxMin diversity picking (gsim_maxmin.hip, gsim_db_maxmin) ----------------------------------------------------------
+// ctl words of a call (zeroed by the host before the first pass; the ticket on its own 128-byte line)
+constexpr uint32_t kMaxMinDone = 0;    // 1: picking has ended (early stop or no unpicked row left); later passes return at once
+constexpr uint32_t kMaxMinPicked = 1;  // picks made so far
+constexpr uint32_t kMaxMinTicket = 32; // workgroups of the current pass that have finished (the last one selects and re-zeroes it)
+constexpr uint32_t kMaxMinUpdated = 64; // (u64) rows whose maxsim strictly increased, summed over passes
+constexpr uint32_t kMaxMinCtlWords = 96;
+struct MaxMinArgs {
+    const void* rows;            // the whole table, nrows x W words
+    uint64_t nrows;
+    uint32_t W;
+    int metric;
+    float alpha, beta;
+    float max_score;
+    float* maxsim;               // nrows: largest score against the picks so far (-1 before pick 0), +inf for a picked row
+    uint32_t* nearest;           // nrows or nullptr: position in picks of the pick that attains maxsim
+    uint32_t* picks;             // npicks rows (without the row base); the seeds are there before the first pass
+    float* pick_scores;          // npicks
+    uint32_t* ctl;               // kMaxMinCtlWords words
+    unsigned long long* partials; // nwg_total: every workgroup's smallest (maxsim bits << 32 | row) of the pass
+    uint32_t npicks, nseeds;
+    uint32_t nwg_total;          // workgroups of one pass over all its launches (the ticket's target)
+};
+// The grid of one launch of a pass over `nrows` rows of width W (the streaming loop's own geometry; nwaves % 4 == 0).
+ScanGeometry maxmin_geometry(uint64_t nrows, uint32_t W, int num_cus);
+// Pass p (the pick whose row is the query) over rows [r0, r0 + nrows) -- g = maxmin_geometry(nrows, ...), r0 a multiple of 64 --
+// whose workgroups are numbered wg0, wg0 + 1, ... within the pass.
+hipError_t launch_maxmin_pass(const MaxMinArgs& m, const ScanGeometry& g, uint64_t r0, uint64_t nrows, uint32_t wg0, uint32_t p,
+                              hipStream_t s);
+// ... the same kernels with default-policy table loads (gsim_maxmin_cached.hip): for tables that fit the Infinity Cache
+hipError_t launch_maxmin_pass_cached(const MaxMinArgs& m, const ScanGeometry& g, uint64_t r0, uint64_t nrows, uint32_t wg0, uint32_t p,
+                                     hipStream_t s);
+
 hipError_t launch_generate(void* rows, uint64_t seed, int kind, uint64_t first_row, uint64_t nrows,
                            uint32_t W, hipStream_t s);
 

@@ -16,7 +16,11 @@ __device__ __forceinline__ u32x4 stream_load(const u32x4* p)
 {
     // read once: keep it out of the caches' way (+13 % on tables far larger than the caches; default-policy loads
     // for tables that fit the 256 MB Infinity Cache were tried on repeated queries over 1 M rows: no gain)
+#ifdef GSIM_STREAM_LOAD_DEFAULT_POLICY
+    return *p; // (a translation unit that defines it: default-policy loads)
+#else
     return __builtin_nontemporal_load(p);
+#endif
 }
 
 // LPR = 16-byte lanes per fingerprint (fp_bits / 128), U = loads per lane per chunk.

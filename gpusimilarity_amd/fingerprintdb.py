@@ -124,6 +124,20 @@ class FingerprintDB:
                 members[c].append(r)
         return [(int(c),) + tuple(m) for c, m in zip(centroids.tolist(), members)]
 
+    def maxmin(self, npicks: int, seeds=(), metric: int = capi.METRIC_TANIMOTO, alpha: float = 1.0, beta: float = 1.0,
+               max_score: float = 1.0, assign: bool = False):
+        """MaxMin diversity picking (gsim_db_maxmin) -> the picked rows, in pick order.  assign=True: (picks, clusters),
+        one tuple per pick -- the pick first, then the rows whose nearest pick it is, ascending (the shape of butina())."""
+        out = self._table.maxmin(int(npicks), seeds, metric, alpha, beta, float(max_score), assign)
+        picks = out[0].tolist()
+        if not assign:
+            return picks
+        members = [[] for _ in picks]
+        for r, j in enumerate(out[3].tolist()):
+            if r != picks[j]:
+                members[j].append(r)
+        return picks, [(p,) + tuple(m) for p, m in zip(picks, members)]
+
     def search_cpu(self, query, dbkey: str, max_return_count: int, similarity_cutoff: float
                    ) -> Tuple[List[bytes], List[bytes], List[float]]:
         """fingerprintdb_cuda.cpp:20-54 (cutoff ignored, approx not produced)."""

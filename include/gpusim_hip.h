@@ -361,6 +361,40 @@ int gsim_graph_destroy(gsim_graph* g);
 int gsim_butina(const uint64_t* indptr, const uint32_t* indices, uint64_t nrows, uint32_t* cluster_of, uint32_t* centroids,
                 uint64_t* nclusters);
 
+/* ---- MaxMin diversity picking --------------------------------------------------------------------------------------------------- */
+/* gsim_db_maxmin: `npicks` mutually dissimilar rows of a single-shard, unfolded handle with N rows, by the MaxMin rule (RDKit's
+ * MaxMinPicker; no counterpart in the reference).  One pass over the table per pick, on the device.
+ *   - score(p, i) is bit for bit the `score` gsim_db_search returns for query = row p against row i; a NaN score (0/0: both rows
+ *     all-zero) counts as 0.0.  Metrics: GSIM_METRIC_TANIMOTO, and GSIM_METRIC_TVERSKY with alpha == beta, finite and >= 0 (then
+ *     every score is in [0, 1] or NaN);
+ *   - picks 0 .. nseeds-1 are the seeds (rows including the row base), in the order given; with nseeds == 0 pick 0 is row 0;
+ *   - every later pick is the unpicked row i with the smallest maxsim[i] = max over the earlier picks p of score(p, i), ties to
+ *     the lowest row.  (Smallest maximum similarity is RDKit's largest minimum distance: 1 - s is exact in double for every
+ *     score of this engine, 0 or c / den with integer operands <= 65 535.)  The result does not depend on reduction order;
+ *   - max_score in [0, 1]: picking ends before the first non-seed candidate whose maxsim > max_score (1.0: never early);
+ *     *npicked = the number of picks made.  Duplicates of picks are picked too, in their turn (maxsim 1.0);
+ *   - picks[j] = the row plus the handle's row base (as gsim_hit.row); pick_scores[j] (or NULL) = the maxsim of pick j when it was
+ *     picked, its largest score against picks 0 .. j-1 (0.0 for pick 0; seeds too);
+ *   - row_score[N] and nearest[N] (either may be NULL): every row's final maxsim, and the position in picks of the pick that
+ *     attains it (ties to the earliest pick: only a strictly greater score moves it).  A picked row reports 1.0 and its own
+ *     position.  Together: an assignment of every row to its nearest diverse centroid.
+ * GSIM_ERR_INVALID, checked before any device state: npicks > N, nseeds > npicks, a seed outside [row_base, row_base + N) or
+ * repeated, max_score outside [0, 1] or NaN, an asymmetric Tversky metric or alpha = beta < 0 / not finite, NULL picks / npicked
+ * (or NULL seeds with nseeds > 0), N >= 2^32.  GSIM_ERR_STATE: multi-shard handles, folded tables, a table not on a GPU.
+ * npicks == 0 does nothing.  Runs on the handle's stream under the one-call-at-a-time rule and leaves the search state as it was;
+ * device memory for the call (4 B per row, 8 B with `nearest`) is allocated and freed by the call. */
+typedef struct {
+    uint64_t picks;        /* picks made (seeds included)                                                                     */
+    uint64_t launches;     /* kernel launches of the call (a pass over a long table is cut into launches of <= ~5 ms)         */
+    uint64_t rows_updated; /* sum over passes of the rows whose maxsim strictly increased (their state was stored)           */
+    double kernel_ms;      /* HIP events around all pass launches                                                             */
+    double d2h_ms;         /* outputs to the host                                                                             */
+    double wall_ms;        /* the whole call, host clock                                                                      */
+} gsim_maxmin_stats;
+int gsim_db_maxmin(gsim_db* db, uint32_t npicks, const uint32_t* seeds, uint32_t nseeds, int metric, float alpha, float beta,
+                   float max_score, uint32_t* picks, float* pick_scores, uint32_t* npicked, float* row_score, uint32_t* nearest,
+                   gsim_maxmin_stats* stats);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
