@@ -293,7 +293,7 @@ int search_batched(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_t k
             if (!redo[q]) continue;
             rc = search_one(db, qb + static_cast<size_t>(q) * db->W, k, cutoff, metric, alpha, beta,
                             hits + static_cast<size_t>(base + q) * kout, &counts[base + q],
-                            approx ? &approx[base + q] : nullptr, merged);
+                            approx ? &approx[base + q] : nullptr);
             if (rc != GSIM_OK) return rc;
         }
     }

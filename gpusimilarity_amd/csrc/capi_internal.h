@@ -69,6 +69,23 @@ constexpr size_t kSummBytes = 4096 * 4 + kTicketWords * 4 + static_cast<size_t>(
 constexpr int kQueryRing = 16;
 constexpr int kPipe = 8; // single queries of one gsim_db_search_each call enqueued ahead of the one being waited for (< kQueryRing)
 
+// The launch sequence of a single query on a shard ("Routes of a single query"; plan_query picks it)
+enum class Route : uint8_t { kClassic, kRanked, kPublishBinrank, kPublishRadix };
+// A route's back-off: after a hand-back (a second scan) the next base << min(streak + lead, 6) queries go around it -- the streak
+// with this hand-back (lead 1) or before it (lead 0) -- once the streak is min_streak.  It counts even with GSIM_FUSED_BACKOFF=0.
+struct Backoff {
+    uint32_t base, lead, min_streak, streak = 0, skip = 0;
+    bool take() { return skip > 0 ? (skip--, true) : false; } // route around it this time?
+    void succeeded() { streak = 0; }
+    void handed_back(bool enabled)
+    {
+        const uint32_t e = std::min(streak + lead, 6u);
+        streak = std::min(streak + 1, 6u);
+        if (enabled && streak >= min_streak) skip = base << e;
+    }
+};
+struct ShardBlock { const void* out; uint8_t why; }; // one shard's result block of a query, and its slot's kQ* bits
+
 struct Shard {
     int device = 0;
     int num_cus = 256;
@@ -109,8 +126,6 @@ struct Shard {
     uint32_t large_cap = 0;
     gsim::LargeKState* d_lk = nullptr;
     uint32_t* d_bincur = nullptr;    // kScanBins cursors of launch_fused_binsort (zero between queries) + kScanBins words: the bins' first positions
-    uint32_t binrank_skip = 0;       // large-k queries left that take the radix tail: the bin-ranked one handed a query back (ties)
-    uint32_t binrank_streak = 0;     // ... consecutive times: the skip doubles (16, 32, ... 1024)
     bool classic_ready = false; // candidate / finalist scratch of the four-kernel pipeline (allocated on first use)
     void* d_pub = nullptr;      // single-launch path: the workgroups' published-candidate regions (128 KB each)
     void* d_hdr = nullptr;      // ... and their headers (64 B each)
@@ -122,10 +137,8 @@ struct Shard {
     // how it was enqueued, what its caller waits for, and why it had to be run again.
     struct PipeSlot {
         bool inflight = false;  // enqueued by a synchronous caller and not finished yet (whatever route it took)
-        bool fused = false;     // it went through the single launch, which announces itself in the block's header ...
-        uint32_t epoch = 0;     // ... with this epoch
-        bool publish = false;   // a large-k query scanned by the publishing launch (header flag 2: run it again)
-        bool binrank = false;   // ... and ranked by coarse bin (a hand-back sends the next ones to the radix tail)
+        Route route = Route::kClassic; // how it was enqueued (valid until the next enqueue): kRanked announces itself in the header ...
+        uint32_t epoch = 0;     // ... with this epoch; the publishing routes say "handed back" with header flag 2
         hipEvent_t ev = nullptr; // recorded behind the last kernel of an enqueue that is not the single launch's own: the caller waits
         bool ev_set = false;    // for THIS query, not for the queries enqueued behind it on the stream
         bool rerun = false;     // it ran behind a launch that left the per-query state dirty: not to be trusted, run again
@@ -133,10 +146,10 @@ struct Shard {
     } slot[kPipe];
     char* h_pipe = nullptr;          // kPipe pinned result blocks (gsim_db_search_each)
     size_t h_pipe_block = 0;
-    // Tables whose scores tie heavily (narrow or very sparse fingerprints) make the single-launch path hand every
-    // query back, i.e. scan twice: after consecutive hand-backs the synchronous path skips it for 2, 4, ... 64 queries.
-    uint32_t redo_streak = 0, fused_skip = 0;
-    uint32_t publish_streak = 0, publish_skip = 0; // the same back-off for the publishing launch of k above fused_select_max_k (synchronous callers)
+    // the synchronous routes' back-offs (plan_query takes them, finish_query_sync feeds them): queries skipped after a hand-back
+    Backoff ranked_backoff{1, 1, 2};   // the single launch (scores that tie heavily): 4, 8, ... 64, from two hand-backs in a row
+    Backoff publish_backoff{1, 1, 0};  // the publishing launch: 2, 4, ... 64
+    Backoff binrank_backoff{16, 0, 0}; // the bin-ranked emission (ties in the top bins): 16, 32, ... 1024, by the radix tail instead
     unsigned long long* d_dbg = nullptr; // GSIM_FUSED_DEBUG: per-workgroup phase timestamps
     void* d_result = nullptr;
     size_t result_bytes = 0;
@@ -227,6 +240,9 @@ struct gsim_db {
     unsigned long long rerun_own = 0, rerun_behind = 0, rerun_torn = 0, rerun_publish = 0, backoff_skips = 0;
     size_t query_flags_at = 0;        // ... the query search_one is answering
     std::vector<uint8_t> query_flags; // kQ* bits of every query of the last gsim_db_search / _each call (timing enabled)
+    std::vector<gsim_host::ShardBlock> blocks; // collect_blocks, kept across queries: one query's shard blocks, their hits, list ends
+    std::vector<gsim_hit> merged;
+    std::vector<size_t> merged_ends;
     unsigned long long blocks_checked = 0, blocks_rechecked = 0, blocks_torn = 0; // single launch, synchronous callers: result blocks whose checksum
                                                                // did not match at first sight / never did (re-run)
     gsim_comm* comm = nullptr; // gsim_db_set_comm: shard results meet through an RCCL all-gather + merge_kernel instead of on the host
@@ -267,16 +283,14 @@ constexpr uint32_t kBatchMaxQ = 256; // queries per batch call on a shard (large
 int free_shard(Shard& s);
 int setup_shard(gsim_db* db, Shard& s);
 // capi_query.cpp: the single-query path
-int ensure_classic_scratch(Shard& s);
 int ensure_result_capacity(Shard& s, uint32_t k);
 int enqueue_query(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k, float cutoff, int metric, float alpha, float beta,
                   uint32_t row_base, void* out, bool caller_syncs, QueryMode mode = kAuto, uint32_t pipe_slot = 0);
 int wait_stream(hipStream_t st);
-int wait_event(hipEvent_t ev);
 int finish_query_sync(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k, float cutoff, int metric, float alpha, float beta,
                       uint32_t row_base, void* out, uint32_t pipe_slot = 0);
 int search_one(gsim_db* db, const uint32_t* query, uint32_t k, float cutoff, int metric, float alpha, float beta, gsim_hit* hits,
-               uint32_t* count, uint64_t* approx, std::vector<gsim_hit>& merged);
+               uint32_t* count, uint64_t* approx);
 int check_search_args(gsim_db* db, const uint32_t* queries, int metric);
 // capi_batch.cpp: multi-query passes
 int enqueue_batch(gsim_db* db, Shard& s, const uint32_t* queries, uint32_t nq, uint32_t k, float cutoff, int metric, float alpha,

@@ -1,6 +1,6 @@
-// capi_query.cpp -- the single-query path of the C ABI: the per-query launch sequence on a shard (single launch, or
-// sample -> scan -> compact -> select), completion, the shard fan-out + host merge of FingerprintDB::search
-// (fingerprintdb_cuda.cu:341-381), gsim_db_search / _each / _device.
+// capi_query.cpp -- the single-query path of the C ABI: the route a query takes on a shard (plan_query chooses; the four
+// routes and what their callers wait for: DESIGN.md section 3, "Routes of a single query"), their launch sequences,
+// completion, the shard fan-out + host merge of FingerprintDB::search (fingerprintdb_cuda.cu:341-381), gsim_db_search / _each / _device.
 #include "capi_internal.h"
 
 #include <chrono>
@@ -8,12 +8,10 @@
 namespace gsim_host
 {
 
-// Scratch of the four-kernel pipeline (per-wave candidate segments + finalists: the worst case is
-// every row a candidate, 24 B per row).  The single-launch path keeps its candidates in LDS and
-// needs none of it, so it is only allocated when a query takes the classic pipeline: k above
-// kFusedMaxK, widths without a specialised scan, or a query the single-launch path handed back
-// (heavy ties, adversarial row orders).
-int ensure_classic_scratch(Shard& s)
+// Scratch of the four-kernel pipeline (per-wave candidate segments + finalists: the worst case is every row a candidate, 24 B per
+// row).  The single-launch path keeps its candidates in LDS and needs none of it, so it is only allocated when a query takes the
+// classic pipeline: k above the publishing route's, widths without a specialised scan, or a query handed back.
+static int ensure_classic_scratch(Shard& s)
 {
     if (s.classic_ready) return GSIM_OK;
     GSIM_HIP(set_device(s.device));
@@ -74,18 +72,15 @@ bool fused_applies(const gsim_db* db, const Shard& s, uint32_t k)
 }
 
 // k in (fused_select_max_k, kFusedPublishMaxK]: the single launch scans and publishes (kFusedPublishOnly), the large-k kernels
-// rank what it published.  Rows of 512 bits and more only: the narrow widths want the sampled seed (enqueue_query_impl), and
-// their scan is bound by the per-row arithmetic either way.  From k = 2049, not 8193: the selectors' own ranking of thousands of
-// rows is issue-bound (one wave per SIMD; profiles/EXPERIMENTS.md) -- k = 4096 at 1 M rows 89 us a query inside the launch, 63
-// published and ranked by score bin; k = 8192 103 -> 74 (Morgan-shaped rows 139 -> 76, and nothing is handed back for "too many
-// finalists"); at 100 M rows k = 4096 0.856 -> 0.872 of the roofline.
+// rank what it published -- from k = 2049, as the selectors' own ranking of thousands of rows is issue-bound.
+// Rows of 512 bits and more unless publish_narrow: the narrow widths want the sampled seed (plan_query).
 bool fused_publish_applies(const gsim_db* db, const Shard& s, uint32_t k)
 {
     if (!db->knobs.fused || !db->knobs.fused_publish || k <= static_cast<uint32_t>(db->knobs.fused_select_max_k) || k > static_cast<uint32_t>(db->knobs.fused_publish_max_k) || s.nrows == 0 ||
         !gsim::fused_supported(s.fgeo))
         return false;
     if (s.fgeo.ragged_words || s.fgeo.ragged_loads) return false;
-    if (s.fgeo.lanes_per_row < 4 && !db->knobs.publish_narrow) return false; // (128 / 256-bit rows: seeded like the ranking launch, enqueue_query_impl)
+    if (s.fgeo.lanes_per_row < 4 && !db->knobs.publish_narrow) return false; // (128 / 256-bit rows: seeded like the ranking launch, plan_query)
     if (gsim::fused_summary_keys(s.fgeo.nwaves, k, gsim::fused_publish_max_m(k)) == 0) return false; // (no thresholds: every row would be published)
     if (s.nrows < static_cast<uint64_t>(db->knobs.publish_min_rows_per_k) * k) return false; // (a short table: the thresholds come late and most of it is published)
     if (k > 65536u && s.nrows < 32ull * k) return false; // (measured: 1 M rows, k = 100 000 -- a tenth of the table -- 286 us classic, 303 published)
@@ -95,9 +90,43 @@ bool fused_publish_applies(const gsim_db* db, const Shard& s, uint32_t k)
 
 namespace
 {
-// A synchronous query that does not end in the single launch's self-announcing block is waited for through an event of its
-// own: the stream holds up to kPipe - 1 later queries of a pipelined call, and waiting for IT to drain idled the device between
-// batches of eight (k = 8192 at 1 M rows: 74 us a query for 59 us of kernels).
+// The route of one query on one shard, whether the narrow-row seed runs ahead of the single launch, and the
+// kQSkip* bits of the back-offs that routed it around a launch.  Back-offs are taken for synchronous callers only.
+struct QueryPlan { Route route = Route::kClassic; bool seed = false; uint8_t why = 0; };
+
+QueryPlan plan_query(gsim_db* db, Shard& s, uint32_t k, bool caller_syncs, QueryMode mode)
+{
+    QueryPlan p;
+    if (mode != kAuto) return p;
+    // (k between the knob fused_select_max_k and kFusedMaxK: the single launch could rank it, the publishing route is preferred)
+    if (fused_publish_applies(db, s, k)) {
+        if (caller_syncs && s.publish_backoff.take()) p.why |= kQSkipPublish; // (tables whose publishing launches hand every query back)
+        else p.route = Route::kPublishRadix;
+    }
+    if (p.route == Route::kClassic && fused_applies(db, s, k)) {
+        if (caller_syncs && s.ranked_backoff.take()) p.why |= kQSkipFused;
+        else p.route = Route::kRanked;
+    }
+    if (p.route == Route::kPublishRadix && caller_syncs) {
+        // The caller reads the block, so a hand-back costs a second run, not a wrong answer: bin-ranked emission (two launches, not
+        // the radix tail's four and a gap).  128 / 256-bit rows score coarsely: from k ~ 10 000 on a top bin holds more than the
+        // emission takes (7 % of the k = 32 768 queries of an 8 M x 128-bit soak were handed back), so their large k takes the radix tail.
+        const uint32_t binrank_max = (s.fgeo.lanes_per_row != 0 && s.fgeo.lanes_per_row <= 2) ? std::min<uint32_t>(8192u, static_cast<uint32_t>(db->knobs.largek_binrank_max_k))
+                                                                                             : static_cast<uint32_t>(db->knobs.largek_binrank_max_k);
+        if (k <= binrank_max) {
+            if (s.binrank_backoff.take()) p.why |= kQSkipPublish;
+            else if (db->knobs.largek_binrank) p.route = Route::kPublishBinrank;
+        }
+    }
+    if (p.why) db->backoff_skips++;
+    // Narrow rows (128 / 256 bits): a wave's LDS store (2048 slots) fills before the first in-loop threshold is elected (~12 us), so
+    // sparse tables were handed back (1/64 of the queries at 256 bits, nearly all at 128).  A strided sample first leaves a starting
+    // threshold.  (Ragged word counts too: they never take the publishing routes, and every launch route has k > 0.)
+    const bool narrow = (s.geo.lanes_per_row != 0 && s.geo.lanes_per_row <= 2) || s.fgeo.ragged_words;
+    p.seed = p.route != Route::kClassic && db->knobs.fused_seed_narrow && narrow && s.nrows > 1500ull * s.fgeo.nwaves && s.sample_chunks > 0;
+    return p;
+}
+
 // The tag of a launch's published lists (FusedArgs::pub_tag): never 0 (what the regions hold when they are allocated), and its
 // low 26 bits -- the part a header carries -- never 0 either.
 uint32_t next_pub_tag(Shard& s)
@@ -107,27 +136,162 @@ uint32_t next_pub_tag(Shard& s)
     return s.pub_tag;
 }
 
-int record_slot_event(Shard& s, uint32_t pipe_slot)
+// Large-k device state, zeroed when made (its kernels leave it zero): d_lk, the d_bincur cursors (`bincur`), `large` keys in d_large
+int ensure_largek_scratch(Shard& s, bool bincur, uint32_t large)
 {
-    Shard::PipeSlot& sl = s.slot[pipe_slot];
-    if (!sl.ev) GSIM_HIP(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
-    GSIM_HIP(hipEventRecord(sl.ev, s.stream));
-    sl.ev_set = true;
+    if (large > s.large_cap) {
+        if (s.d_large) GSIM_HIP(hipFree(s.d_large));
+        s.d_large = nullptr;
+        s.large_cap = 0;
+        GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_large), static_cast<size_t>(large) * 8));
+        s.large_cap = large;
+    }
+    if (!s.d_lk) {
+        GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_lk), sizeof(gsim::LargeKState)));
+        GSIM_HIP(hipMemsetAsync(s.d_lk, 0, sizeof(gsim::LargeKState), s.stream));
+    }
+    if (bincur && !s.d_bincur) {
+        GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_bincur), static_cast<size_t>(gsim::kScanBins) * 8)); // (cursors + the layout)
+        GSIM_HIP(hipMemsetAsync(s.d_bincur, 0, static_cast<size_t>(gsim::kScanBins) * 8, s.stream));
+    }
     return GSIM_OK;
 }
 
-// Enqueue one query on one shard; the result block ends up at `out`, which is
-// device memory or device-visible pinned host memory (zero-copy).
-//
-// Single-launch path (fused_applies): ONE kernel does scan + publish + select.  Synchronous
-// callers (caller_syncs) get the query's epoch stored into s.h_done when the block is complete
-// and check header flag 2 ("handed back": re-run with mode kClassic).  Enqueue-only callers
-// (the RCCL path) get the four classic kernels enqueued behind it, gated on QueryState::redo:
-// they return at once unless the single launch handed the query back.
-//
-// Classic path: sample -> scan -> compact -> select.  The query is read by the kernels straight
-// from a pinned ring slot (no upload op) and the last kernel re-zeroes the per-query state (no
-// memset op).  Nothing here synchronises with the host, whatever k.
+// One query's enqueue on one shard: its kernel arguments, where its block goes, its ring slot and the synchronous caller's
+// pipeline slot, and the gsim_timing events (null: timing off; ev[0] before the scan, ev[1] behind it, ev[2] behind the last kernel)
+struct QueryLaunch {
+    gsim_db* db;
+    Shard& s;
+    gsim::ScanArgs a;
+    uint32_t k, row_base, ring, pipe_slot;
+    void* out;
+    bool caller_syncs;
+    hipEvent_t* ev;
+};
+
+// The single launch's arguments: ranking the query, or publishing only (kFusedPublishOnly: M up to fused_publish_max_m, no final threshold)
+gsim::FusedArgs fused_args(const gsim_db* db, Shard& s, uint32_t k, bool publish)
+{
+    gsim::FusedArgs f{};
+    f.pub = s.d_pub;
+    f.hdr = s.d_hdr;
+    f.arrive = s.d_summ + 4096 + kTicketWords;
+    f.summ = s.d_summ;
+    f.summ_keys = publish ? gsim::fused_summary_keys(s.fgeo.nwaves, k, gsim::fused_publish_max_m(k)) : gsim::fused_summary_keys(s.fgeo.nwaves, k);
+    f.final_keys = publish ? 0 : gsim::fused_final_keys(s.fgeo.nwaves / 4, k);
+    f.tickets = s.d_summ + 4096;
+    // grid-wide waits give up after 2 ms + four scan times at 4 TB/s (only reached when the GPU is shared)
+    f.wait_ticks = static_cast<uint32_t>(std::min<uint64_t>(200000ull + static_cast<uint64_t>(s.nrows) * s.W * 4 / 10000ull, 0xFFFFFFFFull));
+    const uint32_t xflags = static_cast<uint32_t>(db->knobs.fused_flags);
+    f.xflags = publish ? (xflags & ~4u) | gsim::kFusedPublishOnly : xflags;
+    f.pub_tag = next_pub_tag(s);
+    return f;
+}
+
+// The narrow-row seed (plan_query): xflags bit 2 says the sample kernel (its own size rule) left a threshold in QueryState::gtau.
+hipError_t seed_threshold(const QueryLaunch& q, gsim::FusedArgs& f)
+{
+    bool seeded = false;
+    const hipError_t e = gsim::launch_sample(q.a, q.s.geo, 1u, q.s.stream, &seeded, q.db->knobs.sample_shift);
+    if (seeded) f.xflags |= 4u;
+    return e;
+}
+
+// Large k: the k-th largest finalist key by a radix select on the device (the finalist count never reaches the host: nothing
+// here waits), the keys at or above it gathered and sorted in global memory (sized by k); `flags` to the emission
+int enqueue_largek_tail(QueryLaunch& q, uint32_t flags)
+{
+    Shard& s = q.s;
+    const uint32_t np2 = next_pow2_u32(q.k);
+    const int rc = ensure_largek_scratch(s, false, np2);
+    if (rc != GSIM_OK) return rc;
+    // (one workgroup in one launch up to 32 Ki finalists, the grid's eight passes beyond, chosen by the finalist
+    // count the previous large-k query left in pinned memory: a wrong guess is slower, never wrong)
+    static_assert(kPipe <= 15, "the large-k hint word shares h_done's 64-byte block with the pipeline's completion words");
+    uint32_t* hint = s.h_done + 15;
+    const bool one_block = *static_cast<volatile uint32_t*>(hint) <= static_cast<uint32_t>(q.db->knobs.largek_one_block_max);
+    GSIM_HIP(gsim::launch_largek_select(q.a, s.d_final, s.final_cap, s.d_lk, s.d_large, np2, hint, one_block, s.stream));
+    // (tiles sorted, then positions by counting + the hits + the header + the state's reset in one launch)
+    GSIM_HIP(gsim::launch_largek_sort_emit(q.a, s.d_large, np2, s.d_lk, q.row_base, s.nrows, flags, q.out, s.stream));
+    return GSIM_OK;
+}
+
+// The four-kernel pipeline: sample -> scan -> compact -> select (`select`) or the large-k tail; gated (a.gate) behind a launch.
+// The kernels read the query from its pinned ring slot (no upload op) and the last one re-zeroes the per-query state (no memset op).
+int enqueue_classic(QueryLaunch& q, bool select, bool mark_scan_start, bool mark_scan_end)
+{
+    Shard& s = q.s;
+    if (s.nrows > 0 && s.sample_chunks > 0)
+        GSIM_HIP(gsim::launch_sample(q.a, s.geo, static_cast<uint32_t>(s.sample_chunks), s.stream, nullptr, q.db->knobs.sample_shift));
+    if (mark_scan_start && q.ev) GSIM_HIP(hipEventRecord(q.ev[0], s.stream));
+    if (s.nrows > 0) GSIM_HIP(gsim::launch_scan(q.a, s.geo, s.stream));
+    if (!q.caller_syncs) { // the ring slot is free once the scan has run
+        GSIM_HIP(hipEventRecord(s.q_ev[q.ring], s.stream));
+        s.q_pending[q.ring] = true;
+    }
+    if (mark_scan_end && q.ev) GSIM_HIP(hipEventRecord(q.ev[1], s.stream));
+    if (s.nrows > 0) GSIM_HIP(gsim::launch_compact(q.a, s.geo, s.d_final, s.d_final_cb, s.final_cap, s.stream));
+    if (!select) return enqueue_largek_tail(q, 1u);
+    GSIM_HIP(gsim::launch_select(q.a, s.d_final, s.d_final_cb, s.final_cap, q.row_base, q.out, s.stream));
+    return GSIM_OK;
+}
+
+// kRanked: ONE kernel does scan + publish + select.  Synchronous callers poll the block's header: the closing workgroup stores
+// {count, flags | epoch << 8, approx} in ONE 16-byte write when the hits are out (a separate completion word meant waiting for
+// its acknowledgement over PCIe: ~1.3 us per query).  Enqueue-only callers get the classic kernels behind it, gated.
+int enqueue_ranked(QueryLaunch& q, bool seed)
+{
+    Shard& s = q.s;
+    gsim::FusedArgs f = fused_args(q.db, s, q.k, false);
+    f.result = q.out;
+    f.row_base = q.row_base;
+    f.done_flag = q.caller_syncs ? s.h_done + q.pipe_slot : nullptr; // (non-null = "the caller polls the header")
+    f.epoch = ++s.epoch & 0xFFFFFFu;
+    if (f.epoch == 0) f.epoch = ++s.epoch & 0xFFFFFFu; // 0: what a clean header holds
+    if (q.caller_syncs) static_cast<gsim_result_header*>(q.out)->flags = 0;
+    if (q.db->knobs.fused_debug && !s.d_dbg) GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_dbg), (static_cast<size_t>(s.fgeo.nwaves / 4) * 24 + 8) * 8));
+    f.dbg = s.d_dbg;
+    if (q.ev) GSIM_HIP(hipEventRecord(q.ev[0], s.stream));
+    if (seed) GSIM_HIP(seed_threshold(q, f));
+    GSIM_HIP(gsim::launch_fused(q.a, s.fgeo, f, s.stream));
+    if (q.ev) GSIM_HIP(hipEventRecord(q.ev[1], s.stream));
+    if (q.caller_syncs) {
+        s.slot[q.pipe_slot].epoch = f.epoch;
+        return GSIM_OK;
+    }
+    q.a.gate = &s.d_state->redo; // the classic kernels behind it run only if it handed the query back
+    return enqueue_classic(q, q.k <= static_cast<uint32_t>(gsim::kSelectCap), false, false);
+}
+
+// kPublishBinrank / kPublishRadix -- large k: the single launch's scan (0.88 of the HBM roofline, the classic scan 0.82 + compaction)
+// stops after publishing, the large-k kernels rank what it published.  A synchronous caller re-runs a hand-back (finish_query_sync)
+// instead of paying for three gated launches, ~4.5 us each, behind every query.
+int enqueue_publish(QueryLaunch& q, Route route, bool seed)
+{
+    Shard& s = q.s;
+    gsim::FusedArgs f = fused_args(q.db, s, q.k, true);
+    const int rc = ensure_largek_scratch(s, true, 0);
+    if (rc != GSIM_OK) return rc;
+    if (q.ev) GSIM_HIP(hipEventRecord(q.ev[0], s.stream));
+    if (seed) GSIM_HIP(seed_threshold(q, f));
+    GSIM_HIP(gsim::launch_fused(q.a, s.fgeo, f, s.stream));
+    q.db->large_k_published++;
+    if (route == Route::kPublishBinrank) {
+        GSIM_HIP(gsim::launch_fused_binsort(q.a, f, s.fgeo.nwaves / 4, s.d_final, s.final_cap, s.d_bincur, s.stream));
+        if (q.ev) GSIM_HIP(hipEventRecord(q.ev[1], s.stream));
+        GSIM_HIP(gsim::launch_binrank_emit(q.a, s.d_final, s.final_cap, s.d_bincur, s.d_lk, q.row_base, s.nrows, 1u, q.out, s.stream));
+        return GSIM_OK;
+    }
+    // the hand-off kernel makes the published lists the finalists
+    GSIM_HIP(gsim::launch_fused_handoff(q.a, f, s.fgeo.nwaves / 4, s.d_final, s.final_cap, s.stream));
+    q.a.gate = &s.d_state->redo;
+    if (!q.caller_syncs) return enqueue_classic(q, false, false, true);
+    if (q.ev) GSIM_HIP(hipEventRecord(q.ev[1], s.stream));
+    return enqueue_largek_tail(q, 1u | 0x80000000u); // (flag 31: no gated kernels ran, a hand-back makes the block say so)
+}
+
+// Enqueue one query on one shard; the result block ends up at `out`, which is device memory or device-visible pinned host memory
+// (zero-copy).  Nothing here synchronises with the host, whatever k.
 int enqueue_query_impl(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k, float cutoff, int metric, float alpha,
                        float beta, uint32_t row_base, void* out, bool caller_syncs, QueryMode mode, uint32_t pipe_slot)
 {
@@ -140,38 +304,20 @@ int enqueue_query_impl(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k,
         if (s.d_bincur) GSIM_HIP(hipMemsetAsync(s.d_bincur, 0, static_cast<size_t>(gsim::kScanBins) * 4, s.stream));
         s.state_dirty = false;
     }
-    // (k between the knob fused_select_max_k and kFusedMaxK: the single launch could rank it, the publishing route is preferred)
-    bool publish = mode == kAuto && fused_publish_applies(db, s, k);
-    uint8_t why = 0;
-    if (publish && caller_syncs && s.publish_skip) { // (tables that make the publishing launch hand every query back: scanned twice)
-        s.publish_skip--;
-        publish = false;
-        why |= kQSkipPublish;
-    }
-    bool fused = mode == kAuto && !publish && fused_applies(db, s, k);
-    if (fused && caller_syncs && s.fused_skip) {
-        s.fused_skip--;
-        fused = false;
-        why |= kQSkipFused;
-    }
-    if (why) db->backoff_skips++;
-    const bool classic = (!fused && !(publish && caller_syncs)) || !caller_syncs;
-    if (classic) {
-        const int rc = ensure_classic_scratch(s);
-        if (rc != GSIM_OK) return rc;
-    } else if (publish) {
-        const int rc = ensure_publish_scratch(s);
-        if (rc != GSIM_OK) return rc;
-    }
-    const uint32_t slot = s.q_next++ % kQueryRing;
-    uint32_t* hq = s.h_query + static_cast<size_t>(slot) * s.W;
-    if (s.q_pending[slot]) { // only set by asynchronous searches
-        GSIM_HIP(hipEventSynchronize(s.q_ev[slot]));
-        s.q_pending[slot] = false;
+    const QueryPlan p = plan_query(db, s, k, caller_syncs, mode);
+    // the four-kernel pipeline's scratch wherever it runs (gated or not); behind a synchronous caller's publishing launch, its finalists'
+    int rc = p.route == Route::kClassic || !caller_syncs ? ensure_classic_scratch(s) : p.route != Route::kRanked ? ensure_publish_scratch(s) : GSIM_OK;
+    if (rc != GSIM_OK) return rc;
+    const uint32_t ring = s.q_next++ % kQueryRing;
+    uint32_t* hq = s.h_query + static_cast<size_t>(ring) * s.W;
+    if (s.q_pending[ring]) { // only set by asynchronous searches
+        GSIM_HIP(hipEventSynchronize(s.q_ev[ring]));
+        s.q_pending[ring] = false;
     }
     std::memcpy(hq, query, static_cast<size_t>(s.W) * 4); // `query` is already folded for a folded table
 
-    gsim::ScanArgs a{};
+    QueryLaunch q{db, s, {}, k, row_base, ring, pipe_slot, out, caller_syncs, nullptr};
+    gsim::ScanArgs& a = q.a;
     a.rows = s.d_rows;
     a.nrows = s.nrows;
     a.W = s.W;
@@ -186,15 +332,12 @@ int enqueue_query_impl(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k,
     a.cand = s.d_cand;
     a.cand_cb = s.d_cand_cb;
     a.seg_count = s.d_seg_count;
-    a.state = s.d_state;
-    a.gate = nullptr;
+    a.state = s.d_state; // (a.gate: null, set behind a launch)
     if (s.geo.lanes_per_row == 0 || s.nrows == 0) {
         // generic-width scan reads the query per word: give it a device copy
         GSIM_HIP(hipMemcpyAsync(s.d_query, hq, static_cast<size_t>(s.W) * 4, hipMemcpyHostToDevice, s.stream));
         a.query = s.d_query;
     }
-
-    hipEvent_t* ev = nullptr;
     if (db->timing && s.ev_used < kTimingRing) {
         if (s.ev.size() < static_cast<size_t>(3 * (s.ev_used + 1))) {
             for (int i = 0; i < 3; i++) {
@@ -203,177 +346,34 @@ int enqueue_query_impl(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k,
                 s.ev.push_back(e);
             }
         }
-        ev = &s.ev[3 * s.ev_used];
+        q.ev = &s.ev[3 * s.ev_used];
     }
     if (caller_syncs) {
-        sl.fused = false;
-        sl.publish = false;
-        sl.binrank = false;
+        sl.route = p.route;
         sl.ev_set = false;
         sl.rerun = false; // (a slot is enqueued again only after it was finished: a flag still set here is stale -- ADVICE r05)
         sl.inflight = true;
-        if (mode == kAuto) sl.why = why; // (a re-run, kClassic, keeps what the first run recorded)
+        if (mode == kAuto) sl.why = p.why; // (a re-run, kClassic, keeps what the first run recorded)
     }
-    if (fused) {
-        gsim::FusedArgs f{};
-        f.pub = s.d_pub;
-        f.hdr = s.d_hdr;
-        f.arrive = s.d_summ + 4096 + kTicketWords;
-        f.summ = s.d_summ;
-        f.summ_keys = gsim::fused_summary_keys(s.fgeo.nwaves, k);
-        f.final_keys = gsim::fused_final_keys(s.fgeo.nwaves / 4, k);
-        f.tickets = s.d_summ + 4096;
-        f.result = out;
-        f.row_base = row_base;
-        // Synchronous callers poll the result block's own header: the closing workgroup stores {count, flags | epoch << 8,
-        // approx} in ONE 16-byte write when the hits are out (a separate completion word meant waiting for the header's
-        // acknowledgement over PCIe first: ~1.3 us per query); finish_query_sync clears the epoch bits again.
-        f.done_flag = caller_syncs ? s.h_done + pipe_slot : nullptr; // (non-null = "the caller polls the header")
-        f.epoch = ++s.epoch & 0xFFFFFFu;
-        if (f.epoch == 0) f.epoch = ++s.epoch & 0xFFFFFFu; // 0: what a clean header holds
-        f.pub_tag = next_pub_tag(s);
-        if (caller_syncs) static_cast<gsim_result_header*>(out)->flags = 0;
-        const int dbg_on = db->knobs.fused_debug;
-        if (dbg_on && !s.d_dbg) GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_dbg), (static_cast<size_t>(s.fgeo.nwaves / 4) * 24 + 8) * 8));
-        f.dbg = s.d_dbg;
-        // grid-wide waits give up after 2 ms + four scan times at 4 TB/s (only reached when the GPU is shared)
-        f.wait_ticks = static_cast<uint32_t>(std::min<uint64_t>(200000ull + static_cast<uint64_t>(s.nrows) * s.W * 4 / 10000ull, 0xFFFFFFFFull));
-        const int xflags = db->knobs.fused_flags;
-        f.xflags = static_cast<uint32_t>(xflags);
-        if (ev) GSIM_HIP(hipEventRecord(ev[0], s.stream));
-        // Narrow rows (128 / 256 bits): a wave meets 512 / 256 rows per trip and its LDS store (2048 slots) is full after a
-        // few trips -- before the first in-loop threshold has been elected (~12 us) -- so that sparse tables were handed back
-        // (1/64 of the queries at 256 bits, nearly all at 128: scanned twice).  A strided sample first (K0: the
-        // four-kernel pipeline's own) leaves a valid starting threshold in QueryState::gtau as a coarse BIN; the single
-        // launch turns it into a score key (xflags bit 2).
-        const int seed_narrow = db->knobs.fused_seed_narrow;
-        if (seed_narrow && ((s.geo.lanes_per_row != 0 && s.geo.lanes_per_row <= 2) || s.fgeo.ragged_words) && s.nrows > 1500ull * s.fgeo.nwaves &&
-            s.sample_chunks > 0 && k > 0) {
-            bool seeded = false;
-            GSIM_HIP(gsim::launch_sample(a, s.geo, 1u, s.stream, &seeded, db->knobs.sample_shift)); // (sample_rows_kernel: 64 Ki ... 1 Mi rows, by k and the table)
-            if (seeded) f.xflags |= 4u; // (the launcher has its own size rule: the flag says a threshold WAS left in gtau)
-        }
-        GSIM_HIP(gsim::launch_fused(a, s.fgeo, f, s.stream));
-        if (ev) GSIM_HIP(hipEventRecord(ev[1], s.stream));
-        if (caller_syncs) {
-            sl.fused = true;
-            sl.epoch = f.epoch;
-            if (ev) {
-                GSIM_HIP(hipEventRecord(ev[2], s.stream));
-                s.ev_used++;
-            }
-            return GSIM_OK;
-        }
-        a.gate = &s.d_state->redo; // the classic kernels behind it run only if it handed the query back
+    switch (p.route) {
+    case Route::kRanked: rc = enqueue_ranked(q, p.seed); break;
+    case Route::kPublishBinrank:
+    case Route::kPublishRadix: rc = enqueue_publish(q, p.route, p.seed); break;
+    case Route::kClassic: rc = enqueue_classic(q, k <= static_cast<uint32_t>(gsim::kSelectCap), true, true); break;
     }
-    if (publish) {
-        // large k, first half: the single launch's scan with its in-loop thresholds (one read of the table at 0.88 of the HBM
-        // roofline instead of the classic scan's 0.82 + compaction), told to stop after publishing; the hand-off kernel makes
-        // its lists the finalists.  The classic kernels follow, gated as above: they run only for a query handed back.
-        gsim::FusedArgs f{};
-        f.pub = s.d_pub;
-        f.hdr = s.d_hdr;
-        f.arrive = s.d_summ + 4096 + kTicketWords;
-        f.summ = s.d_summ;
-        f.summ_keys = gsim::fused_summary_keys(s.fgeo.nwaves, k, gsim::fused_publish_max_m(k));
-        f.final_keys = 0; // (no end-of-scan reports: nobody elects a final threshold)
-        f.tickets = s.d_summ + 4096;
-        f.wait_ticks = static_cast<uint32_t>(std::min<uint64_t>(200000ull + static_cast<uint64_t>(s.nrows) * s.W * 4 / 10000ull, 0xFFFFFFFFull));
-        f.xflags = (static_cast<uint32_t>(db->knobs.fused_flags) & ~4u) | gsim::kFusedPublishOnly;
-        f.pub_tag = next_pub_tag(s);
-        if (!s.d_lk) {
-            GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_lk), sizeof(gsim::LargeKState)));
-            GSIM_HIP(hipMemsetAsync(s.d_lk, 0, sizeof(gsim::LargeKState), s.stream));
-        }
-        if (!s.d_bincur) {
-            GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_bincur), static_cast<size_t>(gsim::kScanBins) * 8)); // (cursors + the layout)
-            GSIM_HIP(hipMemsetAsync(s.d_bincur, 0, static_cast<size_t>(gsim::kScanBins) * 8, s.stream));
-        }
-        if (ev) GSIM_HIP(hipEventRecord(ev[0], s.stream));
-        // narrow rows: the sampled seed, as for the ranking launch above (a wave's store fills before the first election otherwise)
-        if (db->knobs.fused_seed_narrow && s.geo.lanes_per_row != 0 && s.geo.lanes_per_row <= 2 && s.nrows > 1500ull * s.fgeo.nwaves && s.sample_chunks > 0) {
-            bool seeded = false;
-            GSIM_HIP(gsim::launch_sample(a, s.geo, 1u, s.stream, &seeded, db->knobs.sample_shift));
-            if (seeded) f.xflags |= 4u;
-        }
-        GSIM_HIP(gsim::launch_fused(a, s.fgeo, f, s.stream));
-        db->large_k_published++;
-        if (caller_syncs) {
-            sl.publish = true;
-            // The caller reads the block: a hand-back costs a second run, not a wrong answer -- so the finalists are placed by coarse
-            // bin and ranked inside their bins (two launches; the radix select + gather + sort are four and a gap).  Tables whose
-            // top bins hold more than kBinRankCap rows (ties) hand that back: the next large-k queries take the radix tail.
-            // (128 / 256-bit rows score coarsely: from k ~ 10 000 on a top bin holds more than the emission takes -- 7 % of the k = 32 768
-            // queries of an 8 M x 128-bit soak were handed back for it; their large k goes straight to the radix tail)
-            const uint32_t binrank_max = (s.fgeo.lanes_per_row != 0 && s.fgeo.lanes_per_row <= 2) ? std::min<uint32_t>(8192u, static_cast<uint32_t>(db->knobs.largek_binrank_max_k))
-                                                                                                 : static_cast<uint32_t>(db->knobs.largek_binrank_max_k);
-            if (db->knobs.largek_binrank && s.binrank_skip == 0 && k <= binrank_max) {
-                GSIM_HIP(gsim::launch_fused_binsort(a, f, s.fgeo.nwaves / 4, s.d_final, s.final_cap, s.d_bincur, s.stream));
-                if (ev) GSIM_HIP(hipEventRecord(ev[1], s.stream));
-                GSIM_HIP(gsim::launch_binrank_emit(a, s.d_final, s.final_cap, s.d_bincur, s.d_lk, row_base, s.nrows, 1u, out, s.stream));
-                sl.binrank = true;
-                if (ev) {
-                    GSIM_HIP(hipEventRecord(ev[2], s.stream));
-                    s.ev_used++;
-                }
-                return record_slot_event(s, pipe_slot);
-            }
-            if (s.binrank_skip && k <= binrank_max) {
-                s.binrank_skip--;
-                sl.why |= kQSkipPublish;
-                db->backoff_skips++;
-            }
-        }
-        GSIM_HIP(gsim::launch_fused_handoff(a, f, s.fgeo.nwaves / 4, s.d_final, s.final_cap, s.stream));
-        a.gate = &s.d_state->redo;
-    }
-    // (a synchronous caller of the publishing launch learns of a hand-back from the block's header and runs the query again --
-    // finish_query_sync -- instead of paying for three gated launches, ~4.5 us each, behind every query)
-    const bool scan_classic = !(publish && caller_syncs);
-    if (scan_classic && s.nrows > 0 && s.sample_chunks > 0)
-        GSIM_HIP(gsim::launch_sample(a, s.geo, static_cast<uint32_t>(s.sample_chunks), s.stream, nullptr, db->knobs.sample_shift));
-    if (ev && !fused && !publish) GSIM_HIP(hipEventRecord(ev[0], s.stream));
-    if (scan_classic && s.nrows > 0) GSIM_HIP(gsim::launch_scan(a, s.geo, s.stream));
-    if (!caller_syncs) { // the ring slot is free once the scan has run
-        GSIM_HIP(hipEventRecord(s.q_ev[slot], s.stream));
-        s.q_pending[slot] = true;
-    }
-    if (ev && !fused) GSIM_HIP(hipEventRecord(ev[1], s.stream));
-    if (scan_classic && s.nrows > 0) GSIM_HIP(gsim::launch_compact(a, s.geo, s.d_final, s.d_final_cb, s.final_cap, s.stream));
-    if (k <= static_cast<uint32_t>(gsim::kSelectCap) && !publish) {
-        GSIM_HIP(gsim::launch_select(a, s.d_final, s.d_final_cb, s.final_cap, row_base, out, s.stream));
-    } else {
-        // large k: the k-th largest finalist key by a radix select on the device (the finalist count never reaches the
-        // host: nothing here waits), the keys at or above it gathered and sorted in global memory (sized by k)
-        const uint32_t np2 = next_pow2_u32(k);
-        if (np2 > s.large_cap) {
-            if (s.d_large) GSIM_HIP(hipFree(s.d_large));
-            s.d_large = nullptr;
-            s.large_cap = 0;
-            GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_large), static_cast<size_t>(np2) * 8));
-            s.large_cap = np2;
-        }
-        if (!s.d_lk) {
-            GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_lk), sizeof(gsim::LargeKState)));
-            GSIM_HIP(hipMemsetAsync(s.d_lk, 0, sizeof(gsim::LargeKState), s.stream));
-        }
-        // (the route by the finalist count of the previous large-k query, left in pinned memory by its kernels: one workgroup in
-        // one launch -- two reads of the finalists, the radix passes in LDS over the keys of the boundary bin: select + gather
-        // 56 us instead of 87 at k = 10 000 -- up to 32 Ki finalists, the grid's eight passes + gather beyond (52 k finalists, a
-        // boundary bin of more than 16 Ki keys: 121 us either way).  A wrong guess is slower, never wrong)
-        const int one_block_max = db->knobs.largek_one_block_max;
-        static_assert(kPipe <= 15, "the large-k hint word shares h_done's 64-byte block with the pipeline's completion words");
-        uint32_t* hint = s.h_done + 15;
-        const bool one_block = *static_cast<volatile uint32_t*>(hint) <= static_cast<uint32_t>(one_block_max);
-        GSIM_HIP(gsim::launch_largek_select(a, s.d_final, s.final_cap, s.d_lk, s.d_large, np2, hint, one_block, s.stream));
-        // (tiles sorted, then positions by counting + the hits + the header + the state's reset in one launch)
-        GSIM_HIP(gsim::launch_largek_sort_emit(a, s.d_large, np2, s.d_lk, row_base, s.nrows, 1u | (publish && caller_syncs ? 0x80000000u : 0u), out, s.stream));
-    }
-    if (ev) {
-        GSIM_HIP(hipEventRecord(ev[2], s.stream));
+    if (rc != GSIM_OK) return rc;
+    if (q.ev) {
+        GSIM_HIP(hipEventRecord(q.ev[2], s.stream));
         s.ev_used++;
     }
-    return caller_syncs ? record_slot_event(s, pipe_slot) : GSIM_OK;
+    if (!caller_syncs || p.route == Route::kRanked) return GSIM_OK; // (kRanked announces itself in the block's header)
+    // A synchronous query that does not end in the single launch's self-announcing block is waited for through an event of its
+    // own: the stream holds up to kPipe - 1 later queries of a pipelined call, and waiting for IT to drain idled the device between
+    // batches of eight (k = 8192 at 1 M rows: 74 us a query for 59 us of kernels).
+    if (!sl.ev) GSIM_HIP(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+    GSIM_HIP(hipEventRecord(sl.ev, s.stream));
+    sl.ev_set = true;
+    return GSIM_OK;
 }
 } // namespace
 
@@ -387,7 +387,7 @@ int enqueue_query(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k, floa
 
 // Wait for a stream: poll for a short while (a query takes ~2 ms and the blocking
 // wait's interrupt wake-up costs 10-20 us), then block.
-int wait_event(hipEvent_t ev)
+static int wait_event(hipEvent_t ev)
 {
     for (int i = 0; i < 200000; i++) {
         hipError_t e = hipEventQuery(ev);
@@ -409,65 +409,11 @@ int wait_stream(hipStream_t st)
     return GSIM_OK;
 }
 
-// Wait for the result block of the last synchronous enqueue on `s` (it was given s.h_result or any
-// pinned block `out`).  The single-launch path signals through the pinned epoch word -- the block
-// is complete when it changes, a few microseconds before the stream reports the kernel retired;
-// a query it handed back (header flag 2) is re-run by the classic kernels here.
-int finish_query_sync(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k, float cutoff, int metric, float alpha,
-                      float beta, uint32_t row_base, void* out, uint32_t pipe_slot)
+// kRanked's block, announced by the header's epoch (before the stream reports the kernel retired).  `done`: the header arrived (no:
+// the launch ended without closing the query); `torn`: its hits never matched its checksum (both false on entry).
+static int wait_ranked_block(gsim_db* db, Shard& s, void* out, uint32_t k, uint32_t want, bool& done, bool& torn)
 {
-    Shard::PipeSlot& sl = s.slot[pipe_slot];
-    sl.inflight = false;
-    const bool backoff = db->knobs.fused_backoff != 0;
-    auto run_again = [&]() -> int { // the four-kernel pipeline, waited for
-        int rc = enqueue_query(db, s, query, k, cutoff, metric, alpha, beta, row_base, out, true, kClassic, pipe_slot);
-        if (rc == GSIM_OK) rc = wait_stream(s.stream);
-        sl.inflight = false;
-        sl.ev_set = false;
-        return rc;
-    };
-    if (sl.rerun) {
-        // Enqueued behind a single launch that ended without closing its query (below): this one ran on per-query state
-        // nobody had re-zeroed -- WHATEVER route it took (ADVICE r05: a classic or publishing query behind the failed launch
-        // shared that state too) -- and a block's checksum only covers the block's own hits: run it again.  The stream had
-        // drained when the flag was set, so its own kernels are over.
-        sl.rerun = false;
-        sl.fused = sl.publish = sl.binrank = false;
-        sl.why |= kQRerunBehind;
-        db->rerun_behind++;
-        return run_again();
-    }
-    if (!sl.fused) {
-        int rc = sl.ev_set ? wait_event(sl.ev) : wait_stream(s.stream);
-        sl.ev_set = false;
-        const bool back = rc == GSIM_OK && sl.publish && (static_cast<const gsim_result_header*>(out)->flags & 2u);
-        if (rc == GSIM_OK && sl.publish && !back) {
-            s.publish_streak = 0;
-            if (sl.binrank) s.binrank_streak = 0;
-        }
-        if (back) {
-            // large k, scanned by the single launch, handed back (heavy ties): the emission cleared the per-query state
-            if (sl.binrank) {
-                // ties in the top bins, most likely: the next ones by the radix tail -- 16, 32, ... 1024 of them while it keeps
-                // happening (a fixed 16 made a tie-heavy table pay a second scan every 17th large-k query for good)
-                if (backoff) s.binrank_skip = 16u << s.binrank_streak;
-                s.binrank_streak = s.binrank_streak < 6 ? s.binrank_streak + 1 : 6;
-            } else { // not the bin-ranked emission's doing: the launch itself cannot hold this table's queries -- back off as the single launch does
-                s.publish_streak = s.publish_streak < 6 ? s.publish_streak + 1 : 6;
-                if (backoff) s.publish_skip = 1u << s.publish_streak;
-            }
-            sl.why |= kQPublishBack;
-            db->rerun_publish++;
-            sl.publish = false;
-            return run_again();
-        }
-        sl.publish = false;
-        return rc;
-    }
-    sl.fused = false;
     volatile uint32_t* flag = &static_cast<gsim_result_header*>(out)->flags; // (flags | epoch << 8: one 16-byte store with the rest of the header)
-    const uint32_t want = sl.epoch;
-    bool done = false;
     for (uint64_t spins = 0;; spins++) {
         if ((*flag >> 8) == want) {
             done = true;
@@ -484,7 +430,6 @@ int finish_query_sync(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k, 
     }
     std::atomic_thread_fence(std::memory_order_acquire);
     gsim_result_header* h = static_cast<gsim_result_header*>(out);
-    bool torn = false;
     if (done && !(*flag & 2u)) {
         // The block validates itself: the closing workgroup put the sum of the words of all hits (+ epoch * kBlockCheckMul)
         // into the upper half of approx.  The hits were stored write-through at system scope and every selector waited for
@@ -518,7 +463,7 @@ int finish_query_sync(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k, 
             }
             if (!good) {
                 db->blocks_torn++;
-                torn = true; // (re-run below; the kernel itself closed the query and left the state clean)
+                torn = true; // (re-run by the caller; the kernel itself closed the query and left the state clean)
             }
         }
     }
@@ -527,20 +472,64 @@ int finish_query_sync(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k, 
         h->approx &= 0xFFFFFFFFull;
     }
     if (s.d_dbg && done) dump_fused_phases(s); // phase profile of this query (instrumented runs only)
-    if (done && !torn && !(h->flags & 2u)) {
-        s.redo_streak = 0;
+    return GSIM_OK;
+}
+
+// Wait for the result block of a synchronous enqueue on `s` (it was given s.h_result or any pinned block `out`) and run the query
+// again, on the four-kernel pipeline, when its route handed it back, its block is torn, or it ran behind a launch that failed.
+int finish_query_sync(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k, float cutoff, int metric, float alpha,
+                      float beta, uint32_t row_base, void* out, uint32_t pipe_slot)
+{
+    Shard::PipeSlot& sl = s.slot[pipe_slot];
+    sl.inflight = false;
+    const bool backoff = db->knobs.fused_backoff != 0;
+    auto run_again = [&]() -> int { // the four-kernel pipeline, waited for
+        int rc = enqueue_query(db, s, query, k, cutoff, metric, alpha, beta, row_base, out, true, kClassic, pipe_slot);
+        if (rc == GSIM_OK) rc = wait_stream(s.stream);
+        sl.inflight = false;
+        sl.ev_set = false;
+        return rc;
+    };
+    if (sl.rerun) {
+        // Enqueued behind a single launch that ended without closing its query (below): this one ran on per-query state
+        // nobody had re-zeroed -- WHATEVER route it took (ADVICE r05: a classic or publishing query behind the failed launch
+        // shared that state too) -- and a block's checksum only covers the block's own hits: run it again.  The stream had
+        // drained when the flag was set, so its own kernels are over.
+        sl.rerun = false;
+        sl.why |= kQRerunBehind;
+        db->rerun_behind++;
+        return run_again();
+    }
+    if (sl.route != Route::kRanked) {
+        const int rc = sl.ev_set ? wait_event(sl.ev) : wait_stream(s.stream);
+        sl.ev_set = false;
+        if (rc != GSIM_OK || sl.route == Route::kClassic) return rc;
+        if (!(static_cast<const gsim_result_header*>(out)->flags & 2u)) {
+            s.publish_backoff.succeeded();
+            if (sl.route == Route::kPublishBinrank) s.binrank_backoff.succeeded();
+            return GSIM_OK;
+        }
+        // handed back (heavy ties; the emission cleared the per-query state): by the bin-ranked emission or the launch itself
+        (sl.route == Route::kPublishBinrank ? s.binrank_backoff : s.publish_backoff).handed_back(backoff);
+        sl.why |= kQPublishBack;
+        db->rerun_publish++;
+        return run_again();
+    }
+    bool done = false, torn = false;
+    const int rc = wait_ranked_block(db, s, out, k, sl.epoch, done, torn);
+    if (rc != GSIM_OK) return rc;
+    if (done && !torn && !(static_cast<const gsim_result_header*>(out)->flags & 2u)) {
+        s.ranked_backoff.succeeded();
         return GSIM_OK;
     }
-    if (done && !torn) {
-        s.redo_streak = s.redo_streak < 6 ? s.redo_streak + 1 : 6;
-        if (backoff && s.redo_streak >= 2) s.fused_skip = 1u << s.redo_streak;
-        sl.why |= kQHandedBack;
-        db->rerun_own++;
-    } else if (torn) {
+    if (torn) {
         sl.why |= kQTorn;
         db->rerun_torn++;
-    }
-    if (!done) {
+    } else if (done) { // handed back: the per-query state is zero again (the last selector reset it), `redo` is set
+        s.ranked_backoff.handed_back(backoff);
+        sl.why |= kQHandedBack;
+        db->rerun_own++;
+    } else {
         // The launch ended without closing the query: the state is re-zeroed, and the later queries of a pipelined call --
         // the stream has drained, so they have all run already, on that state -- are run again, whichever
         // route they took (every slot in flight, not only the single launch's)
@@ -550,16 +539,39 @@ int finish_query_sync(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k, 
         for (uint32_t j = 0; j < static_cast<uint32_t>(kPipe); j++)
             if (j != pipe_slot && s.slot[j].inflight) s.slot[j].rerun = true;
     }
-    // handed back: the per-query state is zero again (the last selector reset it), `redo` is set
     return run_again();
+}
+
+// One query's answer from db->blocks (one per shard that ran it): the slots' `why` bits into query_flags[q], approx summed, the
+// hits copied (a single-shard handle) or merged across shards (fingerprintdb_cuda.cu:363-380)
+static void collect_blocks(gsim_db* db, size_t q, uint32_t k, gsim_hit* hits, uint32_t* count, uint64_t* approx)
+{
+    const bool one = db->shards.size() == 1;
+    uint64_t ap = 0;
+    db->merged.clear();
+    db->merged_ends.clear();
+    for (const ShardBlock& b : db->blocks) {
+        if (q < db->query_flags.size()) db->query_flags[q] |= b.why;
+        const gsim_result_header* h = static_cast<const gsim_result_header*>(b.out);
+        const gsim_hit* hh = reinterpret_cast<const gsim_hit*>(h + 1);
+        ap += h->approx;
+        if (one) {
+            std::memcpy(hits, hh, sizeof(gsim_hit) * h->count);
+            *count = h->count;
+        } else {
+            db->merged.insert(db->merged.end(), hh, hh + h->count);
+            db->merged_ends.push_back(db->merged.size());
+        }
+    }
+    if (!one) *count = merge_canonical_lists(db->merged, db->merged_ends, k, hits);
+    if (approx) *approx = ap;
 }
 
 // One query through the single-query pipeline on every shard, host merge across shards
 // (FingerprintDB::search, fingerprintdb_cuda.cu:341-381).
 int search_one(gsim_db* db, const uint32_t* query, uint32_t k, float cutoff, int metric, float alpha, float beta,
-               gsim_hit* hits, uint32_t* count, uint64_t* approx, std::vector<gsim_hit>& merged)
+               gsim_hit* hits, uint32_t* count, uint64_t* approx)
 {
-    const size_t nsh = db->shards.size();
     if (db->comm) return search_one_comm(db, query, k, cutoff, metric, alpha, beta, hits, count, approx);
     for (auto& s : db->shards) {
         int rc = ensure_result_capacity(s, k);
@@ -569,28 +581,15 @@ int search_one(gsim_db* db, const uint32_t* query, uint32_t k, float cutoff, int
                            db->row_base + static_cast<uint32_t>(s.first_row), s.h_result, true);
         if (rc != GSIM_OK) return rc;
     }
-    uint64_t ap = 0;
-    merged.clear();
-    std::vector<size_t> ends;
+    db->blocks.clear();
     for (auto& s : db->shards) {
         GSIM_HIP(set_device(s.device));
         int rc = finish_query_sync(db, s, query, k, cutoff, metric, alpha, beta,
                                    db->row_base + static_cast<uint32_t>(s.first_row), s.h_result);
         if (rc != GSIM_OK) return rc;
-        if (db->query_flags_at < db->query_flags.size()) db->query_flags[db->query_flags_at] |= s.slot[0].why;
-        const gsim_result_header* h = reinterpret_cast<const gsim_result_header*>(s.h_result);
-        const gsim_hit* hh = reinterpret_cast<const gsim_hit*>(h + 1);
-        ap += h->approx;
-        if (nsh == 1) {
-            std::memcpy(hits, hh, sizeof(gsim_hit) * h->count);
-            *count = h->count;
-        } else {
-            merged.insert(merged.end(), hh, hh + h->count);
-            ends.push_back(merged.size());
-        }
+        db->blocks.push_back({s.h_result, s.slot[0].why});
     }
-    if (nsh > 1) *count = merge_canonical_lists(merged, ends, k, hits); // fingerprintdb_cuda.cu:363-380
-    if (approx) *approx = ap;
+    collect_blocks(db, db->query_flags_at, k, hits, count, approx);
     return GSIM_OK;
 }
 
@@ -672,8 +671,6 @@ int search_each_pipelined(gsim_db* db, const uint32_t* queries, uint32_t nq, uin
     // query q of the call on shard i: which search state answers it, and in which of its pipeline slots
     auto state_of = [&](size_t i, uint32_t q) -> Shard& { return use_lanes[i] ? db->shards[i].lanes[q % db->shards[i].lanes.size()] : db->shards[i]; };
     auto slot_of = [&](size_t i, uint32_t q) -> uint32_t { return (use_lanes[i] ? q / static_cast<uint32_t>(db->shards[i].lanes.size()) : q) % kPipe; };
-    std::vector<gsim_hit> merged;
-    std::vector<size_t> ends;
     uint32_t issued = 0;
     for (uint32_t done = 0; done < nq; done++) {
         for (; issued < nq && issued - done < static_cast<uint32_t>(kPipe); issued++) {
@@ -687,9 +684,7 @@ int search_each_pipelined(gsim_db* db, const uint32_t* queries, uint32_t nq, uin
                 if (use_lanes[i]) db->lane_queries++;
             }
         }
-        uint64_t ap = 0;
-        merged.clear();
-        ends.clear();
+        db->blocks.clear();
         for (size_t i = 0; i < nsh; i++) {
             if (db->shards[i].nrows == 0) continue;
             Shard& s = state_of(i, done);
@@ -699,20 +694,9 @@ int search_each_pipelined(gsim_db* db, const uint32_t* queries, uint32_t nq, uin
             const int rc = finish_query_sync(db, s, queries + static_cast<size_t>(done) * db->W, k, cutoff, metric, alpha, beta,
                                              db->row_base + static_cast<uint32_t>(s.first_row), out, slot);
             if (rc != GSIM_OK) return rc;
-            if (done < db->query_flags.size()) db->query_flags[done] |= s.slot[slot].why;
-            const gsim_result_header* h = static_cast<const gsim_result_header*>(out);
-            const gsim_hit* hh = reinterpret_cast<const gsim_hit*>(h + 1);
-            ap += h->approx;
-            if (nsh == 1) {
-                std::memcpy(hits + static_cast<size_t>(done) * kout, hh, sizeof(gsim_hit) * h->count);
-                counts[done] = h->count;
-            } else {
-                merged.insert(merged.end(), hh, hh + h->count);
-                ends.push_back(merged.size());
-            }
+            db->blocks.push_back({out, s.slot[slot].why});
         }
-        if (nsh > 1) counts[done] = merge_canonical_lists(merged, ends, k, hits + static_cast<size_t>(done) * kout); // fingerprintdb_cuda.cu:363-380
-        if (approx) approx[done] = ap;
+        collect_blocks(db, done, k, hits + static_cast<size_t>(done) * kout, &counts[done], approx ? &approx[done] : nullptr);
     }
     return GSIM_OK;
 }
@@ -743,7 +727,6 @@ int gsim_db_search(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_t k
     // from a client must not size them)
     const uint32_t k = static_cast<uint32_t>(std::min<uint64_t>(kout, db->nrows));
     const size_t nsh = db->shards.size();
-    std::vector<gsim_hit> merged;
     db->query_flags.assign(db->timing ? nq : 0, 0); // (gsim_debug_query_flags: how each query of this call was routed / re-run)
     if (db->fold > 1) {
         if (metric != GSIM_METRIC_TANIMOTO) return fail(GSIM_ERR_INVALID, "folded tables support Tanimoto only");
@@ -762,7 +745,7 @@ int gsim_db_search(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_t k
         const uint32_t* query = queries + static_cast<size_t>(q) * db->W;
         db->query_flags_at = q;
         rc = search_one(db, query, k, cutoff, metric, alpha, beta, hits + static_cast<size_t>(q) * kout, &counts[q],
-                        approx ? &approx[q] : nullptr, merged);
+                        approx ? &approx[q] : nullptr);
         if (rc != GSIM_OK) return rc;
     }
     return GSIM_OK;
@@ -777,13 +760,12 @@ int gsim_db_search_timed(gsim_db* db, const uint32_t* queries, uint32_t nq, uint
     if (db->fold > 1) return fail(GSIM_ERR_STATE, "gsim_db_search_timed does not support folded tables");
     std::lock_guard<std::mutex> guard(db->search_mutex);
     const uint32_t k = static_cast<uint32_t>(std::min<uint64_t>(kout, db->nrows));
-    std::vector<gsim_hit> merged;
     db->query_flags.assign(db->timing ? nq : 0, 0);
     for (uint32_t q = 0; q < nq; q++) {
         db->query_flags_at = q;
         const auto t0 = std::chrono::steady_clock::now();
         rc = search_one(db, queries + static_cast<size_t>(q) * db->W, k, cutoff, metric, alpha, beta, hits + static_cast<size_t>(q) * kout,
-                        &counts[q], approx ? &approx[q] : nullptr, merged);
+                        &counts[q], approx ? &approx[q] : nullptr);
         if (rc != GSIM_OK) return rc;
         seconds[q] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
