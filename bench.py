@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: Tanimoto top-1000 scan of synthetic 1024-bit tables.
 
-    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` (N > 1) without a launcher starts its own N ranks (one process per GPU, 127.0.0.1
@@ -16,11 +16,16 @@ run; 125 M at N > 1 so that 8 GPUs hold the 1 B-row table of configs[3]).
 value = rows of the whole table * queries / max-over-ranks time.
 
 Prints ONE JSON line (rank 0).  `roofline` is the dominant kernel's algorithmic bytes (128 B per
-fingerprint per pass) over its HIP-event duration on the stream it runs on.  At N = 1 the line
-also carries `configs`: every single-GPU BASELINE config measured in this run (configs[1]: 1 M
+fingerprint per pass) over its HIP-event duration on the stream it runs on.
+
+A plain run does only what the headline needs: the table, the warm-up, the timed steps, --dump-outputs,
+the line.  Everything that takes runs of its own is behind --full (and --no-* below trims it): the
+one-at-a-time latency (`sync_ms_*`), the rocprofv3 --pmc passes behind `roofline.traffic`, at N > 1 each
+shard's single-GPU twin, and at N = 1 `configs`: every single-GPU BASELINE config (configs[1]: 1 M
 rows; configs[2]: the headline; configs[4]'s per-GPU shape: 125 M x 2048-bit, Tversky, 256-query
 batches) plus the 1 M / 100 M-row tables again with MORGAN-SHAPED rows (clustered, tie-heavy: what the
-reference's own numbers are quoted on), and `cpu_baseline`: the reference's host functor path + top-k on this box's cores
+reference's own numbers are quoted on), large k, other row widths, the 1 B-row table, the server's
+latency, and `cpu_baseline`: the reference's host functor path + top-k on the host's cores
 (oracle/_ref when present, else the oracle port) on bounded samples.
 """
 import argparse
@@ -267,8 +272,9 @@ def compact_line(out, detail_path):
             for m in c["per_rank"]:
                 e = {"rank": m.get("rank")}
                 e.update(m.get("phases_per_query") or {})
-                tw = m.get("single_gpu_twin") or {}
-                e["twin_ms_per_query"], e["twin_kernel_ms"] = tw.get("ms_per_query"), tw.get("kernel_ms_avg")
+                tw = m.get("single_gpu_twin")
+                if tw:  # (--full only)
+                    e["twin_ms_per_query"], e["twin_kernel_ms"] = tw.get("ms_per_query"), tw.get("kernel_ms_avg")
                 pr.append(e)
             cc["per_rank"] = pr
         line["collective"] = cc
@@ -353,10 +359,11 @@ def emit(out, json_fd, detail_name="bench_detail.json"):
 # ---------------------------------------------------------------------------------------------
 
 def time_queries(ctx, table, total_rows, R, fp_bits, kind, k, steps, warmup, qps, sharded, barrier=True, first_row=0,
-                 keep_outputs=False):
+                 keep_outputs=False, latency=True):
     """steps x qps single queries (after warmup x qps), barrier + synchronize on both sides, max over ranks.
     keep_outputs: res["outputs"] holds the last timed step's results (last_step_outputs; the N > 1 path: its last
-    `depth` queries, what the gather + merge objects still hold)."""
+    `depth` queries, what the gather + merge objects still hold).
+    latency: afterwards, the one-at-a-time latency of the single-GPU path (res["sync_latency"], runs of its own)."""
     import torch
     import torch.distributed as dist
     from gpusimilarity_amd.sharded import ShardedSearch
@@ -445,7 +452,7 @@ def time_queries(ctx, table, total_rows, R, fp_bits, kind, k, steps, warmup, qps
     # SURVEY 8(d)'s latency: wall time from query-on-host to top-k-on-host, ONE query at a time through gsim_db_search
     # (nothing enqueued ahead, unlike the timed region above), median and p95 of >= 200 calls
     sync = None
-    if not sharded:
+    if latency and not sharded:
         nlat = 200 if R * fp_bits <= 100_000_000 * 1024 else 50
         qlat = np.ascontiguousarray(np.stack([queries[j % distinct] for j in range(nlat + 20)]))
         blat = table.make_search_buffers(nlat + 20, k)
@@ -484,7 +491,7 @@ def time_queries(ctx, table, total_rows, R, fp_bits, kind, k, steps, warmup, qps
                       (" [two half-grid launches side by side: kernel_ms_avg = a launch's HIP-event duration / 2]" if lanes > 1 else ""),
             "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
             "traffic": None,
-            "traffic_note": "not collected for this entry (the headline entry runs the rocprofv3 --pmc passes)",
+            "traffic_note": "not collected for this entry (the headline entry of a --full run runs the rocprofv3 --pmc passes)",
             "kernel_ms_avg": kernel_ms, "other_kernels_ms_avg": tm["select_ms_sum"] / n,
             "launches_side_by_side": lanes, "kernel_ms_avg_each_launch": kernel_ms_each,
             "algorithmic_bytes_per_launch": algo,
@@ -704,8 +711,8 @@ def in_process(args):
             for name in ("GSIM_TEST_ALIAS_DEVICES", "GSIM_LIB"):
                 env.pop(name, None)
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(N), "--steps", str(steps), "--warmup", str(warmup), "--queries-per-step", str(qps),
-               "--rows-per-gpu", str(R), "--k", str(k), "--fp-bits", str(args.fp_bits), "--kind", args.kind, "--no-configs", "--no-cpu-baseline",
-               "--no-server-latency", "--no-pmc"] + (["--force-sharded-path"] if N == 1 else [])
+               "--rows-per-gpu", str(R), "--k", str(k), "--fp-bits", str(args.fp_bits), "--kind", args.kind, "--full", "--no-configs",
+               "--no-cpu-baseline", "--no-server-latency", "--no-pmc"] + (["--force-sharded-path"] if N == 1 else [])
         try:
             p = subprocess.run(cmd, env=env, capture_output=True, timeout=1800)
             line = json.loads(p.stdout.decode().strip().splitlines()[-1])
@@ -755,17 +762,21 @@ def main():
     ap.add_argument("--k", type=int, default=1000)
     ap.add_argument("--fp-bits", type=int, default=1024)
     ap.add_argument("--kind", choices=["sparse", "dense", "morgan"], default="sparse")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the other single-GPU BASELINE configs (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else this script measures: the one-at-a-time latency, the rocprofv3 "
+                         "--pmc traffic, each shard's single-GPU twin (N > 1), the other configs, row widths, the server's latency "
+                         "and the CPU baseline (N = 1); a plain run times the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the other single-GPU BASELINE configs (N = 1 only)")
     ap.add_argument("--no-server-latency", action="store_true",
-                    help="skip the end-to-end gpusimserver record (scripts/server_latency.py, N = 1 only)")
+                    help="--full: skip the end-to-end gpusimserver record (scripts/server_latency.py, N = 1 only)")
     ap.add_argument("--batch-queries", type=int, default=0,
                     help="BASELINE configs[4] instead of the headline run: Tversky(0.3, 0.7) batches of this many "
                          "queries per step (use with --fp-bits 2048); a step is one batch")
     ap.add_argument("--cutoff", type=float, default=0.0, help="--batch-queries: similarity cutoff of the batch (0.1 keeps 4.5 %% of the synthetic table per query: "
                                                                "the dense-cutoff variant of the contraction kernel counts them)")
     ap.add_argument("--pmc-child", action="store_true", help="internal: the process rocprofv3 counts (pmc_traffic)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc passes behind roofline.traffic")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 --pmc passes behind roofline.traffic")
     ap.add_argument("--in-process", action="store_true",
                     help="the one-process multi-GPU routes of the product (gpusimserver --gpus N): ONE handle sharded over --gpus "
                          "devices -- host merge and the C-ABI collective (gsim_comm: RCCL all-gather + merge_kernel) -- each next to the "
@@ -884,18 +895,19 @@ def main():
 
     qps = max(1, args.queries_per_step)
     res, _ss = time_queries(ctx, table, total_rows, R, args.fp_bits, kind, k, args.steps, args.warmup, qps, sharded,
-                            keep_outputs=bool(args.dump_outputs))
+                            keep_outputs=bool(args.dump_outputs), latency=args.full)
     if args.dump_outputs and rank == 0:
         dump_outputs(res["outputs"], args.dump_outputs)
     if sharded:
-        # what each rank's own phases cost (HIP events on its stream) and -- the N = 1 twin -- what the same shard answers
+        # what each rank's own phases cost (HIP events on its stream) and -- --full: the N = 1 twin -- what the same shard answers
         # alone through the synchronous single-GPU path: the 1 -> N curve then decomposes into scan / gather / merge / copy
-        table.set_stream(0)  # back to the handle's own stream
-        table.set_row_base(rank * R)
-        tw, _ = time_queries(dict(ctx, world=1), table, R, R, args.fp_bits, kind, k, 2, 1, min(qps, 64), False, barrier=False, first_row=rank * R)
-        mine = {"rank": rank, "phases_per_query": res["phases"],
-                "single_gpu_twin": {"rows": R, "ms_per_query": tw["ms_per_query"], "fingerprints_per_s": tw["fingerprints_per_s"],
-                                    "kernel_ms_avg": tw["roofline"]["kernel_ms_avg"]}}
+        mine = {"rank": rank, "phases_per_query": res["phases"]}
+        if args.full:
+            table.set_stream(0)  # back to the handle's own stream
+            table.set_row_base(rank * R)
+            tw, _ = time_queries(dict(ctx, world=1), table, R, R, args.fp_bits, kind, k, 2, 1, min(qps, 64), False, barrier=False, first_row=rank * R)
+            mine["single_gpu_twin"] = {"rows": R, "ms_per_query": tw["ms_per_query"], "fingerprints_per_s": tw["fingerprints_per_s"],
+                                       "kernel_ms_avg": tw["roofline"]["kernel_ms_avg"]}
         per_rank = [mine]
         if dist.is_initialized() and world > 1:
             per_rank = [None] * world
@@ -903,7 +915,7 @@ def main():
         collective["per_rank"] = per_rank
         collective["queries_in_flight"] = 8
     table.close()
-    if world == 1 and not sharded and not args.no_pmc and res["roofline"]["kernel"].startswith("fused_kernel"):
+    if world == 1 and not sharded and args.full and not args.no_pmc and res["roofline"]["kernel"].startswith("fused_kernel"):
         try:
             fetch, write, note = pmc_traffic(R, args.fp_bits, args.kind, k, "fused_kernel")
         except Exception as e:  # a report, never a reason to lose the headline
@@ -927,8 +939,8 @@ def main():
         "value": res["fingerprints_per_s"], "unit": "fingerprints/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": res["ms_per_query"] * qps, "queries_per_step": qps, "ms_per_query": res["ms_per_query"],
-        "ms_per_query_note": "mean over the timed region, up to 8 queries enqueued ahead of the one being waited for; sync_ms_* = one "
-                             "query at a time, query on the host -> hits on the host, timed inside the library (gsim_db_search_timed; SURVEY 8d's latency)",
+        "ms_per_query_note": "mean over the timed region, up to 8 queries enqueued ahead of the one being waited for; sync_ms_* (--full) = "
+                             "one query at a time, query on the host -> hits on the host, timed inside the library (gsim_db_search_timed; SURVEY 8d's latency)",
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "u32", "data": "synthetic",
         "config": {
@@ -946,7 +958,7 @@ def main():
                                 if not sharded else
                                 "one query at a time on every GPU: local search, all-gather, merge, D2H; up to 8 queries' steps are "
                                 "enqueued ahead of the one the host waits for, as at N = 1 (which holds 100 M rows per GPU, this line "
-                                "%d M: collective.per_rank has each rank's phase times and its shard's single-GPU twin)" % (R // 1_000_000)),
+                                "%d M: collective.per_rank has each rank's phase times and, --full, its shard's single-GPU twin)" % (R // 1_000_000)),
         },
         "whole_path_hbm_frac": res["whole_path_hbm_frac"],
         "roofline": res["roofline"],
@@ -954,7 +966,7 @@ def main():
     }
     if res["sync_latency"]:
         out.update(res["sync_latency"])
-    if world == 1 and not args.no_configs and not sharded:
+    if world == 1 and args.full and not args.no_configs and not sharded:
         # the other single-GPU BASELINE configs, measured in this run, each with its own dominant-kernel roofline
         cfgs = []
 
@@ -1049,7 +1061,7 @@ def main():
         out["configs"] = cfgs
         out["configs_note"] = ("configs[0] (small.fsim, CPU path) is timed under cpu_baseline.parts; configs[3] (1B rows over 8 GPUs) "
                                "is this script at --gpus 8")
-    if world == 1 and not sharded and not args.no_server_latency and not args.no_configs:
+    if world == 1 and not sharded and args.full and not args.no_server_latency and not args.no_configs:
         # the reference's own published metric: server-side search latency through the socket backend, at two of its
         # slide-12/13 table sizes (ChEMBL 1 618 358 rows, Enamine 56 667 620 rows), Morgan-shaped rows, k = 20 and 1000
         try:
@@ -1061,7 +1073,7 @@ def main():
         except Exception as e:  # a report, never a reason to lose the headline
             out["server_latency"] = {"error": repr(e)}
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.fp_bits, k, kind)
             except Exception as e:  # the baseline is a report, never a reason to lose the GPU number

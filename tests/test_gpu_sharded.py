@@ -49,7 +49,7 @@ def test_bench_spawns_its_own_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                          "--rows-per-gpu", "2000000", "--no-cpu-baseline", "--no-configs"], env=env, capture_output=True,
+                          "--rows-per-gpu", "2000000"], env=env, capture_output=True,
                          timeout=900)
     assert out.returncode == 0, out.stderr.decode("utf-8", "replace")[-3000:]
     lines = [ln for ln in out.stdout.decode().splitlines() if ln.strip()]
