@@ -19,6 +19,8 @@ LIB_PATH = os.environ.get("GSIM_LIB") or os.path.join(_HERE, "libgsim_hip.so")
 OK = 0
 METRIC_TANIMOTO = 0
 METRIC_TVERSKY = 1
+JOIN_BY_ROW = 0
+JOIN_BY_SCORE = 1
 SYNTH_SPARSE = 0
 SYNTH_DENSE = 1
 SYNTH_MORGAN = 2
@@ -41,6 +43,13 @@ class GsimTiming(C.Structure):
 class GsimGraphStats(C.Structure):
     _fields_ = [("launches", C.c_uint64), ("launches_rerun", C.c_uint64), ("pairs", C.c_uint64), ("tile_ms", C.c_double),
                 ("csr_ms", C.c_double), ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
+
+
+class GsimJoinStats(C.Structure):
+    _fields_ = [("rows_streamed", C.c_uint64), ("rows_tiled", C.c_uint64), ("stream_launches", C.c_uint64),
+                ("tile_launches", C.c_uint64), ("launches_rerun", C.c_uint64), ("pairs", C.c_uint64), ("stream_ms", C.c_double),
+                ("tile_ms", C.c_double), ("csr_ms", C.c_double), ("d2h_ms", C.c_double), ("wall_ms", C.c_double),
+                ("clock_mhz", C.c_double)]
 
 
 class GsimMaxMinStats(C.Structure):
@@ -67,6 +76,7 @@ EXPORTS = [
     "gsim_comm_create", "gsim_comm_destroy", "gsim_comm_size", "gsim_rccl_info", "gsim_db_set_comm", "gsim_db_set_comm_root",
     "gsim_db_enable_timing",
     "gsim_db_neighbors", "gsim_graph_shape", "gsim_graph_copy", "gsim_graph_get_stats", "gsim_graph_destroy", "gsim_butina",
+    "gsim_db_join_queries", "gsim_db_join", "gsim_graph_get_join_stats",
     "gsim_db_maxmin",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
@@ -148,6 +158,9 @@ def load():
         "gsim_graph_copy": (C.c_int, [vp, u64p, u32p, C.POINTER(C.c_float)]),
         "gsim_graph_get_stats": (C.c_int, [vp, C.POINTER(GsimGraphStats)]),
         "gsim_graph_destroy": (C.c_int, [vp]),
+        "gsim_db_join_queries": (C.c_int, [vp, u32p, C.c_uint64, C.c_float, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(vp)]),
+        "gsim_db_join": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_float, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(vp)]),
+        "gsim_graph_get_join_stats": (C.c_int, [vp, C.POINTER(GsimJoinStats)]),
         "gsim_butina": (C.c_int, [u64p, u32p, C.c_uint64, u32p, u32p, u64p]),
         "gsim_db_maxmin": (C.c_int, [vp, C.c_uint32, u32p, C.c_uint32, C.c_int, C.c_float, C.c_float, C.c_float, u32p,
                                      C.POINTER(C.c_float), u32p, C.POINTER(C.c_float), u32p, C.POINTER(GsimMaxMinStats)]),
@@ -300,6 +313,10 @@ class Table:
             row_end = self.count()
         g = C.c_void_p()
         check(self._L.gsim_db_neighbors(self._h, cutoff, metric, alpha, beta, row_begin, row_end, C.byref(g)))
+        return self._take_graph(g, stats, GsimGraphStats, self._L.gsim_graph_get_stats)
+
+    def _take_graph(self, g, stats, stats_type, get_stats):
+        """A gsim_graph -> (indptr, indices, scores) (+ its stats into the dict `stats`); the graph is destroyed."""
         try:
             n, nnz = C.c_uint64(0), C.c_uint64(0)
             check(self._L.gsim_graph_shape(g, C.byref(n), C.byref(nnz)))
@@ -309,12 +326,33 @@ class Table:
             check(self._L.gsim_graph_copy(g, indptr.ctypes.data_as(C.POINTER(C.c_uint64)), _u32(indices),
                                           scores.ctypes.data_as(C.POINTER(C.c_float))))
             if stats is not None:
-                st = GsimGraphStats()
-                check(self._L.gsim_graph_get_stats(g, C.byref(st)))
-                stats.update({f: getattr(st, f) for f, _ in GsimGraphStats._fields_})
+                st = stats_type()
+                check(get_stats(g, C.byref(st)))
+                stats.update({f: getattr(st, f) for f, _ in stats_type._fields_})
         finally:
             self._L.gsim_graph_destroy(g)
         return indptr, indices, scores
+
+    def join(self, left, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, order=JOIN_BY_ROW, row_begin=0, row_end=None,
+             stats=None):
+        """gsim_db_join / gsim_db_join_queries: for every left row, every row j of THIS table with
+        score(query = left row, row j) >= cutoff -> CSR (indptr uint64 [nl + 1], indices uint32 (+ row base), scores float32).
+        `left`: a Table on the same device (its rows [row_begin, row_end)) or a (nq, W) / (W,) uint32 array.
+        `order`: JOIN_BY_ROW (each list by table row) or JOIN_BY_SCORE (search's order: score descending, row ascending).
+        `stats`: a dict that receives the call's gsim_join_stats."""
+        g = C.c_void_p()
+        if isinstance(left, Table):
+            if row_end is None:
+                row_end = left.count()
+            check(self._L.gsim_db_join(self._h, left._h, row_begin, row_end, cutoff, metric, alpha, beta, order, C.byref(g)))
+        else:
+            q = np.ascontiguousarray(left, dtype=np.uint32).reshape(-1, self.W)
+            if row_end is None:
+                row_end = q.shape[0]
+            q = np.ascontiguousarray(q[row_begin:row_end])
+            check(self._L.gsim_db_join_queries(self._h, _u32(q) if len(q) else None, len(q), cutoff, metric, alpha, beta, order,
+                                               C.byref(g)))
+        return self._take_graph(g, stats, GsimJoinStats, self._L.gsim_graph_get_join_stats)
 
     def maxmin(self, npicks, seeds=(), metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, max_score=1.0, assign=False, stats=None):
         """gsim_db_maxmin: MaxMin diversity picking, one pass over the table per pick -> (picks uint32 (+ row base),

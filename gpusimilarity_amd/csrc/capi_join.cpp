@@ -1,0 +1,253 @@
+// capi_join.cpp -- gsim_db_join / gsim_db_join_queries: every table row at or above a cutoff, per left row.  Two thin fronts of
+// one core that takes "left rows in device memory, nl of them"; the device side is gsim_join.hip (streaming route) and the
+// join instantiations of gsim_neighbors.hip's tile kernel.  The rule is stated in include/gpusim_hip.h.
+#include "capi_pairs.h"
+
+#include <chrono>
+#include <cmath>
+
+namespace gsim_host
+{
+
+// Bytes of table rows one launch of a streaming pass reads at most: 256 M rows x 128 B, as a MaxMin pass
+constexpr uint64_t kJoinLaunchBytes = (256ull << 20) * 128ull;
+
+namespace
+{
+
+// Rows per launch of a pass: a multiple of 64 (launch starts stay 16-byte aligned for every width)
+uint64_t launch_rows(uint32_t W)
+{
+    uint64_t r = kJoinLaunchBytes / (static_cast<uint64_t>(W) * 4u);
+#ifdef GSIM_TEST_HOOKS
+    // GSIM_TEST_JOIN_LAUNCH_ROWS: a short cap, so that the tests run multi-launch passes on small tables
+    const int cap = env_int("GSIM_TEST_JOIN_LAUNCH_ROWS", 0);
+    if (cap > 0) r = static_cast<uint64_t>(cap);
+#endif
+    r = r / 64 * 64;
+    return r < 64 ? 64 : r;
+}
+
+struct PassPiece {
+    uint64_t r0, nrows;
+    gsim::ScanGeometry g;
+};
+
+// left rows d_left[0 .. nl) (W words each, on s's device) against s's table
+int join(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, float cutoff, int metric, float alpha, float beta, int order,
+         gsim_graph* g)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t N = s.nrows;
+    g->is_join = true;
+    g->indptr.assign(nl + 1, 0);
+    if (nl == 0 || N == 0) {
+        g->join.wall_ms = g->stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return GSIM_OK;
+    }
+    GSIM_HIP(set_device(s.device));
+    const hipStream_t st = s.stream;
+    const bool stream = db->knobs.join_stream_max_rows > 0 && nl <= static_cast<uint64_t>(db->knobs.join_stream_max_rows);
+    PairRun run;
+    if (stream) {
+        std::vector<PassPiece> pieces;
+        const uint64_t per = launch_rows(s.W);
+        for (uint64_t r0 = 0; r0 < N; r0 += per) {
+            PassPiece p{r0, std::min(per, N - r0), {}};
+            p.g = gsim::maxmin_geometry(p.nrows, s.W, s.num_cus);
+            pieces.push_back(p);
+        }
+        const size_t nlaunch = static_cast<size_t>(nl) * pieces.size();
+        DevBuf ctl; // [0] the cursor, [1 + l] the cursor after launch l
+        GSIM_HIP(ctl.alloc((1 + nlaunch) * 8));
+        gsim::JoinArgs j{};
+        j.rows = s.d_rows;
+        j.W = s.W;
+        j.metric = metric;
+        j.alpha = alpha;
+        j.beta = beta;
+        j.cutoff = cutoff;
+        j.left = d_left;
+        const int rc = run_pair_launches(s, nlaunch, ctl.as<unsigned long long>(), ctl.as<unsigned long long>() + 1,
+                                         [&](size_t l, const PairSink& sink) {
+                                             gsim::JoinArgs jl = j;
+                                             jl.keys = sink.keys;
+                                             jl.vals = sink.vals;
+                                             jl.cursor = sink.cursor;
+                                             jl.cap = sink.cap;
+                                             const PassPiece& p = pieces[l % pieces.size()];
+                                             GSIM_HIP(gsim::launch_join_pass(jl, p.g, p.r0, p.nrows, static_cast<uint32_t>(l / pieces.size()), st));
+                                             return static_cast<int>(GSIM_OK);
+                                         },
+                                         &run);
+        if (rc != GSIM_OK) return rc;
+        g->join.rows_streamed = nl;
+        g->join.stream_launches = nlaunch;
+        g->join.stream_ms = run.ms;
+        g->stats.launches = nlaunch;
+    } else {
+        // popc of every row of either side, and the rows zero-padded to WP words unless they already are WP words
+        const uint32_t WP = gsim::nbr_padded_words(s.W);
+        DevBuf pop, pad, lpop, lpad;
+        GSIM_HIP(pop.alloc(N * 4));
+        GSIM_HIP(lpop.alloc(nl * 4));
+        if (WP != s.W) {
+            GSIM_HIP(pad.alloc(N * WP * 4));
+            GSIM_HIP(lpad.alloc(nl * WP * 4));
+        }
+        GSIM_HIP(gsim::launch_nbr_prepare(s.d_rows, N, s.W, WP, pad.as<uint32_t>(), pop.as<uint32_t>(), st));
+        GSIM_HIP(gsim::launch_nbr_prepare(d_left, nl, s.W, WP, lpad.as<uint32_t>(), lpop.as<uint32_t>(), st));
+        const uint64_t nlt = (nl + gsim::kNbrTile - 1) / gsim::kNbrTile;
+        const uint64_t nct = (N + gsim::kNbrTile - 1) / gsim::kNbrTile;
+        const std::vector<NbrLaunch> plan = plan_launches(nlt, nct, false, WP);
+        DevBuf ctl; // [0] the cursor, [1 + l] the cursor after launch l, then 4 clock stamps per launch
+        GSIM_HIP(ctl.alloc((1 + 5 * plan.size()) * 8));
+        unsigned long long* d_clk = ctl.as<unsigned long long>() + 1 + plan.size();
+        gsim::JoinTileArgs a{};
+        a.rows = WP != s.W ? pad.as<uint32_t>() : static_cast<const uint32_t*>(s.d_rows);
+        a.pop = pop.as<uint32_t>();
+        a.lrows = WP != s.W ? lpad.as<uint32_t>() : d_left;
+        a.lpop = lpop.as<uint32_t>();
+        a.nrows = N;
+        a.row_begin = 0;
+        a.row_end = nl;
+        a.WP = WP;
+        a.metric = metric;
+        a.alpha = alpha;
+        a.beta = beta;
+        a.cutoff = cutoff;
+        const int rc = run_pair_launches(s, plan.size(), ctl.as<unsigned long long>(), ctl.as<unsigned long long>() + 1,
+                                         [&](size_t l, const PairSink& sink) {
+                                             gsim::JoinTileArgs al = a;
+                                             al.keys = sink.keys;
+                                             al.vals = sink.vals;
+                                             al.cursor = sink.cursor;
+                                             al.cap = sink.cap;
+                                             al.clk = d_clk + 4 * l;
+                                             GSIM_HIP(gsim::launch_join_tiles(al, plan[l].rt0, plan[l].nrt, plan[l].ct0, plan[l].nct, st));
+                                             return static_cast<int>(GSIM_OK);
+                                         },
+                                         &run);
+        if (rc != GSIM_OK) return rc;
+        std::vector<unsigned long long> clk(4 * plan.size());
+        GSIM_HIP(hipMemcpyAsync(clk.data(), d_clk, clk.size() * 8, hipMemcpyDeviceToHost, st));
+        GSIM_HIP(hipStreamSynchronize(st));
+        double cyc = 0.0, ticks = 0.0;
+        for (size_t l = 0; l < plan.size(); l++) {
+            cyc += static_cast<double>(clk[4 * l + 2] - clk[4 * l]);
+            ticks += static_cast<double>(clk[4 * l + 3] - clk[4 * l + 1]);
+        }
+        g->join.clock_mhz = g->stats.clock_mhz = ticks > 0.0 ? cyc / ticks * 100.0 : 0.0; // wall clock: 100 MHz
+        g->join.rows_tiled = nl;
+        g->join.tile_launches = plan.size();
+        g->join.tile_ms = run.ms;
+        g->stats.launches = plan.size();
+    }
+    g->stats.launches_rerun = g->join.launches_rerun = run.rerun;
+    g->stats.pairs = g->join.pairs = run.total;
+    g->stats.tile_ms = run.ms;
+    const int rc = build_pair_csr(db, s, run.total, nl, order, g);
+    if (rc != GSIM_OK) return rc;
+    g->join.csr_ms = g->stats.csr_ms;
+    g->join.d2h_ms = g->stats.d2h_ms;
+    g->join.wall_ms = g->stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return GSIM_OK;
+}
+
+// what both entry points check before any device state
+int check_join_args(gsim_db* db, gsim_graph** out, uint64_t nl, float cutoff, int metric, float alpha, float beta, int order)
+{
+    if (!db || !out) return fail(GSIM_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    if (metric != GSIM_METRIC_TANIMOTO && metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
+    if (order != GSIM_JOIN_BY_ROW && order != GSIM_JOIN_BY_SCORE) return fail(GSIM_ERR_INVALID, "unknown join order");
+    if (!(cutoff > 0.0f && cutoff <= 1.0f)) return fail(GSIM_ERR_INVALID, "join cutoff must be in (0, 1]");
+    if (metric == GSIM_METRIC_TVERSKY && !(std::isfinite(alpha) && alpha >= 0.0f && std::isfinite(beta) && beta >= 0.0f))
+        return fail(GSIM_ERR_INVALID, "join: Tversky alpha and beta must be finite and >= 0");
+    if (nl > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "join: 2^32 left rows or more");
+    if (db->nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "join: tables of 2^32 rows or more");
+    if (gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, "joins support rows of up to 4096 bits");
+    return GSIM_OK;
+}
+
+int check_join_state(const gsim_db* db, const char* which)
+{
+    if (!db->finalized) return fail(GSIM_ERR_STATE, std::string(which) + " not finalized (no rows on a GPU)");
+    if (db->fold > 1) return fail(GSIM_ERR_STATE, std::string("joins do not support folded tables: ") + which);
+    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, std::string("joins need single-shard handles: ") + which);
+    return GSIM_OK;
+}
+
+int run_join(gsim_db* db, const uint32_t* d_left, uint64_t nl, float cutoff, int metric, float alpha, float beta, int order, gsim_graph** out)
+{
+    gsim_graph* g = new (std::nothrow) gsim_graph;
+    if (!g) return fail(GSIM_ERR_NOMEM, "graph");
+    int rc;
+    try {
+        rc = join(db, db->shards[0], d_left, nl, cutoff, metric, alpha, beta, order, g);
+    } catch (const std::bad_alloc&) {
+        rc = fail(GSIM_ERR_NOMEM, "host memory for the join's lists");
+    }
+    if (rc != GSIM_OK) {
+        delete g;
+        return rc;
+    }
+    *out = g;
+    return GSIM_OK;
+}
+
+} // namespace
+} // namespace gsim_host
+
+using namespace gsim_host;
+
+extern "C" {
+
+int gsim_db_join_queries(gsim_db* db, const uint32_t* queries, uint64_t nq, float cutoff, int metric, float alpha, float beta, int order,
+                         gsim_graph** out)
+{
+    int rc = check_join_args(db, out, nq, cutoff, metric, alpha, beta, order);
+    if (rc != GSIM_OK) return rc;
+    if (nq && !queries) return fail(GSIM_ERR_INVALID, "NULL queries");
+    rc = check_join_state(db, "table");
+    if (rc != GSIM_OK) return rc;
+    std::lock_guard<std::mutex> guard(db->search_mutex);
+    Shard& s = db->shards[0];
+    DevBuf d_left;
+    if (nq) {
+        GSIM_HIP(set_device(s.device));
+        const size_t bytes = static_cast<size_t>(nq) * s.W * 4;
+        if (d_left.alloc(bytes) != hipSuccess) {
+            (void) hipGetLastError();
+            return fail(GSIM_ERR_NOMEM, "device memory for the join's left rows");
+        }
+        GSIM_HIP(hipMemcpyAsync(d_left.p, queries, bytes, hipMemcpyHostToDevice, s.stream));
+    }
+    return run_join(db, d_left.as<uint32_t>(), nq, cutoff, metric, alpha, beta, order, out);
+}
+
+int gsim_db_join(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, float cutoff, int metric, float alpha, float beta,
+                 int order, gsim_graph** out)
+{
+    if (lrow_begin > lrow_end) {
+        if (out) *out = nullptr;
+        return fail(GSIM_ERR_INVALID, "left row range: begin past end");
+    }
+    int rc = check_join_args(db, out, lrow_end - lrow_begin, cutoff, metric, alpha, beta, order);
+    if (rc != GSIM_OK) return rc;
+    if (!left) return fail(GSIM_ERR_INVALID, "NULL left handle");
+    if (lrow_end > left->nrows) return fail(GSIM_ERR_INVALID, "left row range outside the left table");
+    if (left->fp_bits != db->fp_bits) return fail(GSIM_ERR_INVALID, "the two handles have different fp_bits");
+    rc = check_join_state(db, "table");
+    if (rc == GSIM_OK && left != db) rc = check_join_state(left, "left table");
+    if (rc != GSIM_OK) return rc;
+    if (left->shards[0].device != db->shards[0].device) return fail(GSIM_ERR_STATE, "the two handles are on different devices");
+    // one call at a time on either handle
+    std::unique_lock<std::mutex> g1(db->search_mutex, std::defer_lock), g2(left->search_mutex, std::defer_lock);
+    if (left != db) std::lock(g1, g2);
+    else g1.lock();
+    const uint32_t* d_left = static_cast<const uint32_t*>(left->shards[0].d_rows) + lrow_begin * left->shards[0].W;
+    return run_join(db, d_left, lrow_end - lrow_begin, cutoff, metric, alpha, beta, order, out);
+}
+
+} // extern "C"

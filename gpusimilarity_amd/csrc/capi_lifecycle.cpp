@@ -68,6 +68,7 @@ gsim::Knobs read_knobs()
     k.debug_batch = std::getenv("GSIM_DEBUG_BATCH") ? 1 : 0;
     k.fold_full_on_device = env_value("GSIM_FOLD_FULL_ON_DEVICE", k.fold_full_on_device);
     if (const char* v = std::getenv("GSIM_FOLD_RESCORE")) k.fold_rescore_host = std::string(v) == "host" ? 1 : 0;
+    k.join_stream_max_rows = env_value("GSIM_JOIN_STREAM_MAX_ROWS", k.join_stream_max_rows);
     return k;
 }
 

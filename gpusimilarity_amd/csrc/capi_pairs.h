@@ -1,0 +1,84 @@
+// capi_pairs.h -- what gsim_db_neighbors (capi_neighbors.cpp) and the threshold joins (capi_join.cpp) share: the result
+// object, the handle's pair buffer with its overflow / exact-regrow protocol, the tile kernel's launch plan, and the CSR
+// build.  Implemented in capi_pairs.cpp.  Internal.
+#pragma once
+
+#include "capi_internal.h"
+
+#include <functional>
+
+struct gsim_graph {
+    std::vector<uint64_t> indptr;
+    std::vector<uint32_t> indices;
+    std::vector<float> scores;
+    gsim_graph_stats stats{};
+    bool is_join = false; // made by gsim_db_join / gsim_db_join_queries: `join` is filled
+    gsim_join_stats join{};
+};
+
+namespace gsim_host
+{
+
+// device memory owned for the length of one call
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf()
+    {
+        if (p) (void) hipFree(p);
+    }
+    hipError_t alloc(size_t bytes)
+    {
+        return hipMalloc(&p, bytes ? bytes : 16);
+    }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EventPair()
+    {
+        if (a) (void) hipEventDestroy(a);
+        if (b) (void) hipEventDestroy(b);
+    }
+    hipError_t create()
+    {
+        hipError_t e = hipEventCreate(&a);
+        return e == hipSuccess ? hipEventCreate(&b) : e;
+    }
+    double ms() const
+    {
+        float t = 0.0f;
+        return hipEventElapsedTime(&t, a, b) == hipSuccess ? static_cast<double>(t) : 0.0;
+    }
+};
+
+struct NbrLaunch {
+    uint32_t rt0, nrt, ct0, nct;
+};
+// Tile launches of a call over nlt tile rows x nct tile columns (rows of WP words), each within the work budget.
+std::vector<NbrLaunch> plan_launches(uint64_t nlt, uint64_t nct, bool tri, uint32_t WP);
+
+// Where a launch appends: the shard's pair buffer as it is now
+struct PairSink {
+    unsigned long long* keys;
+    float* vals;
+    unsigned long long* cursor;
+    uint64_t cap;
+};
+using PairLaunchFn = std::function<int(size_t l, const PairSink& sink)>; // enqueue launch l of the call on the shard's stream
+struct PairRun {
+    uint64_t total = 0;  // entries the call appended
+    uint64_t rerun = 0;  // launches run a second time
+    double ms = 0.0;     // HIP events around all launches, reruns included
+};
+// The n launches of a call, in order, each followed by a snapshot of the cursor (d_snap: n words; d_cursor is zeroed here).  If
+// they appended more than the buffer holds it grows to the exact size (GSIM_ERR_NOMEM if it cannot; the buffer is then as it
+// was), keeps what the launches before the first overflowing one appended, and runs the others once more; a different count
+// on that second pass is GSIM_ERR_STATE.  Returns with the stream idle.
+int run_pair_launches(Shard& s, size_t n, unsigned long long* d_cursor, unsigned long long* d_snap, const PairLaunchFn& launch, PairRun* out);
+
+// The pair buffer's `total` entries (keys = list << 32 | column) -> g's CSR over nout lists, columns + db->row_base; each list
+// by column (GSIM_JOIN_BY_ROW) or by (score descending, column) (GSIM_JOIN_BY_SCORE).  Fills g->stats.csr_ms / d2h_ms.
+int build_pair_csr(gsim_db* db, Shard& s, uint64_t total, uint64_t nout, int order, gsim_graph* g);
+
+} // namespace gsim_host

@@ -192,6 +192,8 @@ struct Knobs {
     int debug_batch = 0;             // GSIM_DEBUG_BATCH         print the batch flags (instrumented builds: phase counters)
     int fold_full_on_device = 1;     // GSIM_FOLD_FULL_ON_DEVICE
     int fold_rescore_host = 0;       // GSIM_FOLD_RESCORE=host
+    int join_stream_max_rows = 2;    // GSIM_JOIN_STREAM_MAX_ROWS  joins of at most this many left rows stream the table once per left row, larger
+                                     // ones take the tile kernel (0: always tiles; DESIGN.md section 11 has the crossover)
 };
 
 ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll, bool ragged = true);
@@ -341,10 +343,17 @@ struct NbrArgs {
     uint64_t cap;                // entries keys / vals hold
     unsigned long long* clk;     // this launch's {s_memtime, wall clock} at the start and end of one tile (nullptr: none)
 };
+// The join instantiations of the same kernel (gsim_db_join*): the left operand is not the table -- nl x WP words (16-byte
+// aligned) and their popc; row_begin = 0 and row_end = nl index THESE rows, tri is ignored, and no pair is excluded
+struct JoinTileArgs : NbrArgs {
+    const uint32_t* lrows;
+    const uint32_t* lpop;
+};
 uint32_t nbr_padded_words(uint32_t W); // 0: wider than kNbrMaxWords
 hipError_t launch_nbr_prepare(const void* rows, uint64_t nrows, uint32_t W, uint32_t WP, uint32_t* pad, uint32_t* pop, hipStream_t s);
 // tiles (rt0 .. rt0+nrt-1) x (ct0 .. ct0+nct-1), tile row rt = left rows row_begin + rt * kNbrTile ..
 hipError_t launch_nbr_tiles(const NbrArgs& a, uint32_t rt0, uint32_t nrt, uint32_t ct0, uint32_t nct, hipStream_t s);
+hipError_t launch_join_tiles(const JoinTileArgs& a, uint32_t rt0, uint32_t nrt, uint32_t ct0, uint32_t nct, hipStream_t s);
 hipError_t launch_nbr_snap(const unsigned long long* cursor, unsigned long long* snap, hipStream_t s);
 hipError_t nbr_sort_bytes(uint64_t n, uint32_t end_bit, size_t* bytes);
 hipError_t launch_nbr_csr(void* tmp, size_t tmp_bytes, const unsigned long long* keys, const float* vals, unsigned long long* keys_sorted,
@@ -383,6 +392,28 @@ hipError_t launch_maxmin_pass(const MaxMinArgs& m, const ScanGeometry& g, uint64
 // ... the same kernels with default-policy table loads (gsim_maxmin_cached.hip): for tables that fit the Infinity Cache
 hipError_t launch_maxmin_pass_cached(const MaxMinArgs& m, const ScanGeometry& g, uint64_t r0, uint64_t nrows, uint32_t wg0, uint32_t p,
                                      hipStream_t s);
+
+// ---- threshold joins, streaming route (gsim_join.hip, gsim_db_join / gsim_db_join_queries) -------------------------------------
+struct JoinArgs {
+    const void* rows;            // the whole table, nrows x W words
+    uint32_t W;
+    int metric;
+    float alpha, beta, cutoff;
+    const uint32_t* left;        // the call's left rows, W words each (16-byte aligned when W % 4 == 0)
+    unsigned long long* keys;    // (left row << 32) | table row: the pair buffer gsim_db_neighbors' tile kernel fills
+    float* vals;                 // score
+    unsigned long long* cursor;  // entries appended so far (keeps counting past cap)
+    uint64_t cap;
+};
+// One launch of left row l's pass: table rows [r0, r0 + nrows), g = maxmin_geometry(nrows, ...), r0 a multiple of 64.
+hipError_t launch_join_pass(const JoinArgs& j, const ScanGeometry& g, uint64_t r0, uint64_t nrows, uint32_t l, hipStream_t s);
+// GSIM_JOIN_BY_SCORE: the pairs sorted by (left, column) -- keys / scores as launch_nbr_csr's sort leaves them -- are sorted
+// once more, stably, by (left, score descending); then indptr, indices (+ row_base) and scores_out.  keys / scores are
+// overwritten; keys_tmp / cols_tmp hold n entries each.
+hipError_t join_score_sort_bytes(uint64_t n, uint32_t end_bit, size_t* bytes);
+hipError_t launch_join_by_score(void* tmp, size_t tmp_bytes, unsigned long long* keys, float* scores, unsigned long long* keys_tmp,
+                                uint32_t* cols_tmp, uint64_t n, uint32_t end_bit, uint64_t nrows_out, uint32_t row_base, uint64_t* indptr,
+                                uint32_t* indices, float* scores_out, hipStream_t s);
 
 hipError_t launch_generate(void* rows, uint64_t seed, int kind, uint64_t first_row, uint64_t nrows,
                            uint32_t W, hipStream_t s);

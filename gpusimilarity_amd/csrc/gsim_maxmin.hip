@@ -79,27 +79,6 @@ template <int NLW> struct MaxMinShared {
     uint32_t last;
 };
 
-// One row per lane, word by word: the widths that none of the streaming loops takes (32 and 64 bits; 13, 15, 17 ... words;
-// wider than 8192 bits by powers of two, ...).  Uncoalesced -- these widths are rare.
-__device__ __forceinline__ void maxmin_rows_generic(const ScanArgs& a, const ScanGeometry& g, MaxMinFilter& f, uint32_t w, int lane)
-{
-    const uint32_t* db = static_cast<const uint32_t*>(a.rows);
-    for (u64 c = w; c < g.nchunks; c += g.nwaves) {
-        const u64 row = c * 64u + static_cast<uint32_t>(lane);
-        const bool active = row < a.nrows;
-        uint32_t cc = 0, bb = 0;
-        if (active) {
-            const uint32_t* r = db + row * a.W;
-            for (uint32_t i = 0; i < a.W; i++) {
-                const uint32_t x = r[i];
-                cc += __popc(x & a.query[i]);
-                bb += __popc(x);
-            }
-        }
-        f.template offer_counts<1>(active, static_cast<uint32_t>(row), (cc << 16) + bb, a, lane);
-    }
-}
-
 // KIND 0: scan_rows<LPR, U>; 1: scan_rows_ragged<LPR, U>; 2: scan_rows_wragged<LPR, U> (LPR = words per row); 3: generic.
 template <int KIND, int LPR, int U>
 __global__ __launch_bounds__(kScanBlock) void maxmin_kernel(MaxMinArgs m, ScanGeometry g, u64 r0, u64 nrows, uint32_t wg0, uint32_t p)
@@ -141,7 +120,7 @@ __global__ __launch_bounds__(kScanBlock) void maxmin_kernel(MaxMinArgs m, ScanGe
     } else if constexpr (KIND == 2) {
         scan_rows_wragged<LPR, U>(a, g, f, w, lane, sh.words[wv]);
     } else {
-        maxmin_rows_generic(a, g, f, w, lane);
+        scan_rows_lane(a, g, f, w, lane);
     }
 
     const u64 k = wave_min64(f.key);

@@ -53,12 +53,30 @@ __global__ __launch_bounds__(256) void nbr_prepare_kernel(const uint32_t* __rest
     pop[r] = p;
 }
 
-template <int WP>
-__global__ __launch_bounds__(kNbrBlock) void nbr_tile_kernel(NbrArgs a, uint32_t rt0, uint32_t ct0)
+// JOIN (gsim_db_join*, launch_join_tiles): the left rows are a.lrows / a.lpop instead of the table's own, there is no triangle,
+// and no pair is excluded -- separate instantiations, so that the self-join's stay what they are.
+template <bool JOIN, class Args> __device__ __forceinline__ auto tile_tri(const Args& a)
+{
+    if constexpr (JOIN) return 0;
+    else return a.tri;
+}
+template <bool JOIN, class Args> __device__ __forceinline__ const uint32_t* tile_left_rows(const Args& a)
+{
+    if constexpr (JOIN) return a.lrows;
+    else return a.rows;
+}
+template <bool JOIN, class Args> __device__ __forceinline__ const uint32_t* tile_left_pop(const Args& a)
+{
+    if constexpr (JOIN) return a.lpop;
+    else return a.pop;
+}
+
+template <int WP, bool JOIN = false, class Args = NbrArgs>
+__global__ __launch_bounds__(kNbrBlock) void nbr_tile_kernel(Args a, uint32_t rt0, uint32_t ct0)
 {
     const uint32_t rt = rt0 + blockIdx.y;
     const uint32_t ct = ct0 + blockIdx.x;
-    if (a.tri && ct < rt) return; // below the diagonal: that pair was found from the other side
+    if (tile_tri<JOIN>(a) && ct < rt) return; // below the diagonal: that pair was found from the other side
     const int lane = threadIdx.x & 63;
     const uint32_t wib = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
     const u64 i0 = a.row_begin + static_cast<u64>(rt) * kNbrTile;
@@ -85,11 +103,11 @@ __global__ __launch_bounds__(kNbrBlock) void nbr_tile_kernel(NbrArgs a, uint32_t
     uint32_t nl = static_cast<uint32_t>(iend - i0);
     // diagonal tile (i0 == first right row of the tile): left row i0 + t pairs with some right row of this wave only if
     // t < 64 wib + 63
-    if (a.tri && ct == rt && nl > wib * 64u + 63u) nl = wib * 64u + 63u;
+    if (tile_tri<JOIN>(a) && ct == rt && nl > wib * 64u + 63u) nl = wib * 64u + 63u;
 
     const float cut_lo = valu_cutoff_lo(a.cutoff);
-    const uint32_t per = a.tri ? 2u : 1u;
-    const const_u32x4p lrows = (const_u32x4p) (a.rows) + i0 * (WP / 4);
+    const uint32_t per = tile_tri<JOIN>(a) ? 2u : 1u;
+    const const_u32x4p lrows = (const_u32x4p) (tile_left_rows<JOIN>(a)) + i0 * (WP / 4);
     // left row t against this lane's right row: keep == (score_of(...) >= cutoff), s = that score
     auto pair = [&](uint32_t t, uint32_t av, float& s) __attribute__((always_inline)) -> bool {
         const const_u32x4p qw = lrows + static_cast<u64>(t) * (WP / 4);
@@ -104,7 +122,7 @@ __global__ __launch_bounds__(kNbrBlock) void nbr_tile_kernel(NbrArgs a, uint32_t
         }
         const uint32_t c = (acc0 + acc1) + (acc2 + acc3);
         const u64 i = i0 + t;
-        const bool valid = jin && (a.tri ? j > i : j != i);
+        const bool valid = JOIN ? jin : jin && (tile_tri<JOIN>(a) ? j > i : j != i);
         const float den = score_den(a.metric, a.alpha, a.beta, av, b, c);
         const float cf = static_cast<float>(c);
         const bool maybe = valid && !valu_surely_not_kept(cut_lo, cf, den, c);
@@ -122,7 +140,7 @@ __global__ __launch_bounds__(kNbrBlock) void nbr_tile_kernel(NbrArgs a, uint32_t
     for (uint32_t t = 0; t < nl; t++) {
         if ((t & 63u) == 0) { // popc of the next 64 left rows, one per lane (read back with v_readlane)
             const u64 il = i0 + t + static_cast<uint32_t>(lane);
-            vpop = il < iend ? a.pop[il] : 0u;
+            vpop = il < iend ? tile_left_pop<JOIN>(a)[il] : 0u;
         }
         const uint32_t av = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(vpop), static_cast<int>(t & 63u)));
         float s;
@@ -142,7 +160,7 @@ __global__ __launch_bounds__(kNbrBlock) void nbr_tile_kernel(NbrArgs a, uint32_t
                 const uint32_t t = w * 32u + static_cast<uint32_t>(__builtin_ctz(rows));
                 rows &= rows - 1u;
                 const u64 i = i0 + t;
-                const uint32_t av = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(a.pop[i])));
+                const uint32_t av = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(tile_left_pop<JOIN>(a)[i])));
                 float s;
                 const bool keep = pair(t, av, s);
                 const u64 m = __ballot(keep);
@@ -152,7 +170,7 @@ __global__ __launch_bounds__(kNbrBlock) void nbr_tile_kernel(NbrArgs a, uint32_t
                         a.keys[pos] = ((i - a.row_begin) << 32) | j;
                         a.vals[pos] = s;
                     }
-                    if (a.tri && pos + 1 < a.cap) { // the same pair under the right row (full-table calls: row_begin == 0)
+                    if (tile_tri<JOIN>(a) && pos + 1 < a.cap) { // the same pair under the right row (full-table calls: row_begin == 0)
                         a.keys[pos + 1] = (j << 32) | i;
                         a.vals[pos + 1] = s;
                     }
@@ -219,6 +237,21 @@ hipError_t launch_nbr_tiles(const NbrArgs& a, uint32_t rt0, uint32_t nrt, uint32
     case 32: hipLaunchKernelGGL(nbr_tile_kernel<32>, grid, block, 0, s, a, rt0, ct0); break;
     case 64: hipLaunchKernelGGL(nbr_tile_kernel<64>, grid, block, 0, s, a, rt0, ct0); break;
     case 128: hipLaunchKernelGGL(nbr_tile_kernel<128>, grid, block, 0, s, a, rt0, ct0); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_join_tiles(const JoinTileArgs& a, uint32_t rt0, uint32_t nrt, uint32_t ct0, uint32_t nct, hipStream_t s)
+{
+    const dim3 grid(nct, nrt), block(kNbrBlock);
+    switch (a.WP) {
+    case 4: hipLaunchKernelGGL((nbr_tile_kernel<4, true, JoinTileArgs>), grid, block, 0, s, a, rt0, ct0); break;
+    case 8: hipLaunchKernelGGL((nbr_tile_kernel<8, true, JoinTileArgs>), grid, block, 0, s, a, rt0, ct0); break;
+    case 16: hipLaunchKernelGGL((nbr_tile_kernel<16, true, JoinTileArgs>), grid, block, 0, s, a, rt0, ct0); break;
+    case 32: hipLaunchKernelGGL((nbr_tile_kernel<32, true, JoinTileArgs>), grid, block, 0, s, a, rt0, ct0); break;
+    case 64: hipLaunchKernelGGL((nbr_tile_kernel<64, true, JoinTileArgs>), grid, block, 0, s, a, rt0, ct0); break;
+    case 128: hipLaunchKernelGGL((nbr_tile_kernel<128, true, JoinTileArgs>), grid, block, 0, s, a, rt0, ct0); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

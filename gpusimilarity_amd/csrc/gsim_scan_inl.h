@@ -332,6 +332,28 @@ __device__ __forceinline__ void scan_rows_wragged(const ScanArgs& a, const ScanG
     }
 }
 
+// One row per lane, word by word: the widths that none of the streaming loops takes (32 and 64 bits; 13, 15, 17 ... words;
+// wider than 8192 bits by powers of two, ...).  Uncoalesced -- these widths are rare.  (gsim_maxmin.hip, gsim_join.hip)
+template <typename Filter>
+__device__ __forceinline__ void scan_rows_lane(const ScanArgs& a, const ScanGeometry& g, Filter& f, uint32_t w, int lane)
+{
+    const uint32_t* db = static_cast<const uint32_t*>(a.rows);
+    for (u64 c = w; c < g.nchunks; c += g.nwaves) {
+        const u64 row = c * 64u + static_cast<uint32_t>(lane);
+        const bool active = row < a.nrows;
+        uint32_t cc = 0, bb = 0;
+        if (active) {
+            const uint32_t* r = db + row * a.W;
+            for (uint32_t i = 0; i < a.W; i++) {
+                const uint32_t x = r[i];
+                cc += __popc(x & a.query[i]);
+                bb += __popc(x);
+            }
+        }
+        f.template offer_counts<1>(active, static_cast<uint32_t>(row), (cc << 16) + bb, a, lane);
+    }
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize, set once per device and kernel (whether the runtime keeps the attribute
 // per function or per device is its business; a multi-device handle launches the same kernel on several devices).
 struct DynLdsOnce {

@@ -113,6 +113,18 @@ class FingerprintDB:
         [row_begin, row_end), each row's list sorted by column.  No counterpart in the reference."""
         return self._table.neighbors(float(cutoff), metric, alpha, beta, row_begin, row_end)
 
+    def join(self, left, cutoff: float, metric: int = capi.METRIC_TANIMOTO, alpha: float = 1.0, beta: float = 1.0,
+             order: int = capi.JOIN_BY_ROW, row_begin: int = 0, row_end=None):
+        """Every row of this table at or above `cutoff`, per left row (gsim_db_join / gsim_db_join_queries) -> CSR
+        (indptr, indices, scores).  `left`: another FingerprintDB on the same GPU, or an array of fingerprints."""
+        if isinstance(left, FingerprintDB):
+            left = left._table
+        return self._table.join(left, float(cutoff), metric, alpha, beta, order, row_begin, row_end)
+
+    def screen(self, query):
+        """The fingerprint screen of a substructure search: the rows whose bits include all of `query`'s (Tversky 1 / 0 = 1.0)."""
+        return self.join(query, 1.0, capi.METRIC_TVERSKY, 1.0, 0.0)[1]
+
     def butina(self, cutoff: float, metric: int = capi.METRIC_TANIMOTO, alpha: float = 1.0, beta: float = 1.0):
         """Taylor-Butina clustering at `cutoff` -> one tuple per cluster in creation order: the centroid first, then
         its members ascending (the shape of RDKit's Butina.ClusterData result)."""

@@ -361,6 +361,57 @@ int gsim_graph_destroy(gsim_graph* g);
 int gsim_butina(const uint64_t* indptr, const uint32_t* indices, uint64_t nrows, uint32_t* cluster_of, uint32_t* centroids,
                 uint64_t* nclusters);
 
+/* ---- threshold joins: every table row at or above a cutoff, per left row --------------------------------------------------------- */
+/* gsim_db_join_queries / gsim_db_join: for each of nl LEFT rows -- the nq fingerprints at `queries` (host memory, nq x fp_bits / 32
+ * words), or the rows [lrow_begin, lrow_end) of another handle `left` that is resident on the same device -- the list of EVERY row
+ * of the table `db` at or above `cutoff` (chemfp's threshold search; with many left rows a library-against-library join; with
+ * Tversky 1 / 0 at cutoff 1.0 the fingerprint screen "rows whose bits include all of the left row's").  No counterpart in the
+ * reference.  The result is a gsim_graph: gsim_graph_shape / _copy / _destroy work on it, gsim_graph_get_stats reports the call's
+ * totals (launches of either route, the time of all of them in tile_ms), gsim_graph_get_join_stats the details.
+ *   - list i (i = position in `queries`, or left row - lrow_begin) holds every table row j with
+ *     score(query = left row i, row j) >= cutoff, where the score is bit for bit the `score` gsim_db_search returns for that query
+ *     and that row (a = popc(left row), b = popc(table row)).  NaN (0 / 0) is never >= cutoff: an all-zero left row has an empty
+ *     list.  No pair is excluded: joining a handle with itself (left == db is allowed) lists every non-zero row under itself, 1.0;
+ *   - indices = table row + the TABLE handle's row base (as gsim_hit.row; the left handle's base plays no part); indptr has nl + 1
+ *     entries;
+ *   - cutoff must be in (0, 1];
+ *   - metrics: GSIM_METRIC_TANIMOTO, and GSIM_METRIC_TVERSKY with any finite alpha >= 0, beta >= 0 -- asymmetric included;
+ *   - order GSIM_JOIN_BY_ROW: each list by table row, ascending.  GSIM_JOIN_BY_SCORE: (score descending, row ascending), exactly the
+ *     order of gsim_db_search's hits.  Either way the output is byte-identical from run to run and does not depend on the route:
+ *     calls of at most GSIM_JOIN_STREAM_MAX_ROWS left rows (read once per handle, the table's) stream the table once
+ *     per left row, larger ones run gsim_db_neighbors' tile kernel on the rectangle left x table;
+ *   - GSIM_ERR_INVALID, checked before any device state: NULL db / out / left (NULL queries with nq > 0), unknown metric or order,
+ *     cutoff outside (0, 1] or NaN, Tversky alpha / beta negative or not finite, nl >= 2^32, a table of 2^32 rows or more,
+ *     lrow_begin > lrow_end or lrow_end past the left handle's count, handles of different fp_bits, rows wider than 4096 bits.
+ *     GSIM_ERR_STATE: either handle multi-shard, folded or not on a GPU; handles on different devices.  nl == 0: an empty graph
+ *     (indptr = {0}), GSIM_OK;
+ *   - tables from gsim_db_generate and gsim_db_attach_device_rows work on either side; no host copy is needed;
+ *   - runs on the table handle's stream under the one-call-at-a-time rule (of both handles), leaves the search state of both as it
+ *     was, and keeps the pair buffer with the table handle (shared with gsim_db_neighbors; 12 bytes per listed pair; sorting takes
+ *     about as much again for the length of the call).  If device memory for the call's exact size cannot be had:
+ *     GSIM_ERR_NOMEM, nothing truncated, nothing leaked. */
+#define GSIM_JOIN_BY_ROW   0   /* each list by table row, ascending                                   */
+#define GSIM_JOIN_BY_SCORE 1   /* each list in gsim_db_search's order: score descending, row ascending */
+typedef struct {
+    uint64_t rows_streamed;   /* left rows taken by the streaming route (one pass over the table each)                        */
+    uint64_t rows_tiled;      /* left rows taken by the tile route                                                            */
+    uint64_t stream_launches; /* launches of the streaming kernel (a pass over a long table is cut into launches of <= ~7 ms) */
+    uint64_t tile_launches;   /* launches of the tile kernel                                                                  */
+    uint64_t launches_rerun;  /* ... of either, run once more because the pair buffer overflowed (it grows to the exact size)  */
+    uint64_t pairs;           /* entries listed                                                                               */
+    double stream_ms;         /* HIP events on the table handle's stream: all streaming launches, reruns included             */
+    double tile_ms;           /* ... all tile launches                                                                        */
+    double csr_ms;            /* the sort(s) + row offsets, on the device                                                     */
+    double d2h_ms;            /* CSR into host memory                                                                         */
+    double wall_ms;           /* the whole call, host clock                                                                   */
+    double clock_mhz;         /* tile route: shader clock the kernel ran at (as gsim_graph_stats.clock_mhz); 0 when streaming */
+} gsim_join_stats;
+int gsim_db_join_queries(gsim_db* db, const uint32_t* queries, uint64_t nq, float cutoff, int metric, float alpha, float beta,
+                         int order, gsim_graph** out);
+int gsim_db_join(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, float cutoff, int metric, float alpha,
+                 float beta, int order, gsim_graph** out);
+int gsim_graph_get_join_stats(const gsim_graph* g, gsim_join_stats* out); /* GSIM_ERR_INVALID for a gsim_db_neighbors result */
+
 /* ---- MaxMin diversity picking --------------------------------------------------------------------------------------------------- */
 /* gsim_db_maxmin: `npicks` mutually dissimilar rows of a single-shard, unfolded handle with N rows, by the MaxMin rule (RDKit's
  * MaxMinPicker; no counterpart in the reference).  One pass over the table per pick, on the device.
