@@ -57,6 +57,11 @@ class GsimMaxMinStats(C.Structure):
                 ("d2h_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
+class GsimRowsetStats(C.Structure):
+    _fields_ = [("selected", C.c_uint64), ("queries_gather", C.c_uint64), ("queries_stream", C.c_uint64), ("launches", C.c_uint64),
+                ("kernel_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -78,6 +83,7 @@ EXPORTS = [
     "gsim_db_neighbors", "gsim_graph_shape", "gsim_graph_copy", "gsim_graph_get_stats", "gsim_graph_destroy", "gsim_butina",
     "gsim_db_join_queries", "gsim_db_join", "gsim_graph_get_join_stats",
     "gsim_db_maxmin",
+    "gsim_rowset_from_rows", "gsim_rowset_from_bitmap", "gsim_rowset_count", "gsim_rowset_rows", "gsim_rowset_destroy", "gsim_db_search_rows",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -164,6 +170,13 @@ def load():
         "gsim_butina": (C.c_int, [u64p, u32p, C.c_uint64, u32p, u32p, u64p]),
         "gsim_db_maxmin": (C.c_int, [vp, C.c_uint32, u32p, C.c_uint32, C.c_int, C.c_float, C.c_float, C.c_float, u32p,
                                      C.POINTER(C.c_float), u32p, C.POINTER(C.c_float), u32p, C.POINTER(GsimMaxMinStats)]),
+        "gsim_rowset_from_rows": (C.c_int, [vp, u32p, C.c_uint64, C.c_uint32, C.POINTER(vp)]),
+        "gsim_rowset_from_bitmap": (C.c_int, [vp, u32p, C.c_uint32, C.POINTER(vp)]),
+        "gsim_rowset_count": (C.c_int, [vp, u64p]),
+        "gsim_rowset_rows": (C.c_int, [vp, u32p]),
+        "gsim_rowset_destroy": (C.c_int, [vp]),
+        "gsim_db_search_rows": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, vp, u32p, u64p,
+                                          C.POINTER(GsimRowsetStats)]),
         "gsim_last_error": (C.c_char_p, []),
         "gsim_version": (C.c_char_p, []),
     }
@@ -217,6 +230,39 @@ def result_block_bytes(k: int) -> int:
 
 def _u32(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+class RowSet:
+    """``gsim_rowset``: a set of rows of one :class:`Table` (Table.rowset makes it, Table.search_rows searches inside it).
+    It lives in the table's device memory: close it (or drop it) before the table."""
+
+    def __init__(self, table, handle):
+        self._L = table._L
+        self._h = handle
+        self._table = table  # (keeps the handle it belongs to alive)
+
+    @property
+    def count(self) -> int:
+        n = C.c_uint64(0)
+        check(self._L.gsim_rowset_count(self._h, C.byref(n)))
+        return n.value
+
+    def rows(self) -> np.ndarray:
+        """The selected rows, ascending, row base included."""
+        out = np.empty(self.count, dtype=np.uint32)
+        check(self._L.gsim_rowset_rows(self._h, _u32(out) if len(out) else None))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.gsim_rowset_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Table:
@@ -376,6 +422,41 @@ class Table:
             stats.update({f: getattr(st, f) for f, _ in GsimMaxMinStats._fields_})
         out = (picks[:n.value].copy(), scores[:n.value].copy())
         return out + (row_score, nearest) if assign else out
+
+    def rowset(self, rows=None, bitmap=None, exclude=False) -> RowSet:
+        """gsim_rowset_from_rows / _from_bitmap: `rows` are row indices including the row base (gsim_hit.row values), any order,
+        duplicates collapse; `bitmap` is (count + 31) // 32 uint32 words, bit r % 32 of word r // 32 selecting row r without the
+        row base.  exclude=True: every row of the table except those."""
+        if (rows is None) == (bitmap is None):
+            raise ValueError("give either rows or bitmap")
+        h = C.c_void_p()
+        flags = 1 if exclude else 0
+        if bitmap is not None:
+            b = np.ascontiguousarray(bitmap, dtype=np.uint32).reshape(-1)
+            if len(b) < (self.count() + 31) // 32:
+                raise ValueError("bitmap needs (count + 31) // 32 words")
+            check(self._L.gsim_rowset_from_bitmap(self._h, _u32(b), flags, C.byref(h)))
+        else:
+            r = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+            check(self._L.gsim_rowset_from_rows(self._h, _u32(r) if len(r) else None, len(r), flags, C.byref(h)))
+        return RowSet(self, h)
+
+    def search_rows(self, rowset, queries, k, cutoff=0.0, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, stats=False):
+        """gsim_db_search_rows: the top k of the rows in `rowset` -> what :meth:`search` returns (list of HIT_DTYPE arrays, approx);
+        with stats=True a third item, the call's gsim_rowset_stats as a dict."""
+        q = np.ascontiguousarray(queries, dtype=np.uint32).reshape(-1, self.W)
+        nq = q.shape[0]
+        hits = np.zeros((nq, max(k, 1)), dtype=HIT_DTYPE)
+        counts = np.zeros(nq, dtype=np.uint32)
+        approx = np.zeros(nq, dtype=np.uint64)
+        st = GsimRowsetStats()
+        check(self._L.gsim_db_search_rows(self._h, rowset._h, _u32(q), nq, k, cutoff, metric, alpha, beta,
+                                          hits.ctypes.data_as(C.c_void_p), _u32(counts),
+                                          approx.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(st)))
+        out = [hits[i, :counts[i]].copy() for i in range(nq)], approx
+        if stats:
+            out += ({f: getattr(st, f) for f, _ in GsimRowsetStats._fields_},)
+        return out
 
     def make_search_buffers(self, nq, k):
         """Preallocated outputs for :meth:`search_into` (latency-sensitive callers)."""

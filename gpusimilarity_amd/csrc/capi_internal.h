@@ -127,6 +127,8 @@ struct Shard {
     gsim::LargeKState* d_lk = nullptr;
     uint32_t* d_bincur = nullptr;    // kScanBins cursors of launch_fused_binsort (zero between queries) + kScanBins words: the bins' first positions
     bool classic_ready = false; // candidate / finalist scratch of the four-kernel pipeline (allocated on first use)
+    uint64_t cand_slots = 0;    // gsim_db_search_rows: slots of d_cand / d_cand_cb and words of d_seg_count where one of its geometries needed
+    uint32_t seg_waves = 0;     // more than geo's (0: as geo -- capi_subset.cpp grows them, never shrinks)
     void* d_pub = nullptr;      // single-launch path: the workgroups' published-candidate regions (128 KB each)
     void* d_hdr = nullptr;      // ... and their headers (64 B each)
     uint32_t* d_summ = nullptr; // single-launch path: per-wave checkpoint summaries (16 KB, zero between queries)
@@ -216,6 +218,17 @@ template <class T> struct NoInitAllocator : std::allocator<T> {
     template <class U, class... Args> void construct(U* p, Args&&... args) { ::new (static_cast<void*>(p)) U(std::forward<Args>(args)...); }
 };
 
+// A row set (gsim_rowset_*, capi_subset.cpp): device memory of the handle it was made for, immutable.
+struct gsim_rowset {
+    gsim_db* owner = nullptr;
+    int device = 0;
+    uint64_t nrows = 0;       // rows of the owner's table when the set was made
+    uint64_t count = 0;       // selected rows
+    uint32_t row_base = 0;    // ... and its row base then (what gsim_rowset_rows adds)
+    uint32_t* d_bits = nullptr; // rowset_words(nrows) + kRowsetPadWords words
+    uint32_t* d_list = nullptr; // count rows, ascending, without the row base
+};
+
 struct gsim_db {
     uint32_t fp_bits = 0;
     uint32_t W = 0;
@@ -292,6 +305,9 @@ int finish_query_sync(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k, 
 int search_one(gsim_db* db, const uint32_t* query, uint32_t k, float cutoff, int metric, float alpha, float beta, gsim_hit* hits,
                uint32_t* count, uint64_t* approx);
 int check_search_args(gsim_db* db, const uint32_t* queries, int metric);
+int ensure_classic_scratch(Shard& s);
+int enqueue_scan_tail(gsim_db* db, Shard& s, const gsim::ScanArgs& a, const gsim::ScanGeometry& g, uint32_t row_base, uint64_t approx_if_no_cutoff,
+                      void* out);
 // capi_batch.cpp: multi-query passes
 int enqueue_batch(gsim_db* db, Shard& s, const uint32_t* queries, uint32_t nq, uint32_t k, float cutoff, int metric, float alpha,
                   float beta, uint32_t row_base, void* results, bool allow_mfma = true);

@@ -11,7 +11,7 @@ namespace gsim_host
 // Scratch of the four-kernel pipeline (per-wave candidate segments + finalists: the worst case is every row a candidate, 24 B per
 // row).  The single-launch path keeps its candidates in LDS and needs none of it, so it is only allocated when a query takes the
 // classic pipeline: k above the publishing route's, widths without a specialised scan, or a query handed back.
-static int ensure_classic_scratch(Shard& s)
+int ensure_classic_scratch(Shard& s)
 {
     if (s.classic_ready) return GSIM_OK;
     GSIM_HIP(set_device(s.device));
@@ -376,6 +376,26 @@ int enqueue_query_impl(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k,
     return GSIM_OK;
 }
 } // namespace
+
+// The four-kernel pipeline's tail behind a scan of the caller's own (capi_subset.cpp): compaction of the candidate segments of
+// geometry g, then the select kernel or, above kSelectCap, the large-k select and sort -- as enqueue_classic runs them.
+int enqueue_scan_tail(gsim_db* db, Shard& s, const gsim::ScanArgs& a, const gsim::ScanGeometry& g, uint32_t row_base, uint64_t approx_if_no_cutoff,
+                      void* out)
+{
+    GSIM_HIP(gsim::launch_compact(a, g, s.d_final, s.d_final_cb, s.final_cap, s.stream));
+    if (a.k <= static_cast<uint32_t>(gsim::kSelectCap)) {
+        GSIM_HIP(gsim::launch_select(a, s.d_final, s.d_final_cb, s.final_cap, row_base, out, s.stream));
+        return GSIM_OK;
+    }
+    const uint32_t np2 = next_pow2_u32(a.k);
+    const int rc = ensure_largek_scratch(s, false, np2);
+    if (rc != GSIM_OK) return rc;
+    uint32_t* hint = s.h_done + 15; // (enqueue_largek_tail's hint word)
+    const bool one_block = *static_cast<volatile uint32_t*>(hint) <= static_cast<uint32_t>(db->knobs.largek_one_block_max);
+    GSIM_HIP(gsim::launch_largek_select(a, s.d_final, s.final_cap, s.d_lk, s.d_large, np2, hint, one_block, s.stream));
+    GSIM_HIP(gsim::launch_largek_sort_emit(a, s.d_large, np2, s.d_lk, row_base, approx_if_no_cutoff, 1u, out, s.stream));
+    return GSIM_OK;
+}
 
 int enqueue_query(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k, float cutoff, int metric, float alpha,
                   float beta, uint32_t row_base, void* out, bool caller_syncs, QueryMode mode, uint32_t pipe_slot)

@@ -194,6 +194,9 @@ struct Knobs {
     int fold_rescore_host = 0;       // GSIM_FOLD_RESCORE=host
     int join_stream_max_rows = 2;    // GSIM_JOIN_STREAM_MAX_ROWS  joins of at most this many left rows stream the table once per left row, larger
                                      // ones take the tile kernel (0: always tiles; DESIGN.md section 11 has the crossover)
+    int subset_gather_max_permille = 250; // GSIM_SUBSET_GATHER_MAX_PERMILLE  gsim_db_search_rows gathers the selected rows when
+                                     // selected x max(row bytes, 128) x 1000 <= this x N x row bytes, else streams the table under the
+                                     // mask (0: always stream, 1000 or more: always gather; DESIGN.md section 12 has the crossover)
 };
 
 ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll, bool ragged = true);
@@ -414,6 +417,27 @@ hipError_t join_score_sort_bytes(uint64_t n, uint32_t end_bit, size_t* bytes);
 hipError_t launch_join_by_score(void* tmp, size_t tmp_bytes, unsigned long long* keys, float* scores, unsigned long long* keys_tmp,
                                 uint32_t* cols_tmp, uint64_t n, uint32_t end_bit, uint64_t nrows_out, uint32_t row_base, uint64_t* indptr,
                                 uint32_t* indices, float* scores_out, hipStream_t s);
+
+// ---- row sets (gsim_subset.hip, gsim_rowset_* / gsim_db_search_rows) ------------------------------------------------------------
+// A set's bitmap: rowset_words(nrows) words + kRowsetPadWords zero words (the streaming route reads three consecutive words)
+constexpr uint64_t kRowsetPadWords = 2;
+inline uint64_t rowset_words(uint64_t nrows) { return (nrows + 31) / 32; }
+// rows d_rows[0 .. n) (with the row base, all inside the table) marked in the zeroed bitmap
+hipError_t launch_rowset_mark(const uint32_t* d_rows, uint64_t n, uint32_t row_base, uint64_t nrows, uint32_t* bits, hipStream_t s);
+// the bitmap finished in place (src: the caller's words instead of the marks; invert: an exclusion set; zero past the last row and in
+// the padding -- nalloc = words + padding) and popc[0 .. words] = its words' popcounts (popc[words] = 0)
+hipError_t launch_rowset_finish(uint32_t* bits, const uint32_t* src, uint64_t nrows, uint64_t nalloc, int invert, uint32_t* popc, hipStream_t s);
+// offs[0 .. n) = exclusive prefix sums of popc[0 .. n) (n = words + 1: offs[words] is the set's size)
+hipError_t rowset_scan_bytes(uint64_t n, size_t* bytes);
+hipError_t launch_rowset_offsets(void* tmp, size_t tmp_bytes, const uint32_t* popc, uint32_t* offs, uint64_t n, hipStream_t s);
+// list[offs[t] ..] = the rows of word t, ascending
+hipError_t launch_rowset_list(const uint32_t* bits, const uint32_t* offs, uint64_t nwords, uint32_t* list, hipStream_t s);
+// The two scans of gsim_db_search_rows; both leave what launch_scan leaves (candidate segments of g.seg_cap slots per wave,
+// seg_count, QueryState) for launch_compact and the tail behind it.
+ScanGeometry subset_scan_geometry(uint64_t nrows, uint32_t W, int num_cus);  // streaming: the whole table under the mask
+ScanGeometry subset_gather_geometry(uint64_t nsel, uint32_t W, int num_cus); // gather: the list
+hipError_t launch_subset_scan(const ScanArgs& a, const ScanGeometry& g, const uint32_t* bits, hipStream_t s);
+hipError_t launch_subset_gather(const ScanArgs& a, const ScanGeometry& g, const uint32_t* list, uint32_t nsel, hipStream_t s);
 
 hipError_t launch_generate(void* rows, uint64_t seed, int kind, uint64_t first_row, uint64_t nrows,
                            uint32_t W, hipStream_t s);

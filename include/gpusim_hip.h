@@ -446,6 +446,52 @@ int gsim_db_maxmin(gsim_db* db, uint32_t npicks, const uint32_t* seeds, uint32_t
                    float max_score, uint32_t* picks, float* pick_scores, uint32_t* npicked, float* row_score, uint32_t* nearest,
                    gsim_maxmin_stats* stats);
 
+/* ---- row sets: exact top-k search restricted to a subset of the table ------------------------------------------------------------- */
+/* A gsim_rowset is a set of rows of ONE single-shard, unfolded handle ("the compounds in stock", "the rows that passed the property
+ * filter", "this Butina cluster", "everything except what we already bought"); gsim_db_search_rows searches inside it.  No
+ * counterpart in the reference.
+ * THE RESULT RULE: for every query the result is exactly what gsim_db_search would return on a table holding only the selected rows,
+ * in ascending row order, with every hit's `row` mapped back to the original row (+ the row base):
+ *   - scores, `common` and `popc_db` are bit for bit gsim_db_search's; the order is (score descending, row ascending); the boundary
+ *     tie group keeps its lowest selected rows; counts[q] = min(k, kept);
+ *   - approx[q] (approx may be NULL) = the number of selected rows when cutoff <= 0, else the number of selected rows with
+ *     score >= cutoff (NaN is never counted);
+ *   - an empty set is legal: zero hits, approx 0.  A set of all rows gives gsim_db_search's result byte for byte.
+ * Rows: gsim_rowset_from_rows takes row indices INCLUDING the handle's row base, i.e. gsim_hit.row values -- hit lists, MaxMin picks,
+ * Butina members and join columns go straight in -- in any order; duplicates collapse (set semantics).  gsim_rowset_from_bitmap: bit
+ * r % 32 of word r / 32 selects row r WITHOUT the row base; the caller supplies (count + 31) / 32 words; bits past the last row are
+ * ignored.  GSIM_ROWSET_EXCLUDE: the set is every row of the table except the ones given.  gsim_rowset_rows writes the set's
+ * gsim_rowset_count rows, ascending, row base included.
+ * Lifetime: a row set belongs to the handle it was made for, lives in that handle's device memory (one bit per table row + 4 bytes
+ * per selected row), is immutable and serves any number of searches; destroy it before its handle.
+ * Execution: gsim_db_search_rows runs on the handle's stream under the one-call-at-a-time rule, answers the nq queries one after
+ * another (k is the stride of `hits`, as gsim_db_search's), and leaves the search state as it found it: a gsim_db_search before and
+ * after returns identical bytes, the back-off counters and the lanes are untouched.  Per call it either GATHERS the selected rows
+ * (sparse sets: reads only them) or STREAMS the table under the set's bitmap (dense sets): gather when
+ * selected x max(row bytes, 128) x 1000 <= GSIM_SUBSET_GATHER_MAX_PERMILLE x N x row bytes (read once per handle; 0: always stream,
+ * 1000 or more: always gather).  The result does not depend on the route.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / out / rs / queries / hits / counts / bits (NULL rows with n > 0),
+ * unknown flag bits, a row outside [row_base, row_base + N), n >= 2^32, a table of 2^32 rows or more, a row set made for another
+ * handle, an unknown metric (gsim_db_search's checks; like it, k == 0 is legal and returns no hits).  *out is cleared on failure.
+ * GSIM_ERR_STATE: a table not on a GPU, a multi-shard handle, a folded table.  GSIM_ERR_NOMEM as elsewhere. */
+typedef struct gsim_rowset gsim_rowset;
+#define GSIM_ROWSET_EXCLUDE 1u  /* the set is every row of the table EXCEPT the ones given */
+typedef struct {
+    uint64_t selected;       /* rows in the set                                                                               */
+    uint64_t queries_gather; /* queries answered by the gather route                                                          */
+    uint64_t queries_stream; /* queries answered by the streaming route                                                       */
+    uint64_t launches;       /* kernel launches: per query the scan, the compaction and the select (k > 8192: three for it)   */
+    double kernel_ms;        /* HIP events around every query's launches, summed                                              */
+    double wall_ms;          /* the whole call, host clock                                                                    */
+} gsim_rowset_stats;
+int gsim_rowset_from_rows(gsim_db* db, const uint32_t* rows, uint64_t n, uint32_t flags, gsim_rowset** out);
+int gsim_rowset_from_bitmap(gsim_db* db, const uint32_t* bits, uint32_t flags, gsim_rowset** out);
+int gsim_rowset_count(const gsim_rowset* rs, uint64_t* n);
+int gsim_rowset_rows(const gsim_rowset* rs, uint32_t* rows);   /* ascending, count entries, row base included */
+int gsim_rowset_destroy(gsim_rowset* rs);
+int gsim_db_search_rows(gsim_db* db, const gsim_rowset* rs, const uint32_t* queries, uint32_t nq, uint32_t k, float cutoff, int metric,
+                        float alpha, float beta, gsim_hit* hits, uint32_t* counts, uint64_t* approx, gsim_rowset_stats* stats /* or NULL */);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
