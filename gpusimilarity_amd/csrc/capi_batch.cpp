@@ -9,7 +9,7 @@ namespace gsim_host
 int ensure_batch_buffers(gsim_db* db, Shard& s, uint32_t k)
 {
     GSIM_HIP(set_device(s.device));
-    if (s.bq_cap == 0) {
+    if (s.bq_cap == 0 || s.bseg_cap == 0) { // first use -- or a regrow of the segments failed: they start over
         const int wpc = db->knobs.batch_waves_per_cu;
         s.bgeo = gsim::scan_geometry(s.nrows, s.W, s.num_cus, wpc, 8, db->knobs.scan_ragged != 0);
         const uint64_t nchunks = (s.nrows + 63) / 64;
@@ -35,35 +35,28 @@ int ensure_batch_buffers(gsim_db* db, Shard& s, uint32_t k)
         s.bseg_max = static_cast<uint32_t>(cap);
         const uint64_t init = static_cast<uint64_t>(db->knobs.batch_seg_cap_init);
         if (cap > init) cap = init < 16 ? 16 : init;
-        s.bseg_cap = static_cast<uint32_t>(cap);
         s.bseg_waves = static_cast<uint32_t>(nw);
         const size_t slots = static_cast<size_t>(nw) * cap;
-        GSIM_HIP(hipMalloc(&s.d_bqueries, static_cast<size_t>(kBatchMaxQ) * s.W * 4));
-        GSIM_HIP(hipMalloc(&s.d_bqpop, kBatchMaxQ * 4));
-        GSIM_HIP(hipMalloc(&s.d_bstate, sizeof(gsim::BatchQueryState) * kBatchMaxQ));
-        GSIM_HIP(hipMalloc(&s.d_bcand, slots * 8));
-        GSIM_HIP(hipMalloc(&s.d_bcand_cb, slots * 4));
-        GSIM_HIP(hipMalloc(&s.d_bcand_q, slots * 4));
-        GSIM_HIP(hipMalloc(&s.d_bseg_count, nw * 4));
-        GSIM_HIP(hipMalloc(&s.d_bfin_key, static_cast<size_t>(kBatchMaxQ) * gsim::kSelectCap * 8));
-        GSIM_HIP(hipMalloc(&s.d_bfin_cb, static_cast<size_t>(kBatchMaxQ) * gsim::kSelectCap * 4));
-        GSIM_HIP(hipMalloc(&s.d_bflags, 64));
-        GSIM_HIP(hipMalloc(&s.d_brare, sizeof(gsim::BatchRare)));
-        GSIM_HIP(hipHostMalloc(&s.h_brare, sizeof(gsim::BatchRare), kHostPinned));
-        GSIM_HIP(hipHostMalloc(&s.h_bflags, 64, kHostPinned));
-        GSIM_HIP(hipHostMalloc(&s.h_bqueries, static_cast<size_t>(kBatchMaxQ) * (s.W + 1) * 4, kHostPinned));
+        GSIM_HIP(s.d_bqueries.grow(static_cast<size_t>(kBatchMaxQ) * s.W * 4));
+        GSIM_HIP(s.d_bqpop.grow(kBatchMaxQ * 4));
+        GSIM_HIP(s.d_bstate.grow(sizeof(gsim::BatchQueryState) * kBatchMaxQ));
+        GSIM_HIP(s.d_bcand.grow(slots * 8));
+        GSIM_HIP(s.d_bcand_cb.grow(slots * 4));
+        GSIM_HIP(s.d_bcand_q.grow(slots * 4));
+        GSIM_HIP(s.d_bseg_count.grow(nw * 4));
+        GSIM_HIP(s.d_bfin_key.grow(static_cast<size_t>(kBatchMaxQ) * gsim::kSelectCap * 8));
+        GSIM_HIP(s.d_bfin_cb.grow(static_cast<size_t>(kBatchMaxQ) * gsim::kSelectCap * 4));
+        GSIM_HIP(s.d_bflags.grow(64));
+        GSIM_HIP(s.d_brare.grow(sizeof(gsim::BatchRare)));
+        GSIM_HIP(s.h_brare.grow(sizeof(gsim::BatchRare)));
+        GSIM_HIP(s.h_bflags.grow(64));
+        GSIM_HIP(s.h_bqueries.grow(static_cast<size_t>(kBatchMaxQ) * (s.W + 1) * 4));
+        s.bseg_cap = static_cast<uint32_t>(cap); // (with the segments it counts, never ahead of them)
         s.bq_cap = kBatchMaxQ;
     }
     const size_t need = gsim_result_block_bytes(k) * kBatchMaxQ;
-    if (need > s.h_bresult_bytes) {
-        if (s.h_bresult) GSIM_HIP(hipHostFree(s.h_bresult));
-        if (s.d_bresult) GSIM_HIP(hipFree(s.d_bresult));
-        s.h_bresult = nullptr;
-        s.d_bresult = nullptr;
-        GSIM_HIP(hipHostMalloc(&s.h_bresult, need, kHostPinned));
-        GSIM_HIP(hipMalloc(&s.d_bresult, need));
-        s.h_bresult_bytes = need;
-    }
+    GSIM_HIP(s.h_bresult.grow(need));
+    GSIM_HIP(s.d_bresult.grow(need));
     return GSIM_OK;
 }
 
@@ -120,13 +113,13 @@ int enqueue_batch(gsim_db* db, Shard& s, const uint32_t* queries, uint32_t nq, u
     // cutoff it needs the matrix-core sample pass (large tables), which also estimates how many
     // rows the cutoff keeps: a cutoff that keeps many sets bit 3 of the flags and the kernel leaves
     // the batch to the VALU pass (the callers re-enqueue with allow_mfma = false).
-    hipEvent_t* bev = nullptr;
+    Event* bev = nullptr;
     if (db->timing && s.bev_used < kTimingRing) {
         if (s.bev.size() < static_cast<size_t>(2 * (s.bev_used + 1))) {
             for (int i = 0; i < 2; i++) {
-                hipEvent_t e;
-                GSIM_HIP(hipEventCreate(&e));
-                s.bev.push_back(e);
+                Event e;
+                GSIM_HIP(e.create());
+                s.bev.push_back(std::move(e));
             }
         }
         bev = &s.bev[2 * s.bev_used];
@@ -140,15 +133,15 @@ int enqueue_batch(gsim_db* db, Shard& s, const uint32_t* queries, uint32_t nq, u
         a.nq = nq;
         // the rows' popcounts: once per table; borrowed rows (gsim_db_attach_device_rows) may have changed since the
         // last call, so theirs are recounted every time (one more read of the table)
-        if (!s.d_rowpop) GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_rowpop), gsim::row_popcount_bytes(s.nrows)));
-        if (!s.rowpop_valid || !s.owns_rows) {
+        GSIM_HIP(s.d_rowpop.grow(gsim::row_popcount_bytes(s.nrows)));
+        if (!s.rowpop_valid || !s.rows_owned) {
             GSIM_HIP(gsim::launch_row_popcounts(s.d_rows, s.nrows, s.W, s.d_rowpop, s.stream));
             s.rowpop_valid = true;
         }
         a.rowpop = s.d_rowpop;
         GSIM_HIP(gsim::launch_batch_mfma_pass(a, s.bgeo, s.num_cus, sample, row_base, results,
-                                              gsim_result_block_bytes(k), s.stream, bev ? bev[0] : nullptr,
-                                              bev ? bev[1] : nullptr));
+                                              gsim_result_block_bytes(k), s.stream, bev ? bev[0].h : nullptr,
+                                              bev ? bev[1].h : nullptr));
         if (to_host)
             GSIM_HIP(hipMemcpyAsync(s.h_bresult, s.d_bresult, gsim_result_block_bytes(k) * nq, hipMemcpyDeviceToHost, s.stream));
         GSIM_HIP(hipMemcpyAsync(s.h_bflags, s.d_bflags, 64, hipMemcpyDeviceToHost, s.stream));
@@ -181,14 +174,13 @@ static int grow_batch_segments(Shard& s, uint32_t wanted, bool* grown)
     if (cap > s.bseg_max) cap = s.bseg_max;
     GSIM_HIP(set_device(s.device));
     GSIM_HIP(hipStreamSynchronize(s.stream));
-    GSIM_HIP(hipFree(s.d_bcand));
-    GSIM_HIP(hipFree(s.d_bcand_cb));
-    GSIM_HIP(hipFree(s.d_bcand_q));
-    s.d_bcand = nullptr, s.d_bcand_cb = nullptr, s.d_bcand_q = nullptr;
+    // (all three released before the first is allocated anew: old and new segments may not fit side by side)
+    s.d_bcand.reset(), s.d_bcand_cb.reset(), s.d_bcand_q.reset();
+    s.bseg_cap = 0; // (a failure below leaves it there: ensure_batch_buffers starts the segments over)
     const size_t slots = static_cast<size_t>(s.bseg_waves) * cap;
-    GSIM_HIP(hipMalloc(&s.d_bcand, slots * 8));
-    GSIM_HIP(hipMalloc(&s.d_bcand_cb, slots * 4));
-    GSIM_HIP(hipMalloc(&s.d_bcand_q, slots * 4));
+    GSIM_HIP(s.d_bcand.grow(slots * 8));
+    GSIM_HIP(s.d_bcand_cb.grow(slots * 4));
+    GSIM_HIP(s.d_bcand_q.grow(slots * 4));
     s.bseg_cap = static_cast<uint32_t>(cap);
     *grown = true;
     return GSIM_OK;

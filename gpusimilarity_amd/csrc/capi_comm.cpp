@@ -42,20 +42,14 @@ int ensure_gather(gsim_db* db, size_t per_shard)
     const size_t need = per_shard * db->shards.size();
     for (auto& s : db->shards) {
         GSIM_HIP(set_device(s.device));
-        if (need > s.gather_bytes) {
-            if (s.d_gather) GSIM_HIP(hipFree(s.d_gather));
-            s.d_gather = nullptr;
-            s.gather_bytes = 0;
-            GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_gather), need));
-            GSIM_HIP(hipMemset(s.d_gather, 0, need)); // (a shard without rows never writes its slots: they read as empty blocks)
-            s.gather_bytes = need;
-        }
-        if (!s.gather_ev) GSIM_HIP(hipEventCreateWithFlags(&s.gather_ev, hipEventDisableTiming));
+        bool fresh = false;
+        GSIM_HIP(s.d_gather.grow(need, &fresh));
+        if (fresh) GSIM_HIP(hipMemset(s.d_gather, 0, need)); // (a shard without rows never writes its slots: they read as empty blocks)
+        GSIM_HIP(s.gather_ev.create(hipEventDisableTiming));
     }
     Shard& s0 = db->shards[db->comm_root]; // (the shard whose device merges and answers the host)
     GSIM_HIP(set_device(s0.device));
-    for (auto& e : s0.cev)
-        if (!e) GSIM_HIP(hipEventCreate(&e));
+    for (auto& e : s0.cev) GSIM_HIP(e.create());
     return GSIM_OK;
 }
 
@@ -133,15 +127,6 @@ int fold_comm_timing(gsim_db* db)
 
 } // namespace
 
-void free_comm_buffers(Shard& s)
-{
-    if (s.d_gather) (void) hipFree(s.d_gather);
-    if (s.d_merged) (void) hipFree(s.d_merged);
-    if (s.gather_ev) (void) hipEventDestroy(s.gather_ev);
-    for (auto e : s.cev)
-        if (e) (void) hipEventDestroy(e);
-}
-
 // One query on every shard -> blocks in HBM -> all-gather -> merge_kernel -> pinned host block (search_one's twin).
 int search_one_comm(gsim_db* db, const uint32_t* query, uint32_t k, float cutoff, int metric, float alpha, float beta, gsim_hit* hits,
                     uint32_t* count, uint64_t* approx)
@@ -175,7 +160,7 @@ int search_one_comm(gsim_db* db, const uint32_t* query, uint32_t k, float cutoff
         rc = fold_comm_timing(db);
         if (rc != GSIM_OK) return rc;
     }
-    const gsim_result_header* h = reinterpret_cast<const gsim_result_header*>(s0.h_result);
+    const gsim_result_header* h = s0.h_result.as<const gsim_result_header>();
     std::memcpy(hits, h + 1, sizeof(gsim_hit) * h->count);
     *count = h->count;
     if (approx) *approx = h->approx;
@@ -198,13 +183,7 @@ int search_batch_comm(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_
         int rc = ensure_gather(db, per);
         if (rc != GSIM_OK) return rc;
         GSIM_HIP(set_device(s0.device));
-        if (per > s0.merged_bytes) {
-            if (s0.d_merged) GSIM_HIP(hipFree(s0.d_merged));
-            s0.d_merged = nullptr;
-            s0.merged_bytes = 0;
-            GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s0.d_merged), per));
-            s0.merged_bytes = per;
-        }
+        GSIM_HIP(s0.d_merged.grow(per));
         // all shards scan at once; each says whether its pass could finish every query (run_batch repeats what it can)
         std::vector<void*> outs(n);
         for (size_t i = 0; i < n; i++) outs[i] = db->shards[i].d_gather + i * per;

@@ -225,30 +225,31 @@ int gsim_debug_litmus(int device, int test, uint32_t workgroups, uint32_t iterat
     if (device < 0 || device >= ndev) return fail(GSIM_ERR_NO_DEVICE, "device index out of range");
     GSIM_HIP(set_device(device));
     const unsigned long long budget = 3000000000ull; // 30 s of the 100 MHz clock: a test that needs it has failed
-    unsigned long long* d_stats = nullptr;
-    GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&d_stats), 8 * sizeof(unsigned long long)));
+    DevBuf<unsigned long long> d_stats;
+    GSIM_HIP(d_stats.grow(8 * sizeof(unsigned long long)));
     hipError_t e = hipMemset(d_stats, 0, 8 * sizeof(unsigned long long));
-    void *d_a = nullptr, *d_b = nullptr, *h_slots = nullptr;
-    uint32_t* h_ack = nullptr;
+    DevBuf<> d_a, d_b;
+    HostBuf<> h_slots(kHostPolled);
+    HostBuf<uint32_t> h_ack(kHostPolled);
     unsigned long long host_obs = 0, host_torn = 0;
     if (e == hipSuccess && test != 2) {
         const size_t bytes = static_cast<size_t>(workgroups) * 32 * 16;
-        e = hipMalloc(&d_a, bytes);
-        if (e == hipSuccess) e = hipMalloc(&d_b, bytes);
+        e = d_a.grow(bytes);
+        if (e == hipSuccess) e = d_b.grow(bytes);
         if (e == hipSuccess) e = hipMemset(d_a, 0, bytes);
         if (e == hipSuccess) e = hipMemset(d_b, 0, bytes);
         if (e == hipSuccess) e = gsim::launch_litmus_pair(d_a, d_b, d_stats, workgroups, iterations, test == 3 ? 1 : (test == 4 ? 2 : 0), budget, nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();
     } else if (e == hipSuccess) {
-        e = hipHostMalloc(&h_slots, static_cast<size_t>(workgroups) * 16, kHostPolled);
-        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h_ack), static_cast<size_t>(workgroups) * 4, kHostPolled);
+        e = h_slots.grow(static_cast<size_t>(workgroups) * 16);
+        if (e == hipSuccess) e = h_ack.grow(static_cast<size_t>(workgroups) * 4);
         if (e == hipSuccess) {
             std::memset(h_slots, 0, static_cast<size_t>(workgroups) * 16);
             std::memset(h_ack, 0, static_cast<size_t>(workgroups) * 4);
             e = gsim::launch_litmus_host(h_slots, h_ack, d_stats, workgroups, iterations, budget, nullptr);
         }
         if (e == hipSuccess) {
-            volatile uint32_t* w = static_cast<volatile uint32_t*>(h_slots);
+            volatile uint32_t* w = h_slots.as<volatile uint32_t>();
             std::vector<uint32_t> last(workgroups, 0);
             uint32_t finished = 0;
             const auto t0 = std::chrono::steady_clock::now();
@@ -275,11 +276,6 @@ int gsim_debug_litmus(int device, int test, uint32_t workgroups, uint32_t iterat
         stats[0] = host_obs;
         stats[1] = host_torn;
     }
-    if (d_a) (void) hipFree(d_a);
-    if (d_b) (void) hipFree(d_b);
-    if (h_slots) (void) hipHostFree(h_slots);
-    if (h_ack) (void) hipHostFree(h_ack);
-    (void) hipFree(d_stats);
     if (e != hipSuccess) return fail_hip(e, "litmus");
     return GSIM_OK;
 }
@@ -293,11 +289,10 @@ int gsim_debug_score_table(int device, int metric, float alpha, float beta, uint
     if (device < 0 || device >= ndev) return fail(GSIM_ERR_NO_DEVICE, "device index out of range");
     GSIM_HIP(set_device(device));
     const size_t n = static_cast<size_t>(max_b + 1) * (max_c + 1);
-    float* d = nullptr;
-    GSIM_HIP(hipMalloc(&d, n * sizeof(float)));
+    DevBuf<float> d;
+    GSIM_HIP(d.grow(n * sizeof(float)));
     hipError_t e = gsim::launch_score_table(metric, alpha, beta, a, max_b, max_c, d, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out, d, n * sizeof(float), hipMemcpyDeviceToHost);
-    (void) hipFree(d);
     if (e != hipSuccess) return fail_hip(e, "score table");
     return GSIM_OK;
 }
@@ -310,14 +305,13 @@ int gsim_debug_sort_desc(int device, unsigned long long* keys, uint32_t n)
     gsim_device_count(&ndev);
     if (device < 0 || device >= ndev) return fail(GSIM_ERR_NO_DEVICE, "device index out of range");
     GSIM_HIP(set_device(device));
-    unsigned long long* d = nullptr;
-    GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&d), static_cast<size_t>(n) * 16));
+    DevBuf<unsigned long long> d;
+    GSIM_HIP(d.grow(static_cast<size_t>(n) * 16));
     hipError_t e = hipMemcpy(d, keys, static_cast<size_t>(n) * 8, hipMemcpyHostToDevice);
     unsigned long long* sorted = d;
     if (e == hipSuccess) e = gsim::launch_sort_desc(d, d + n, n, nullptr, &sorted);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(keys, sorted, static_cast<size_t>(n) * 8, hipMemcpyDeviceToHost);
-    (void) hipFree(d);
     if (e != hipSuccess) return fail_hip(e, "sort");
     return GSIM_OK;
 }
@@ -337,11 +331,10 @@ int gsim_debug_prefilter_constants(int device, int metric, float alpha, float be
     if (device >= ndev) return fail(GSIM_ERR_NO_DEVICE, "device index out of range");
     GSIM_HIP(set_device(device));
     const size_t n = static_cast<size_t>(max_qa + 1) * (has_cutoff ? 1 : gsim::kBBins) * 4;
-    float* d = nullptr;
-    GSIM_HIP(hipMalloc(&d, n * sizeof(float)));
+    DevBuf<float> d;
+    GSIM_HIP(d.grow(n * sizeof(float)));
     hipError_t e = gsim::launch_prefilter_table(tv, alpha, beta, max_qa, has_cutoff, cutoff, d, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out, d, n * sizeof(float), hipMemcpyDeviceToHost);
-    (void) hipFree(d);
     if (e != hipSuccess) return fail_hip(e, "prefilter table");
     return GSIM_OK;
 }

@@ -61,7 +61,7 @@ int search_folded(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_t ko
     for (auto& s : db->shards) on_device = on_device && s.d_full != nullptr;
     // the host path for one storage: its folded candidates (in s.h_result) re-scored with the host copy of the full rows
     auto rescore_on_host = [&](Shard& s, const uint32_t* query) {
-        const gsim_result_header* h = reinterpret_cast<const gsim_result_header*>(s.h_result);
+        const gsim_result_header* h = s.h_result.as<const gsim_result_header>();
         const gsim_hit* hh = reinterpret_cast<const gsim_hit*>(h + 1);
         const uint32_t n = h->count;
         idx.resize(n);
@@ -134,12 +134,10 @@ int search_folded(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_t ko
             // re-score with the full rows, sort, first k at or above the cutoff -> pinned host block
             GSIM_HIP(set_device(s.device));
             const uint32_t npad = next_pow2_u32(kshard[i] ? kshard[i] : 1);
-            if (!s.d_fq) {
-                GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_fq), static_cast<size_t>(W) * 4 + 64));
-                GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_key2), static_cast<size_t>(65536) * 16)); // (keys + the sort's second buffer)
-                GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_cb2), static_cast<size_t>(65536) * 4));
-                GSIM_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.h_fq), static_cast<size_t>(W) * 4 + 64, kHostPinned));
-            }
+            GSIM_HIP(s.d_fq.grow(static_cast<size_t>(W) * 4 + 64)); // (the four of them: made on first use)
+            GSIM_HIP(s.d_key2.grow(static_cast<size_t>(65536) * 16)); // (keys + the sort's second buffer)
+            GSIM_HIP(s.d_cb2.grow(static_cast<size_t>(65536) * 4));
+            GSIM_HIP(s.h_fq.grow(static_cast<size_t>(W) * 4 + 64));
             GSIM_HIP(hipStreamSynchronize(s.stream)); // (the pinned staging of the previous query's fingerprint is free)
             std::memcpy(s.h_fq, query, static_cast<size_t>(W) * 4);
             s.h_fq[W] = 0;
@@ -159,7 +157,7 @@ int search_folded(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_t ko
                 int rc = wait_stream(s.stream);
                 if (rc != GSIM_OK) return rc;
                 if (s.h_fq[W] == 0) { // (no NaN among the re-scored candidates: the block in s.h_result is the storage's answer)
-                    const gsim_result_header* h = reinterpret_cast<const gsim_result_header*>(s.h_result);
+                    const gsim_result_header* h = s.h_result.as<const gsim_result_header>();
                     const gsim_hit* hh = reinterpret_cast<const gsim_hit*>(h + 1);
                     ap += h->approx;
                     merged.insert(merged.end(), hh, hh + h->count);

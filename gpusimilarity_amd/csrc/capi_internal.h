@@ -22,6 +22,7 @@
 #include <utility>
 #include <vector>
 
+#include "capi_owned.h"
 #include "gsim_device.h"
 #include "gsim_synth.h"
 
@@ -39,7 +40,11 @@ int fail_hip(hipError_t e, const char* what);
         hipError_t e__ = (call);                         \
         if (e__ != hipSuccess) return fail_hip(e__, #call); \
     } while (0)
-
+// device memory whose shortage is GSIM_ERR_NOMEM, the caller's to handle
+#define GSIM_ALLOC(buf, bytes, what)                                                                 \
+    do {                                                                                             \
+        if ((buf).grow(bytes) != hipSuccess) return fail(GSIM_ERR_NOMEM, "device memory for " what); \
+    } while (0)
 
 gsim::Knobs read_knobs(); // (the one place that calls getenv for tuning knobs; gsim_db_create)
 #ifdef GSIM_TEST_HOOKS
@@ -98,41 +103,40 @@ struct Shard {
     uint64_t first_row = 0; // offset inside the handle's table
     uint64_t nrows = 0;
     uint32_t W = 0;         // words per row ON THE DEVICE (table width / fold factor)
-    void* d_rows = nullptr;
-    uint16_t* d_rowpop = nullptr; // popc(row) side array of the matrix-core batch pass (2 B per row, made on first use)
+    void* d_rows = nullptr; // what the kernels read: rows_owned, or borrowed (attached rows; a lane borrows its shard's)
+    DevBuf<> rows_owned;    // the table where the handle made it (empty for borrowed rows)
+    DevBuf<uint16_t> d_rowpop; // popc(row) side array of the matrix-core batch pass (2 B per row, made on first use)
     bool rowpop_valid = false;
-    bool owns_rows = false;
-    hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr; // the stream in use (own or caller's)
     gsim::ScanGeometry geo{};
     gsim::ScanGeometry fgeo{}; // single-launch path: fewer waves on small tables (every wave gets >= 4 chunks)
     bool state_dirty = false; // set when an enqueue failed: the device state is re-zeroed before the next one
     int sample_chunks = 4; // chunks per scan wave scored by the sample kernel (0 = off)
-    uint32_t* d_query = nullptr;
-    gsim::QueryState* d_state = nullptr;
-    unsigned long long* d_cand = nullptr;
-    uint32_t* d_cand_cb = nullptr;
-    uint32_t* d_seg_count = nullptr;
-    unsigned long long* d_final = nullptr;
-    uint32_t* d_final_cb = nullptr;
+    DevBuf<uint32_t> d_query;
+    DevBuf<gsim::QueryState> d_state;
+    DevBuf<unsigned long long> d_cand;
+    DevBuf<uint32_t> d_cand_cb;
+    DevBuf<uint32_t> d_seg_count;
+    DevBuf<unsigned long long> d_final;
+    DevBuf<uint32_t> d_final_cb;
     uint32_t final_cap = 0;
     // folded tables: the storage's FULL fingerprints in HBM too (when they fit), and the re-score's buffers
-    uint32_t* d_full = nullptr;
-    uint32_t* d_fq = nullptr;              // the full query (+ one word: the NaN flag)
-    uint32_t* h_fq = nullptr;              // ... its pinned staging
-    unsigned long long* d_key2 = nullptr;  // re-scored keys, 2 x 64 Ki (the sort's second buffer)
-    uint32_t* d_cb2 = nullptr;
-    unsigned long long* d_large = nullptr; // k > kSelectCap: the gathered top-k keys and the sort's second buffer, 2 x next_pow2(k) entries
+    DevBuf<uint32_t> d_full;
+    DevBuf<uint32_t> d_fq;               // the full query (+ one word: the NaN flag)
+    HostBuf<uint32_t> h_fq{kHostPinned}; // ... its pinned staging
+    DevBuf<unsigned long long> d_key2;   // re-scored keys, 2 x 64 Ki (the sort's second buffer)
+    DevBuf<uint32_t> d_cb2;
+    DevBuf<unsigned long long> d_large; // k > kSelectCap: the gathered top-k keys and the sort's second buffer, 2 x next_pow2(k) entries
     uint32_t large_cap = 0;
-    gsim::LargeKState* d_lk = nullptr;
-    uint32_t* d_bincur = nullptr;    // kScanBins cursors of launch_fused_binsort (zero between queries) + kScanBins words: the bins' first positions
+    DevBuf<gsim::LargeKState> d_lk;
+    DevBuf<uint32_t> d_bincur;    // kScanBins cursors of launch_fused_binsort (zero between queries) + kScanBins words: the bins' first positions
     bool classic_ready = false; // candidate / finalist scratch of the four-kernel pipeline (allocated on first use)
     uint64_t cand_slots = 0;    // gsim_db_search_rows: slots of d_cand / d_cand_cb and words of d_seg_count where one of its geometries needed
     uint32_t seg_waves = 0;     // more than geo's (0: as geo -- capi_subset.cpp grows them, never shrinks)
-    void* d_pub = nullptr;      // single-launch path: the workgroups' published-candidate regions (128 KB each)
-    void* d_hdr = nullptr;      // ... and their headers (64 B each)
-    uint32_t* d_summ = nullptr; // single-launch path: per-wave checkpoint summaries (16 KB, zero between queries)
-    uint32_t* h_done = nullptr; // single-launch path: pinned words, one per pipeline slot (since round 3 only their address is used: "the caller polls the header")
+    DevBuf<> d_pub;          // single-launch path: the workgroups' published-candidate regions (128 KB each)
+    DevBuf<> d_hdr;          // ... and their headers (64 B each)
+    DevBuf<uint32_t> d_summ; // single-launch path: per-wave checkpoint summaries (16 KB, zero between queries)
+    HostBuf<uint32_t> h_done{kHostPolled}; // single-launch path: pinned words, one per pipeline slot (since round 3 only their address is used: "the caller polls the header")
     uint32_t epoch = 0;
     uint32_t pub_tag = 0;           // the last single launch's FusedArgs::pub_tag
     // One synchronous query in flight on this shard (gsim_db_search: slot 0; gsim_db_search_each: up to kPipe, slot = query mod kPipe):
@@ -141,33 +145,30 @@ struct Shard {
         bool inflight = false;  // enqueued by a synchronous caller and not finished yet (whatever route it took)
         Route route = Route::kClassic; // how it was enqueued (valid until the next enqueue): kRanked announces itself in the header ...
         uint32_t epoch = 0;     // ... with this epoch; the publishing routes say "handed back" with header flag 2
-        hipEvent_t ev = nullptr; // recorded behind the last kernel of an enqueue that is not the single launch's own: the caller waits
+        Event ev;               // recorded behind the last kernel of an enqueue that is not the single launch's own: the caller waits
         bool ev_set = false;    // for THIS query, not for the queries enqueued behind it on the stream
         bool rerun = false;     // it ran behind a launch that left the per-query state dirty: not to be trusted, run again
         uint8_t why = 0;        // kQ* bits: how it was routed and why it was run again (gsim_debug_query_flags)
     } slot[kPipe];
-    char* h_pipe = nullptr;          // kPipe pinned result blocks (gsim_db_search_each)
-    size_t h_pipe_block = 0;
+    HostBuf<char> h_pipe{kHostPolled}; // kPipe pinned result blocks (gsim_db_search_each)
     // the synchronous routes' back-offs (plan_query takes them, finish_query_sync feeds them): queries skipped after a hand-back
     Backoff ranked_backoff{1, 1, 2};   // the single launch (scores that tie heavily): 4, 8, ... 64, from two hand-backs in a row
     Backoff publish_backoff{1, 1, 0};  // the publishing launch: 2, 4, ... 64
     Backoff binrank_backoff{16, 0, 0}; // the bin-ranked emission (ties in the top bins): 16, 32, ... 1024, by the radix tail instead
-    unsigned long long* d_dbg = nullptr; // GSIM_FUSED_DEBUG: per-workgroup phase timestamps
-    void* d_result = nullptr;
-    size_t result_bytes = 0;
+    DevBuf<unsigned long long> d_dbg; // GSIM_FUSED_DEBUG: per-workgroup phase timestamps
+    DevBuf<> d_result;
     // pinned host staging; queries go through a ring so that back-to-back
     // asynchronous searches never overwrite a query whose upload is still queued
-    uint32_t* h_query = nullptr; // kQueryRing slots of W words
-    std::vector<hipEvent_t> q_ev; // scan-done event per slot (asynchronous searches)
+    HostBuf<uint32_t> h_query{kHostPinned}; // kQueryRing slots of W words
+    std::vector<Event> q_ev; // scan-done event per slot (asynchronous searches)
     bool q_pending[kQueryRing] = {};
     uint32_t q_next = 0;
-    unsigned char* h_result = nullptr;
-    size_t h_result_bytes = 0;
-    gsim::QueryState* h_state = nullptr; // staging for the running totals
+    HostBuf<unsigned char> h_result{kHostPolled};
+    HostBuf<gsim::QueryState> h_state{kHostPinned}; // staging for the running totals
     // timing
-    std::vector<hipEvent_t> ev; // 3 per slot
+    std::vector<Event> ev; // 3 per slot
     uint32_t ev_used = 0;
-    std::vector<hipEvent_t> bev; // multi-query passes: 2 per slot
+    std::vector<Event> bev; // multi-query passes: 2 per slot
     uint32_t bev_used = 0;
     unsigned long long base_ncand = 0, base_nfinal = 0, base_nredo = 0; // device totals when timing was enabled
     // multi-query batches (allocated on first use)
@@ -175,35 +176,33 @@ struct Shard {
     uint32_t bq_cap = 0;          // queries the batch buffers hold
     uint32_t bseg_cap = 0;        // candidate slots per wave segment, now / at most (grown on overflow) / number of segments
     uint32_t bseg_max = 0, bseg_waves = 0;
-    uint32_t* d_bqueries = nullptr;
-    uint32_t* d_bqpop = nullptr;
-    gsim::BatchQueryState* d_bstate = nullptr;
-    unsigned long long* d_bcand = nullptr;
-    uint32_t* d_bcand_cb = nullptr;
-    uint32_t* d_bcand_q = nullptr;
-    uint32_t* d_bseg_count = nullptr;
-    unsigned long long* d_bfin_key = nullptr;
-    uint32_t* d_bfin_cb = nullptr;
-    uint32_t* d_bflags = nullptr; // [0] overflow flags, [1] ticket
-    gsim::BatchRare* d_brare = nullptr;
-    gsim::BatchRare* h_brare = nullptr; // pinned
-    uint32_t* h_bflags = nullptr;
-    uint32_t* h_bqueries = nullptr; // pinned staging: queries + popcounts
-    unsigned char* h_bresult = nullptr;
-    unsigned char* d_bresult = nullptr; // the select kernel writes here; one bulk copy to h_bresult
-    size_t h_bresult_bytes = 0;
+    DevBuf<uint32_t> d_bqueries;
+    DevBuf<uint32_t> d_bqpop;
+    DevBuf<gsim::BatchQueryState> d_bstate;
+    DevBuf<unsigned long long> d_bcand;
+    DevBuf<uint32_t> d_bcand_cb;
+    DevBuf<uint32_t> d_bcand_q;
+    DevBuf<uint32_t> d_bseg_count;
+    DevBuf<unsigned long long> d_bfin_key;
+    DevBuf<uint32_t> d_bfin_cb;
+    DevBuf<uint32_t> d_bflags; // [0] overflow flags, [1] ticket
+    DevBuf<gsim::BatchRare> d_brare;
+    HostBuf<gsim::BatchRare> h_brare{kHostPinned}; // pinned
+    HostBuf<uint32_t> h_bflags{kHostPinned};
+    HostBuf<uint32_t> h_bqueries{kHostPinned}; // pinned staging: queries + popcounts
+    HostBuf<unsigned char> h_bresult{kHostPinned};
+    DevBuf<unsigned char> d_bresult; // the select kernel writes here; one bulk copy to h_bresult
     // in-process collective route (gsim_db_set_comm, capi_comm.cpp): every shard's gather buffer holds one slot per
     // shard (an in-place all-gather: the shard's own kernels write slot `index of the shard`)
-    unsigned char* d_gather = nullptr;
-    size_t gather_bytes = 0;
-    unsigned char* d_merged = nullptr; // first shard only: the merged blocks of a batch (single queries merge straight into h_result)
-    size_t merged_bytes = 0;
-    hipEvent_t gather_ev = nullptr;    // loop-back comm (aliased devices): "this shard's block is in its slot"
-    hipEvent_t cev[3] = {};            // first shard, timing: scan done / gather done / merge done
+    DevBuf<unsigned char> d_gather;
+    DevBuf<unsigned char> d_merged; // first shard only: the merged blocks of a batch (single queries merge straight into h_result)
+    Event gather_ev;                // loop-back comm (aliased devices): "this shard's block is in its slot"
+    Event cev[3];                   // first shard, timing: scan done / gather done / merge done
     // gsim_db_neighbors: the pair buffer (sort keys + scores), grown to what a call needed and kept for the next one
-    unsigned long long* d_nbr_keys = nullptr;
-    float* d_nbr_vals = nullptr;
+    DevBuf<unsigned long long> d_nbr_keys;
+    DevBuf<float> d_nbr_vals;
     uint64_t nbr_cap = 0;
+    Stream own_stream; // (last: free_shard's `s = Shard{}` releases in this order, the stream behind everything enqueued on it)
 };
 
 } // namespace gsim_host
@@ -225,8 +224,8 @@ struct gsim_rowset {
     uint64_t nrows = 0;       // rows of the owner's table when the set was made
     uint64_t count = 0;       // selected rows
     uint32_t row_base = 0;    // ... and its row base then (what gsim_rowset_rows adds)
-    uint32_t* d_bits = nullptr; // rowset_words(nrows) + kRowsetPadWords words
-    uint32_t* d_list = nullptr; // count rows, ascending, without the row base
+    gsim_host::DevBuf<uint32_t> d_bits; // rowset_words(nrows) + kRowsetPadWords words
+    gsim_host::DevBuf<uint32_t> d_list; // count rows, ascending, without the row base
 };
 
 struct gsim_db {
@@ -306,6 +305,9 @@ int search_one(gsim_db* db, const uint32_t* query, uint32_t k, float cutoff, int
                uint32_t* count, uint64_t* approx);
 int check_search_args(gsim_db* db, const uint32_t* queries, int metric);
 int ensure_classic_scratch(Shard& s);
+int rezero_dirty_state(Shard& s);
+gsim::ScanArgs scan_args(const Shard& s, const uint32_t* query_words, const uint32_t* query, uint32_t* query_dev, uint32_t k, float cutoff, int metric,
+                         float alpha, float beta);
 int enqueue_scan_tail(gsim_db* db, Shard& s, const gsim::ScanArgs& a, const gsim::ScanGeometry& g, uint32_t row_base, uint64_t approx_if_no_cutoff,
                       void* out);
 // capi_batch.cpp: multi-query passes
@@ -328,7 +330,6 @@ int search_one_comm(gsim_db* db, const uint32_t* query, uint32_t k, float cutoff
                     uint32_t* count, uint64_t* approx);
 int search_batch_comm(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_t k, uint32_t kout, float cutoff, int metric, float alpha,
                       float beta, gsim_hit* hits, uint32_t* counts, uint64_t* approx);
-void free_comm_buffers(Shard& s);
 // capi_batch.cpp: nb <= kBatchMaxQ queries on one shard, result blocks in device memory at `out` (the per-shard half of
 // gsim_db_search_batch_device)
 int batch_to_device(gsim_db* db, Shard& s, const uint32_t* qb, uint32_t nb, uint32_t k, float cutoff, int metric, float alpha,

@@ -58,8 +58,8 @@ int join(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, float cutof
             pieces.push_back(p);
         }
         const size_t nlaunch = static_cast<size_t>(nl) * pieces.size();
-        DevBuf ctl; // [0] the cursor, [1 + l] the cursor after launch l
-        GSIM_HIP(ctl.alloc((1 + nlaunch) * 8));
+        DevBuf<> ctl; // [0] the cursor, [1 + l] the cursor after launch l
+        GSIM_HIP(ctl.grow((1 + nlaunch) * 8));
         gsim::JoinArgs j{};
         j.rows = s.d_rows;
         j.W = s.W;
@@ -88,20 +88,20 @@ int join(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, float cutof
     } else {
         // popc of every row of either side, and the rows zero-padded to WP words unless they already are WP words
         const uint32_t WP = gsim::nbr_padded_words(s.W);
-        DevBuf pop, pad, lpop, lpad;
-        GSIM_HIP(pop.alloc(N * 4));
-        GSIM_HIP(lpop.alloc(nl * 4));
+        DevBuf<> pop, pad, lpop, lpad;
+        GSIM_HIP(pop.grow(N * 4));
+        GSIM_HIP(lpop.grow(nl * 4));
         if (WP != s.W) {
-            GSIM_HIP(pad.alloc(N * WP * 4));
-            GSIM_HIP(lpad.alloc(nl * WP * 4));
+            GSIM_HIP(pad.grow(N * WP * 4));
+            GSIM_HIP(lpad.grow(nl * WP * 4));
         }
         GSIM_HIP(gsim::launch_nbr_prepare(s.d_rows, N, s.W, WP, pad.as<uint32_t>(), pop.as<uint32_t>(), st));
         GSIM_HIP(gsim::launch_nbr_prepare(d_left, nl, s.W, WP, lpad.as<uint32_t>(), lpop.as<uint32_t>(), st));
         const uint64_t nlt = (nl + gsim::kNbrTile - 1) / gsim::kNbrTile;
         const uint64_t nct = (N + gsim::kNbrTile - 1) / gsim::kNbrTile;
         const std::vector<NbrLaunch> plan = plan_launches(nlt, nct, false, WP);
-        DevBuf ctl; // [0] the cursor, [1 + l] the cursor after launch l, then 4 clock stamps per launch
-        GSIM_HIP(ctl.alloc((1 + 5 * plan.size()) * 8));
+        DevBuf<> ctl; // [0] the cursor, [1 + l] the cursor after launch l, then 4 clock stamps per launch
+        GSIM_HIP(ctl.grow((1 + 5 * plan.size()) * 8));
         unsigned long long* d_clk = ctl.as<unsigned long long>() + 1 + plan.size();
         gsim::JoinTileArgs a{};
         a.rows = WP != s.W ? pad.as<uint32_t>() : static_cast<const uint32_t*>(s.d_rows);
@@ -213,15 +213,12 @@ int gsim_db_join_queries(gsim_db* db, const uint32_t* queries, uint64_t nq, floa
     if (rc != GSIM_OK) return rc;
     std::lock_guard<std::mutex> guard(db->search_mutex);
     Shard& s = db->shards[0];
-    DevBuf d_left;
+    DevBuf<> d_left;
     if (nq) {
         GSIM_HIP(set_device(s.device));
         const size_t bytes = static_cast<size_t>(nq) * s.W * 4;
-        if (d_left.alloc(bytes) != hipSuccess) {
-            (void) hipGetLastError();
-            return fail(GSIM_ERR_NOMEM, "device memory for the join's left rows");
-        }
-        GSIM_HIP(hipMemcpyAsync(d_left.p, queries, bytes, hipMemcpyHostToDevice, s.stream));
+        GSIM_ALLOC(d_left, bytes, "the join's left rows");
+        GSIM_HIP(hipMemcpyAsync(d_left, queries, bytes, hipMemcpyHostToDevice, s.stream));
     }
     return run_join(db, d_left.as<uint32_t>(), nq, cutoff, metric, alpha, beta, order, out);
 }

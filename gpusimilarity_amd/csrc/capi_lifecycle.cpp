@@ -106,59 +106,7 @@ int free_shard(Shard& s)
     for (auto& l : s.lanes) (void) free_shard(l); // (they share s.d_rows and do not own it)
     s.lanes.clear();
     (void) set_device(s.device);
-    if (s.stream) (void) hipStreamSynchronize(s.stream);
-    if (s.owns_rows && s.d_rows) (void) hipFree(s.d_rows);
-    if (s.d_rowpop) (void) hipFree(s.d_rowpop);
-    if (s.d_query) (void) hipFree(s.d_query);
-    if (s.d_state) (void) hipFree(s.d_state);
-    if (s.d_cand) (void) hipFree(s.d_cand);
-    if (s.d_cand_cb) (void) hipFree(s.d_cand_cb);
-    if (s.d_final_cb) (void) hipFree(s.d_final_cb);
-    if (s.d_seg_count) (void) hipFree(s.d_seg_count);
-    if (s.d_final) (void) hipFree(s.d_final);
-    if (s.d_result) (void) hipFree(s.d_result);
-    if (s.d_full) (void) hipFree(s.d_full);
-    if (s.d_fq) (void) hipFree(s.d_fq);
-    if (s.h_fq) (void) hipHostFree(s.h_fq);
-    if (s.d_key2) (void) hipFree(s.d_key2);
-    if (s.d_cb2) (void) hipFree(s.d_cb2);
-    if (s.d_large) (void) hipFree(s.d_large);
-    if (s.d_lk) (void) hipFree(s.d_lk);
-    if (s.d_bincur) (void) hipFree(s.d_bincur);
-    if (s.d_nbr_keys) (void) hipFree(s.d_nbr_keys);
-    if (s.d_nbr_vals) (void) hipFree(s.d_nbr_vals);
-    for (auto& sl : s.slot)
-        if (sl.ev) (void) hipEventDestroy(sl.ev);
-    if (s.d_pub) (void) hipFree(s.d_pub);
-    if (s.d_hdr) (void) hipFree(s.d_hdr);
-    if (s.d_summ) (void) hipFree(s.d_summ);
-    if (s.d_dbg) (void) hipFree(s.d_dbg);
-    if (s.h_done) (void) hipHostFree(s.h_done);
-    if (s.h_pipe) (void) hipHostFree(s.h_pipe);
-    if (s.h_query) (void) hipHostFree(s.h_query);
-    if (s.h_result) (void) hipHostFree(s.h_result);
-    if (s.h_state) (void) hipHostFree(s.h_state);
-    if (s.d_bqueries) (void) hipFree(s.d_bqueries);
-    if (s.d_bqpop) (void) hipFree(s.d_bqpop);
-    if (s.d_bstate) (void) hipFree(s.d_bstate);
-    if (s.d_bcand) (void) hipFree(s.d_bcand);
-    if (s.d_bcand_cb) (void) hipFree(s.d_bcand_cb);
-    if (s.d_bcand_q) (void) hipFree(s.d_bcand_q);
-    if (s.d_bseg_count) (void) hipFree(s.d_bseg_count);
-    if (s.d_bfin_key) (void) hipFree(s.d_bfin_key);
-    if (s.d_bfin_cb) (void) hipFree(s.d_bfin_cb);
-    if (s.d_bflags) (void) hipFree(s.d_bflags);
-    if (s.d_brare) (void) hipFree(s.d_brare);
-    if (s.h_brare) (void) hipHostFree(s.h_brare);
-    if (s.h_bflags) (void) hipHostFree(s.h_bflags);
-    if (s.h_bqueries) (void) hipHostFree(s.h_bqueries);
-    if (s.h_bresult) (void) hipHostFree(s.h_bresult);
-    if (s.d_bresult) (void) hipFree(s.d_bresult);
-    free_comm_buffers(s);
-    for (auto e : s.ev) (void) hipEventDestroy(e);
-    for (auto e : s.bev) (void) hipEventDestroy(e);
-    for (auto e : s.q_ev) (void) hipEventDestroy(e);
-    if (s.own_stream) (void) hipStreamDestroy(s.own_stream);
+    if (s.stream) (void) hipStreamSynchronize(s.stream); // (nothing is released before the stream has drained)
     s = Shard{};
     return 0;
 }
@@ -173,7 +121,7 @@ int setup_shard(gsim_db* db, Shard& s)
     GSIM_HIP(hipGetDeviceProperties(&prop, phys_device(s.device)));
     s.num_cus = (prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256) / (s.cu_share > 0 ? s.cu_share : 1);
     if (s.num_cus < 1) s.num_cus = 1;
-    GSIM_HIP(hipStreamCreateWithFlags(&s.own_stream, hipStreamNonBlocking));
+    GSIM_HIP(s.own_stream.create(hipStreamNonBlocking));
     s.stream = s.own_stream;
     const gsim::Knobs& kn = db->knobs;
     if (s.W == 0) s.W = db->W;
@@ -188,16 +136,16 @@ int setup_shard(gsim_db* db, Shard& s)
         uint64_t nw = s.fgeo.nchunks / per / 4 * 4;
         s.fgeo.nwaves = static_cast<uint32_t>(nw < 4 ? 4 : nw);
     }
-    GSIM_HIP(hipMalloc(&s.d_query, static_cast<size_t>(s.W) * 4));
-    GSIM_HIP(hipMalloc(&s.d_state, sizeof(gsim::QueryState)));
+    GSIM_HIP(s.d_query.grow(static_cast<size_t>(s.W) * 4));
+    GSIM_HIP(s.d_state.grow(sizeof(gsim::QueryState)));
     GSIM_HIP(hipMemset(s.d_state, 0, sizeof(gsim::QueryState))); // the kernels keep it zero between queries
     // every workgroup of the single launch is a selector and there are at most kFusedSelectors: on a part with more CUs
     // (or with GSIM_SCAN_WAVES_PER_CU > 4) the grid is clamped -- its waves take more chunks each -- instead of losing the path
     const uint32_t fused_max_waves = static_cast<uint32_t>(gsim::kFusedSelectors) * (gsim::kScanBlock / 64);
     if (s.fgeo.nwaves > fused_max_waves) s.fgeo.nwaves = fused_max_waves;
     if (gsim::fused_supported(s.fgeo)) {
-        GSIM_HIP(hipMalloc(&s.d_pub, gsim::fused_pub_bytes(s.fgeo.nwaves / 4)));
-        GSIM_HIP(hipMalloc(&s.d_hdr, gsim::fused_hdr_bytes(s.fgeo.nwaves / 4)));
+        GSIM_HIP(s.d_pub.grow(gsim::fused_pub_bytes(s.fgeo.nwaves / 4)));
+        GSIM_HIP(s.d_hdr.grow(gsim::fused_hdr_bytes(s.fgeo.nwaves / 4)));
         // (no launch carries tag 0: a selector never takes what the regions held before their first query for a published list)
         GSIM_HIP(hipMemset(s.d_pub, 0, gsim::fused_pub_bytes(s.fgeo.nwaves / 4)));
         GSIM_HIP(hipMemset(s.d_hdr, 0, gsim::fused_hdr_bytes(s.fgeo.nwaves / 4)));
@@ -207,17 +155,14 @@ int setup_shard(gsim_db* db, Shard& s)
             std::fprintf(stderr, "gpusimilarity_amd: the single-launch path is off for this table's scan geometry (%u waves, unroll %u): "
                                  "queries run on the four-kernel pipeline\n", s.fgeo.nwaves, s.fgeo.unroll);
     }
-    GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_summ), kSummBytes));
+    GSIM_HIP(s.d_summ.grow(kSummBytes));
     GSIM_HIP(hipMemset(s.d_summ, 0, kSummBytes));
-    GSIM_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.h_done), 64, kHostPolled));
+    GSIM_HIP(s.h_done.grow(64));
     std::memset(s.h_done, 0, 64);
-    GSIM_HIP(hipHostMalloc(&s.h_query, static_cast<size_t>(s.W) * 4 * kQueryRing, kHostPinned));
-    for (int i = 0; i < kQueryRing; i++) {
-        hipEvent_t e;
-        GSIM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        s.q_ev.push_back(e);
-    }
-    GSIM_HIP(hipHostMalloc(&s.h_state, sizeof(gsim::QueryState), kHostPinned));
+    GSIM_HIP(s.h_query.grow(static_cast<size_t>(s.W) * 4 * kQueryRing));
+    s.q_ev.resize(kQueryRing);
+    for (auto& e : s.q_ev) GSIM_HIP(e.create(hipEventDisableTiming));
+    GSIM_HIP(s.h_state.grow(sizeof(gsim::QueryState)));
     return GSIM_OK;
 }
 
@@ -252,13 +197,12 @@ int upload_rows(void* d_dst, const void* h_src, size_t bytes, hipStream_t stream
         GSIM_HIP(hipMemcpy(d_dst, h_src, bytes, hipMemcpyHostToDevice));
         return GSIM_OK;
     }
-    void* stage[2] = {nullptr, nullptr};
-    hipEvent_t done[2] = {nullptr, nullptr};
-    int rc = GSIM_OK;
+    HostBuf<> stage[2] = {HostBuf<>(kHostPinned), HostBuf<>(kHostPinned)};
+    Event done[2];
     hipError_t e = hipSuccess;
     for (int i = 0; i < 2 && e == hipSuccess; i++) {
-        e = hipHostMalloc(&stage[i], kChunk, kHostPinned);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&done[i], hipEventDisableTiming);
+        e = stage[i].grow(kChunk);
+        if (e == hipSuccess) e = done[i].create(hipEventDisableTiming);
     }
     size_t off = 0;
     for (int i = 0; e == hipSuccess && off < bytes; i ^= 1) {
@@ -271,12 +215,7 @@ int upload_rows(void* d_dst, const void* h_src, size_t bytes, hipStream_t stream
         off += n;
     }
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) rc = fail_hip(e, "upload_rows");
-    for (int i = 0; i < 2; i++) {
-        if (done[i]) (void) hipEventDestroy(done[i]);
-        if (stage[i]) (void) hipHostFree(stage[i]);
-    }
-    return rc;
+    return e == hipSuccess ? GSIM_OK : fail_hip(e, "upload_rows");
 }
 
 
@@ -459,8 +398,8 @@ int gsim_db_finalize(gsim_db* db, int device, int ndevices)
             folded.resize(static_cast<size_t>(s.nrows) * Wf);
             fold_rows_mt(db->host_rows.data() + s.first_row * db->W, s.nrows, db->W, db->fold, folded.data());
             GSIM_HIP(set_device(s.device));
-            GSIM_HIP(hipMalloc(&s.d_rows, bytes ? bytes : 16));
-            s.owns_rows = true;
+            GSIM_HIP(s.rows_owned.grow(bytes));
+            s.d_rows = s.rows_owned;
             if (bytes) GSIM_HIP(hipMemcpy(s.d_rows, folded.data(), bytes, hipMemcpyHostToDevice));
             int rc = setup_shard(db, s);
             if (rc != GSIM_OK) return rc;
@@ -489,9 +428,7 @@ int gsim_db_finalize(gsim_db* db, int device, int ndevices)
             const size_t full_bytes = static_cast<size_t>(s.nrows) * db->W * 4;
             if (!full_bytes) continue;
             GSIM_HIP(set_device(s.device));
-            if (hipMalloc(reinterpret_cast<void**>(&s.d_full), full_bytes) != hipSuccess) {
-                (void) hipGetLastError();
-                s.d_full = nullptr;
+            if (s.d_full.grow(full_bytes) != hipSuccess) {
                 keep_full = false;
                 break;
             }
@@ -502,8 +439,7 @@ int gsim_db_finalize(gsim_db* db, int device, int ndevices)
             for (auto& s : db->shards) {
                 if (!s.d_full) continue;
                 (void) set_device(s.device);
-                (void) hipFree(s.d_full);
-                s.d_full = nullptr;
+                s.d_full.reset();
             }
         }
         db->finalized = true;
@@ -526,8 +462,8 @@ int gsim_db_finalize(gsim_db* db, int device, int ndevices)
         s.nrows = std::min<uint64_t>(per, db->nrows - s.first_row);
         GSIM_HIP(set_device(s.device));
         const size_t bytes = static_cast<size_t>(s.nrows) * row_bytes;
-        GSIM_HIP(hipMalloc(&s.d_rows, bytes ? bytes : 16));
-        s.owns_rows = true;
+        GSIM_HIP(s.rows_owned.grow(bytes));
+        s.d_rows = s.rows_owned;
         if (bytes) {
             const int urc = upload_rows(s.d_rows, db->host_rows.data() + s.first_row * db->W, bytes, nullptr);
             if (urc != GSIM_OK) return urc;
@@ -559,8 +495,8 @@ int gsim_db_generate(gsim_db* db, uint64_t seed, int kind, uint64_t first_row, u
     s.nrows = nrows;
     GSIM_HIP(set_device(device));
     const size_t bytes = static_cast<size_t>(nrows) * db->W * 4;
-    GSIM_HIP(hipMalloc(&s.d_rows, bytes ? bytes : 16));
-    s.owns_rows = true;
+    GSIM_HIP(s.rows_owned.grow(bytes));
+    s.d_rows = s.rows_owned;
     int rc = setup_shard(db, s);
     if (rc != GSIM_OK) return rc;
     GSIM_HIP(gsim::launch_generate(s.d_rows, seed, kind, first_row, nrows, db->W, s.stream));
@@ -593,8 +529,8 @@ int gsim_db_generate_sharded(gsim_db* db, uint64_t seed, int kind, uint64_t firs
         s.nrows = std::min<uint64_t>(per, nrows - s.first_row);
         GSIM_HIP(set_device(s.device));
         const size_t bytes = static_cast<size_t>(s.nrows) * db->W * 4;
-        GSIM_HIP(hipMalloc(&s.d_rows, bytes ? bytes : 16));
-        s.owns_rows = true;
+        GSIM_HIP(s.rows_owned.grow(bytes));
+        s.d_rows = s.rows_owned;
         int rc = setup_shard(db, s);
         if (rc != GSIM_OK) return rc;
         if (s.nrows) GSIM_HIP(gsim::launch_generate(s.d_rows, seed, kind, first_row + s.first_row, s.nrows, db->W, s.stream));
@@ -636,8 +572,7 @@ int gsim_db_attach_device_rows(gsim_db* db, const void* d_rows, uint64_t nrows, 
     Shard& s = db->shards[0];
     s.device = device;
     s.nrows = nrows;
-    s.d_rows = const_cast<void*>(d_rows);
-    s.owns_rows = false;
+    s.d_rows = const_cast<void*>(d_rows); // (borrowed)
     int rc = setup_shard(db, s);
     if (rc != GSIM_OK) return rc;
     db->finalized = true;

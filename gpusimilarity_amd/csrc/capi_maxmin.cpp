@@ -21,43 +21,6 @@ constexpr uint32_t kMaxMinBatch = 64;
 namespace
 {
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf()
-    {
-        if (p) (void) hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-struct HostBuf {
-    uint32_t* p = nullptr;
-    ~HostBuf()
-    {
-        if (p) (void) hipHostFree(p);
-    }
-};
-
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair()
-    {
-        if (a) (void) hipEventDestroy(a);
-        if (b) (void) hipEventDestroy(b);
-    }
-    hipError_t create()
-    {
-        hipError_t e = hipEventCreate(&a);
-        return e == hipSuccess ? hipEventCreate(&b) : e;
-    }
-    double ms() const
-    {
-        float t = 0.0f;
-        return hipEventElapsedTime(&t, a, b) == hipSuccess ? static_cast<double>(t) : 0.0;
-    }
-};
-
 // Rows per launch of a pass: a multiple of 64 (launch starts stay 16-byte aligned for every width)
 uint64_t launch_rows(uint32_t W)
 {
@@ -97,15 +60,15 @@ int maxmin(gsim_db* db, Shard& s, uint32_t npicks, const uint32_t* seeds, uint32
         plan.push_back(l);
     }
 
-    DevBuf d_maxsim, d_nearest, d_picks, d_scores, d_ctl, d_part;
-    GSIM_HIP(d_maxsim.alloc(N * 4));
-    if (nearest) GSIM_HIP(d_nearest.alloc(N * 4));
-    GSIM_HIP(d_picks.alloc(static_cast<size_t>(npicks) * 4));
-    GSIM_HIP(d_scores.alloc(static_cast<size_t>(npicks) * 4));
-    GSIM_HIP(d_ctl.alloc(gsim::kMaxMinCtlWords * 4));
-    GSIM_HIP(d_part.alloc(static_cast<size_t>(nwg) * 8));
-    HostBuf h_done; // the done word after every batch, two slots
-    GSIM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_done.p), 64, hipHostMallocDefault));
+    DevBuf<> d_maxsim, d_nearest, d_picks, d_scores, d_ctl, d_part;
+    GSIM_HIP(d_maxsim.grow(N * 4));
+    if (nearest) GSIM_HIP(d_nearest.grow(N * 4));
+    GSIM_HIP(d_picks.grow(static_cast<size_t>(npicks) * 4));
+    GSIM_HIP(d_scores.grow(static_cast<size_t>(npicks) * 4));
+    GSIM_HIP(d_ctl.grow(gsim::kMaxMinCtlWords * 4));
+    GSIM_HIP(d_part.grow(static_cast<size_t>(nwg) * 8));
+    HostBuf<uint32_t> h_done(hipHostMallocDefault); // the done word after every batch, two slots
+    GSIM_HIP(h_done.grow(64));
 
     // initial state: maxsim = -1 everywhere, pick 0 (the first seed, or row 0) marked picked, its score 0
     std::vector<uint32_t> first(std::max<uint32_t>(nseeds, 1));
@@ -117,11 +80,11 @@ int maxmin(gsim_db* db, Shard& s, uint32_t npicks, const uint32_t* seeds, uint32
     std::memcpy(&picked_bits, &picked, 4);
     std::vector<uint32_t> ctl(gsim::kMaxMinCtlWords, 0u);
     ctl[gsim::kMaxMinPicked] = 1;
-    GSIM_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_maxsim.p), static_cast<int>(minus_one_bits), N, stream));
+    GSIM_HIP(hipMemsetD32Async(static_cast<hipDeviceptr_t>(d_maxsim), static_cast<int>(minus_one_bits), N, stream));
     GSIM_HIP(hipMemcpyAsync(d_maxsim.as<uint32_t>() + first[0], &picked_bits, 4, hipMemcpyHostToDevice, stream));
-    GSIM_HIP(hipMemcpyAsync(d_picks.p, first.data(), first.size() * 4, hipMemcpyHostToDevice, stream));
-    GSIM_HIP(hipMemcpyAsync(d_scores.p, &zero, 4, hipMemcpyHostToDevice, stream));
-    GSIM_HIP(hipMemcpyAsync(d_ctl.p, ctl.data(), ctl.size() * 4, hipMemcpyHostToDevice, stream));
+    GSIM_HIP(hipMemcpyAsync(d_picks, first.data(), first.size() * 4, hipMemcpyHostToDevice, stream));
+    GSIM_HIP(hipMemcpyAsync(d_scores, &zero, 4, hipMemcpyHostToDevice, stream));
+    GSIM_HIP(hipMemcpyAsync(d_ctl, ctl.data(), ctl.size() * 4, hipMemcpyHostToDevice, stream));
 
     gsim::MaxMinArgs m{};
     m.rows = s.d_rows;
@@ -146,17 +109,8 @@ int maxmin(gsim_db* db, Shard& s, uint32_t npicks, const uint32_t* seeds, uint32
     EventPair ev_k, ev_d2h;
     GSIM_HIP(ev_k.create());
     GSIM_HIP(ev_d2h.create());
-    hipEvent_t ev_batch[2] = {nullptr, nullptr};
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard()
-        {
-            for (int i = 0; i < 2; i++)
-                if (e[i]) (void) hipEventDestroy(e[i]);
-        }
-    } ev_guard{ev_batch};
-    GSIM_HIP(hipEventCreateWithFlags(&ev_batch[0], hipEventDisableTiming));
-    GSIM_HIP(hipEventCreateWithFlags(&ev_batch[1], hipEventDisableTiming));
+    Event ev_batch[2];
+    for (auto& e : ev_batch) GSIM_HIP(e.create(hipEventDisableTiming));
     const bool cached = N * (static_cast<uint64_t>(s.W) * 4u + (nearest ? 8u : 4u)) <= kMaxMinCachedBytes;
     const auto launch = cached ? gsim::launch_maxmin_pass_cached : gsim::launch_maxmin_pass;
     uint64_t launches = 0;
@@ -169,21 +123,21 @@ int maxmin(gsim_db* db, Shard& s, uint32_t npicks, const uint32_t* seeds, uint32
                 GSIM_HIP(launch(m, l.g, l.r0, l.nrows, l.wg0, p, stream));
                 launches++;
             }
-        GSIM_HIP(hipMemcpyAsync(h_done.p + (b & 1), d_ctl.p, 4, hipMemcpyDeviceToHost, stream));
+        GSIM_HIP(hipMemcpyAsync(h_done + (b & 1), d_ctl, 4, hipMemcpyDeviceToHost, stream));
         GSIM_HIP(hipEventRecord(ev_batch[b & 1], stream));
         if (b > 0) {
             GSIM_HIP(hipEventSynchronize(ev_batch[(b - 1) & 1]));
-            if (h_done.p[(b - 1) & 1]) break;
+            if (h_done[(b - 1) & 1]) break;
         }
     }
     GSIM_HIP(hipEventRecord(ev_k.b, stream));
 
     GSIM_HIP(hipEventRecord(ev_d2h.a, stream));
-    GSIM_HIP(hipMemcpyAsync(ctl.data(), d_ctl.p, ctl.size() * 4, hipMemcpyDeviceToHost, stream));
-    GSIM_HIP(hipMemcpyAsync(picks, d_picks.p, static_cast<size_t>(npicks) * 4, hipMemcpyDeviceToHost, stream));
-    if (pick_scores) GSIM_HIP(hipMemcpyAsync(pick_scores, d_scores.p, static_cast<size_t>(npicks) * 4, hipMemcpyDeviceToHost, stream));
-    if (row_score) GSIM_HIP(hipMemcpyAsync(row_score, d_maxsim.p, N * 4, hipMemcpyDeviceToHost, stream));
-    if (nearest) GSIM_HIP(hipMemcpyAsync(nearest, d_nearest.p, N * 4, hipMemcpyDeviceToHost, stream));
+    GSIM_HIP(hipMemcpyAsync(ctl.data(), d_ctl, ctl.size() * 4, hipMemcpyDeviceToHost, stream));
+    GSIM_HIP(hipMemcpyAsync(picks, d_picks, static_cast<size_t>(npicks) * 4, hipMemcpyDeviceToHost, stream));
+    if (pick_scores) GSIM_HIP(hipMemcpyAsync(pick_scores, d_scores, static_cast<size_t>(npicks) * 4, hipMemcpyDeviceToHost, stream));
+    if (row_score) GSIM_HIP(hipMemcpyAsync(row_score, d_maxsim, N * 4, hipMemcpyDeviceToHost, stream));
+    if (nearest) GSIM_HIP(hipMemcpyAsync(nearest, d_nearest, N * 4, hipMemcpyDeviceToHost, stream));
     GSIM_HIP(hipEventRecord(ev_d2h.b, stream));
     GSIM_HIP(hipStreamSynchronize(stream));
 

@@ -25,16 +25,16 @@ int neighbors(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, floa
     GSIM_HIP(set_device(s.device));
     const hipStream_t st = s.stream;
     // popc of every row, and the rows zero-padded to WP words unless they already are WP words
-    DevBuf pop, pad;
-    GSIM_HIP(pop.alloc(N * 4));
-    if (WP != s.W) GSIM_HIP(pad.alloc(N * WP * 4));
+    DevBuf<> pop, pad;
+    GSIM_HIP(pop.grow(N * 4));
+    if (WP != s.W) GSIM_HIP(pad.grow(N * WP * 4));
     GSIM_HIP(gsim::launch_nbr_prepare(s.d_rows, N, s.W, WP, pad.as<uint32_t>(), pop.as<uint32_t>(), st));
 
     const uint64_t nlt = (nout + gsim::kNbrTile - 1) / gsim::kNbrTile;
     const uint64_t nct = (N + gsim::kNbrTile - 1) / gsim::kNbrTile;
     const std::vector<NbrLaunch> plan = plan_launches(nlt, nct, tri, WP);
-    DevBuf ctl; // [0] the cursor, [1 + l] the cursor after launch l, then 4 clock stamps per launch
-    GSIM_HIP(ctl.alloc((1 + 5 * plan.size()) * 8));
+    DevBuf<> ctl; // [0] the cursor, [1 + l] the cursor after launch l, then 4 clock stamps per launch
+    GSIM_HIP(ctl.grow((1 + 5 * plan.size()) * 8));
     unsigned long long* d_cursor = ctl.as<unsigned long long>();
     unsigned long long* d_snap = d_cursor + 1;
     unsigned long long* d_clk = d_snap + plan.size();

@@ -86,15 +86,9 @@ int run_pair_launches(Shard& s, size_t n, unsigned long long* d_cursor, unsigned
     const hipStream_t st = s.stream;
     *out = PairRun{};
     if (n == 0) return GSIM_OK;
-    if (!s.d_nbr_keys) {
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&s.d_nbr_keys), kNbrInitCap * 8);
-        if (e == hipSuccess) {
-            e = hipMalloc(reinterpret_cast<void**>(&s.d_nbr_vals), kNbrInitCap * 4);
-            if (e != hipSuccess) {
-                (void) hipFree(s.d_nbr_keys);
-                s.d_nbr_keys = nullptr;
-            }
-        }
+    if (s.nbr_cap == 0) {
+        hipError_t e = s.d_nbr_keys.grow_keep(kNbrInitCap * 8);
+        if (e == hipSuccess) e = s.d_nbr_vals.grow_keep(kNbrInitCap * 4);
         if (e != hipSuccess) return fail_alloc(e, "the pair buffer");
         s.nbr_cap = kNbrInitCap;
     }
@@ -117,23 +111,16 @@ int run_pair_launches(Shard& s, size_t n, unsigned long long* d_cursor, unsigned
     size_t lf = 0;
     while (snap[lf] <= s.nbr_cap) lf++;
     const unsigned long long kept = lf ? snap[lf - 1] : 0;
-    unsigned long long* nk = nullptr;
-    float* nv = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&nk), total * 8);
-    if (e != hipSuccess) return fail_alloc(e, "growing the pair buffer");
-    e = hipMalloc(reinterpret_cast<void**>(&nv), total * 4);
+    DevBuf<unsigned long long> nk;
+    DevBuf<float> nv;
+    hipError_t e = nk.grow(total * 8);
+    if (e == hipSuccess) e = nv.grow(total * 4);
     if (e == hipSuccess && kept) e = hipMemcpyAsync(nk, s.d_nbr_keys, kept * 8, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess && kept) e = hipMemcpyAsync(nv, s.d_nbr_vals, kept * 4, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void) hipFree(nk);
-        if (nv) (void) hipFree(nv);
-        return fail_alloc(e, "growing the pair buffer");
-    }
-    (void) hipFree(s.d_nbr_keys);
-    (void) hipFree(s.d_nbr_vals);
-    s.d_nbr_keys = nk;
-    s.d_nbr_vals = nv;
+    if (e != hipSuccess) return fail_alloc(e, "growing the pair buffer"); // (the buffer is as it was)
+    s.d_nbr_keys = std::move(nk);
+    s.d_nbr_vals = std::move(nv);
     s.nbr_cap = total;
     GSIM_HIP(ev_rerun.create());
     if (lf) GSIM_HIP(hipMemcpyAsync(d_cursor, d_snap + lf - 1, 8, hipMemcpyDeviceToDevice, st));
@@ -156,7 +143,7 @@ int build_pair_csr(gsim_db* db, Shard& s, uint64_t total, uint64_t nout, int ord
     const bool by_score = order == GSIM_JOIN_BY_SCORE;
     // sort the keys (list, column), then the row offsets and the column indices
     const uint32_t end_bit = 32 + bit_width(nout - 1);
-    DevBuf keys2, vals2, d_indptr, d_indices, tmp;
+    DevBuf<> keys2, vals2, d_indptr, d_indices, tmp;
     EventPair ev_csr, ev_d2h;
     GSIM_HIP(ev_csr.create());
     GSIM_HIP(ev_d2h.create());
@@ -164,27 +151,27 @@ int build_pair_csr(gsim_db* db, Shard& s, uint64_t total, uint64_t nout, int ord
     GSIM_HIP(gsim::nbr_sort_bytes(total, end_bit, &tmp_bytes));
     if (by_score) GSIM_HIP(gsim::join_score_sort_bytes(total, end_bit, &tmp2_bytes));
     tmp_bytes = std::max(tmp_bytes, tmp2_bytes);
-    hipError_t e = keys2.alloc(total * 8);
-    if (e == hipSuccess) e = vals2.alloc(total * 4);
-    if (e == hipSuccess) e = d_indptr.alloc((nout + 1) * 8);
-    if (e == hipSuccess) e = d_indices.alloc(total * 4);
-    if (e == hipSuccess) e = tmp.alloc(tmp_bytes);
+    hipError_t e = keys2.grow(total * 8);
+    if (e == hipSuccess) e = vals2.grow(total * 4);
+    if (e == hipSuccess) e = d_indptr.grow((nout + 1) * 8);
+    if (e == hipSuccess) e = d_indices.grow(total * 4);
+    if (e == hipSuccess) e = tmp.grow(tmp_bytes);
     if (e != hipSuccess) return fail_alloc(e, "device memory for the CSR build");
     GSIM_HIP(hipEventRecord(ev_csr.a, st));
-    GSIM_HIP(gsim::launch_nbr_csr(tmp.p, tmp_bytes, s.d_nbr_keys, s.d_nbr_vals, keys2.as<unsigned long long>(), vals2.as<float>(), total, end_bit,
+    GSIM_HIP(gsim::launch_nbr_csr(tmp, tmp_bytes, s.d_nbr_keys, s.d_nbr_vals, keys2.as<unsigned long long>(), vals2.as<float>(), total, end_bit,
                                   nout, db->row_base, d_indptr.as<uint64_t>(), d_indices.as<uint32_t>(), st));
     if (by_score) // (the pair buffer is free again: the second sort's output; the scores come back in vals2)
-        GSIM_HIP(gsim::launch_join_by_score(tmp.p, tmp_bytes, keys2.as<unsigned long long>(), vals2.as<float>(), s.d_nbr_keys,
-                                            reinterpret_cast<uint32_t*>(s.d_nbr_vals), total, end_bit, nout, db->row_base,
+        GSIM_HIP(gsim::launch_join_by_score(tmp, tmp_bytes, keys2.as<unsigned long long>(), vals2.as<float>(), s.d_nbr_keys,
+                                            s.d_nbr_vals.as<uint32_t>(), total, end_bit, nout, db->row_base,
                                             d_indptr.as<uint64_t>(), d_indices.as<uint32_t>(), vals2.as<float>(), st));
     GSIM_HIP(hipEventRecord(ev_csr.b, st));
     g->indices.resize(total);
     g->scores.resize(total);
     GSIM_HIP(hipEventRecord(ev_d2h.a, st));
-    GSIM_HIP(hipMemcpyAsync(g->indptr.data(), d_indptr.p, (nout + 1) * 8, hipMemcpyDeviceToHost, st));
+    GSIM_HIP(hipMemcpyAsync(g->indptr.data(), d_indptr, (nout + 1) * 8, hipMemcpyDeviceToHost, st));
     if (total) {
-        GSIM_HIP(hipMemcpyAsync(g->indices.data(), d_indices.p, total * 4, hipMemcpyDeviceToHost, st));
-        GSIM_HIP(hipMemcpyAsync(g->scores.data(), vals2.p, total * 4, hipMemcpyDeviceToHost, st));
+        GSIM_HIP(hipMemcpyAsync(g->indices.data(), d_indices, total * 4, hipMemcpyDeviceToHost, st));
+        GSIM_HIP(hipMemcpyAsync(g->scores.data(), vals2, total * 4, hipMemcpyDeviceToHost, st));
     }
     GSIM_HIP(hipEventRecord(ev_d2h.b, st));
     GSIM_HIP(hipStreamSynchronize(st));

@@ -19,39 +19,6 @@ struct gsim_graph {
 namespace gsim_host
 {
 
-// device memory owned for the length of one call
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf()
-    {
-        if (p) (void) hipFree(p);
-    }
-    hipError_t alloc(size_t bytes)
-    {
-        return hipMalloc(&p, bytes ? bytes : 16);
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair()
-    {
-        if (a) (void) hipEventDestroy(a);
-        if (b) (void) hipEventDestroy(b);
-    }
-    hipError_t create()
-    {
-        hipError_t e = hipEventCreate(&a);
-        return e == hipSuccess ? hipEventCreate(&b) : e;
-    }
-    double ms() const
-    {
-        float t = 0.0f;
-        return hipEventElapsedTime(&t, a, b) == hipSuccess ? static_cast<double>(t) : 0.0;
-    }
-};
-
 struct NbrLaunch {
     uint32_t rt0, nrt, ct0, nct;
 };

@@ -16,17 +16,19 @@ int ensure_classic_scratch(Shard& s)
     if (s.classic_ready) return GSIM_OK;
     GSIM_HIP(set_device(s.device));
     const uint64_t slots = static_cast<uint64_t>(s.geo.nwaves) * s.geo.seg_cap;
-    GSIM_HIP(hipMalloc(&s.d_cand, static_cast<size_t>(slots) * 8));
-    GSIM_HIP(hipMalloc(&s.d_cand_cb, static_cast<size_t>(slots) * 4));
-    GSIM_HIP(hipMalloc(&s.d_seg_count, static_cast<size_t>(s.geo.nwaves) * 4));
-    if (s.d_final) { // (the publishing route's smaller list: nothing is in flight on it when a classic query is about to be enqueued
-        GSIM_HIP(hipStreamSynchronize(s.stream)); //  behind it on the same stream -- but the free must not overtake the kernels)
-        GSIM_HIP(hipFree(s.d_final));
-        s.d_final = nullptr;
+    GSIM_HIP(s.d_cand.grow(static_cast<size_t>(slots) * 8));
+    GSIM_HIP(s.d_cand_cb.grow(static_cast<size_t>(slots) * 4));
+    GSIM_HIP(s.d_seg_count.grow(static_cast<size_t>(s.geo.nwaves) * 4));
+    const uint32_t cap = next_pow2_u32(slots);
+    if (s.d_final.bytes() < static_cast<size_t>(cap) * 8) {
+        // (the publishing route's smaller list: nothing is in flight on it when a classic query is about to be enqueued
+        //  behind it on the same stream -- but the free must not overtake the kernels)
+        if (s.d_final) GSIM_HIP(hipStreamSynchronize(s.stream));
+        s.final_cap = 0;
     }
-    s.final_cap = next_pow2_u32(slots);
-    GSIM_HIP(hipMalloc(&s.d_final, static_cast<size_t>(s.final_cap) * 8));
-    GSIM_HIP(hipMalloc(&s.d_final_cb, static_cast<size_t>(s.final_cap) * 4));
+    GSIM_HIP(s.d_final.grow(static_cast<size_t>(cap) * 8));
+    s.final_cap = cap; // (it counts d_final alone, which the publishing routes share: set with it, whatever becomes of d_final_cb)
+    GSIM_HIP(s.d_final_cb.grow(static_cast<size_t>(cap) * 4));
     s.classic_ready = true;
     return GSIM_OK;
 }
@@ -37,27 +39,20 @@ int ensure_publish_scratch(Shard& s)
 {
     if (s.d_final) return GSIM_OK;
     GSIM_HIP(set_device(s.device));
-    s.final_cap = next_pow2_u32(static_cast<uint64_t>(s.fgeo.nwaves / 4) * gsim::kFusedRegion);
-    GSIM_HIP(hipMalloc(&s.d_final, static_cast<size_t>(s.final_cap) * 8));
+    const uint32_t cap = next_pow2_u32(static_cast<uint64_t>(s.fgeo.nwaves / 4) * gsim::kFusedRegion);
+    GSIM_HIP(s.d_final.grow(static_cast<size_t>(cap) * 8));
+    s.final_cap = cap;
     return GSIM_OK;
 }
 
 int ensure_result_capacity(Shard& s, uint32_t k)
 {
     const size_t need = gsim_result_block_bytes(k);
-    if (need > s.result_bytes) {
+    if (need > s.d_result.bytes()) {
         GSIM_HIP(set_device(s.device));
-        if (s.d_result) GSIM_HIP(hipFree(s.d_result));
-        s.d_result = nullptr;
-        GSIM_HIP(hipMalloc(&s.d_result, need));
-        s.result_bytes = need;
+        GSIM_HIP(s.d_result.grow(need));
     }
-    if (need > s.h_result_bytes) {
-        if (s.h_result) GSIM_HIP(hipHostFree(s.h_result));
-        s.h_result = nullptr;
-        GSIM_HIP(hipHostMalloc(&s.h_result, need, kHostPolled));
-        s.h_result_bytes = need;
-    }
+    GSIM_HIP(s.h_result.grow(need));
     return GSIM_OK;
 }
 
@@ -140,19 +135,16 @@ uint32_t next_pub_tag(Shard& s)
 int ensure_largek_scratch(Shard& s, bool bincur, uint32_t large)
 {
     if (large > s.large_cap) {
-        if (s.d_large) GSIM_HIP(hipFree(s.d_large));
-        s.d_large = nullptr;
         s.large_cap = 0;
-        GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_large), static_cast<size_t>(large) * 8));
+        GSIM_HIP(s.d_large.grow(static_cast<size_t>(large) * 8));
         s.large_cap = large;
     }
-    if (!s.d_lk) {
-        GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_lk), sizeof(gsim::LargeKState)));
-        GSIM_HIP(hipMemsetAsync(s.d_lk, 0, sizeof(gsim::LargeKState), s.stream));
-    }
-    if (bincur && !s.d_bincur) {
-        GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_bincur), static_cast<size_t>(gsim::kScanBins) * 8)); // (cursors + the layout)
-        GSIM_HIP(hipMemsetAsync(s.d_bincur, 0, static_cast<size_t>(gsim::kScanBins) * 8, s.stream));
+    bool fresh = false;
+    GSIM_HIP(s.d_lk.grow(sizeof(gsim::LargeKState), &fresh));
+    if (fresh) GSIM_HIP(hipMemsetAsync(s.d_lk, 0, sizeof(gsim::LargeKState), s.stream));
+    if (bincur) {
+        GSIM_HIP(s.d_bincur.grow(static_cast<size_t>(gsim::kScanBins) * 8, &fresh)); // (cursors + the layout)
+        if (fresh) GSIM_HIP(hipMemsetAsync(s.d_bincur, 0, static_cast<size_t>(gsim::kScanBins) * 8, s.stream));
     }
     return GSIM_OK;
 }
@@ -166,7 +158,7 @@ struct QueryLaunch {
     uint32_t k, row_base, ring, pipe_slot;
     void* out;
     bool caller_syncs;
-    hipEvent_t* ev;
+    Event* ev;
 };
 
 // The single launch's arguments: ranking the query, or publishing only (kFusedPublishOnly: M up to fused_publish_max_m, no final threshold)
@@ -197,23 +189,33 @@ hipError_t seed_threshold(const QueryLaunch& q, gsim::FusedArgs& f)
     return e;
 }
 
+// The finalist count the last large-k query left in pinned memory: the last word of h_done's 64-byte block
+static_assert(kPipe <= 15, "the large-k hint word shares h_done's 64-byte block with the pipeline's completion words");
+uint32_t* largek_hint(const Shard& s)
+{
+    return s.h_done + 15;
+}
+
 // Large k: the k-th largest finalist key by a radix select on the device (the finalist count never reaches the host: nothing
 // here waits), the keys at or above it gathered and sorted in global memory (sized by k); `flags` to the emission
-int enqueue_largek_tail(QueryLaunch& q, uint32_t flags)
+int enqueue_largek_tail(const gsim_db* db, Shard& s, const gsim::ScanArgs& a, uint32_t row_base, uint64_t approx_if_no_cutoff, uint32_t flags,
+                        void* out)
 {
-    Shard& s = q.s;
-    const uint32_t np2 = next_pow2_u32(q.k);
+    const uint32_t np2 = next_pow2_u32(a.k);
     const int rc = ensure_largek_scratch(s, false, np2);
     if (rc != GSIM_OK) return rc;
     // (one workgroup in one launch up to 32 Ki finalists, the grid's eight passes beyond, chosen by the finalist
     // count the previous large-k query left in pinned memory: a wrong guess is slower, never wrong)
-    static_assert(kPipe <= 15, "the large-k hint word shares h_done's 64-byte block with the pipeline's completion words");
-    uint32_t* hint = s.h_done + 15;
-    const bool one_block = *static_cast<volatile uint32_t*>(hint) <= static_cast<uint32_t>(q.db->knobs.largek_one_block_max);
-    GSIM_HIP(gsim::launch_largek_select(q.a, s.d_final, s.final_cap, s.d_lk, s.d_large, np2, hint, one_block, s.stream));
+    uint32_t* hint = largek_hint(s);
+    const bool one_block = *static_cast<volatile uint32_t*>(hint) <= static_cast<uint32_t>(db->knobs.largek_one_block_max);
+    GSIM_HIP(gsim::launch_largek_select(a, s.d_final, s.final_cap, s.d_lk, s.d_large, np2, hint, one_block, s.stream));
     // (tiles sorted, then positions by counting + the hits + the header + the state's reset in one launch)
-    GSIM_HIP(gsim::launch_largek_sort_emit(q.a, s.d_large, np2, s.d_lk, q.row_base, s.nrows, flags, q.out, s.stream));
+    GSIM_HIP(gsim::launch_largek_sort_emit(a, s.d_large, np2, s.d_lk, row_base, approx_if_no_cutoff, flags, out, s.stream));
     return GSIM_OK;
+}
+int enqueue_largek_tail(QueryLaunch& q, uint32_t flags)
+{
+    return enqueue_largek_tail(q.db, q.s, q.a, q.row_base, q.s.nrows, flags, q.out);
 }
 
 // The four-kernel pipeline: sample -> scan -> compact -> select (`select`) or the large-k tail; gated (a.gate) behind a launch.
@@ -249,7 +251,7 @@ int enqueue_ranked(QueryLaunch& q, bool seed)
     f.epoch = ++s.epoch & 0xFFFFFFu;
     if (f.epoch == 0) f.epoch = ++s.epoch & 0xFFFFFFu; // 0: what a clean header holds
     if (q.caller_syncs) static_cast<gsim_result_header*>(q.out)->flags = 0;
-    if (q.db->knobs.fused_debug && !s.d_dbg) GSIM_HIP(hipMalloc(reinterpret_cast<void**>(&s.d_dbg), (static_cast<size_t>(s.fgeo.nwaves / 4) * 24 + 8) * 8));
+    if (q.db->knobs.fused_debug) GSIM_HIP(s.d_dbg.grow((static_cast<size_t>(s.fgeo.nwaves / 4) * 24 + 8) * 8));
     f.dbg = s.d_dbg;
     if (q.ev) GSIM_HIP(hipEventRecord(q.ev[0], s.stream));
     if (seed) GSIM_HIP(seed_threshold(q, f));
@@ -297,16 +299,11 @@ int enqueue_query_impl(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k,
 {
     Shard::PipeSlot& sl = s.slot[pipe_slot]; // (only touched for synchronous callers)
     GSIM_HIP(set_device(s.device));
-    if (s.state_dirty) { // a previous enqueue failed half way: the per-query state may not be zero
-        GSIM_HIP(hipMemsetAsync(s.d_state, 0, offsetof(gsim::QueryState, redo_why), s.stream)); // (the per-query part)
-        if (s.d_lk) GSIM_HIP(hipMemsetAsync(s.d_lk, 0, sizeof(gsim::LargeKState), s.stream));   // (a large-k enqueue may have failed between its radix passes)
-        GSIM_HIP(hipMemsetAsync(s.d_summ, 0, kSummBytes, s.stream));
-        if (s.d_bincur) GSIM_HIP(hipMemsetAsync(s.d_bincur, 0, static_cast<size_t>(gsim::kScanBins) * 4, s.stream));
-        s.state_dirty = false;
-    }
+    int rc = rezero_dirty_state(s);
+    if (rc != GSIM_OK) return rc;
     const QueryPlan p = plan_query(db, s, k, caller_syncs, mode);
     // the four-kernel pipeline's scratch wherever it runs (gated or not); behind a synchronous caller's publishing launch, its finalists'
-    int rc = p.route == Route::kClassic || !caller_syncs ? ensure_classic_scratch(s) : p.route != Route::kRanked ? ensure_publish_scratch(s) : GSIM_OK;
+    rc = p.route == Route::kClassic || !caller_syncs ? ensure_classic_scratch(s) : p.route != Route::kRanked ? ensure_publish_scratch(s) : GSIM_OK;
     if (rc != GSIM_OK) return rc;
     const uint32_t ring = s.q_next++ % kQueryRing;
     uint32_t* hq = s.h_query + static_cast<size_t>(ring) * s.W;
@@ -316,23 +313,9 @@ int enqueue_query_impl(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k,
     }
     std::memcpy(hq, query, static_cast<size_t>(s.W) * 4); // `query` is already folded for a folded table
 
-    QueryLaunch q{db, s, {}, k, row_base, ring, pipe_slot, out, caller_syncs, nullptr};
+    // (the kernels read hq -- hipHostMalloc memory: device-visible at the same address; a.gate: null, set behind a launch)
+    QueryLaunch q{db, s, scan_args(s, query, hq, s.d_query, k, cutoff, metric, alpha, beta), k, row_base, ring, pipe_slot, out, caller_syncs, nullptr};
     gsim::ScanArgs& a = q.a;
-    a.rows = s.d_rows;
-    a.nrows = s.nrows;
-    a.W = s.W;
-    a.query = hq; // hipHostMalloc memory: device-visible at the same address
-    a.query_dev = s.d_query;
-    a.qpop = popcount_words(query, s.W);
-    a.k = k;
-    a.cutoff = cutoff;
-    a.metric = metric;
-    a.alpha = alpha;
-    a.beta = beta;
-    a.cand = s.d_cand;
-    a.cand_cb = s.d_cand_cb;
-    a.seg_count = s.d_seg_count;
-    a.state = s.d_state; // (a.gate: null, set behind a launch)
     if (s.geo.lanes_per_row == 0 || s.nrows == 0) {
         // generic-width scan reads the query per word: give it a device copy
         GSIM_HIP(hipMemcpyAsync(s.d_query, hq, static_cast<size_t>(s.W) * 4, hipMemcpyHostToDevice, s.stream));
@@ -341,9 +324,9 @@ int enqueue_query_impl(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k,
     if (db->timing && s.ev_used < kTimingRing) {
         if (s.ev.size() < static_cast<size_t>(3 * (s.ev_used + 1))) {
             for (int i = 0; i < 3; i++) {
-                hipEvent_t e;
-                GSIM_HIP(hipEventCreate(&e));
-                s.ev.push_back(e);
+                Event e;
+                GSIM_HIP(e.create());
+                s.ev.push_back(std::move(e));
             }
         }
         q.ev = &s.ev[3 * s.ev_used];
@@ -370,12 +353,47 @@ int enqueue_query_impl(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k,
     // A synchronous query that does not end in the single launch's self-announcing block is waited for through an event of its
     // own: the stream holds up to kPipe - 1 later queries of a pipelined call, and waiting for IT to drain idled the device between
     // batches of eight (k = 8192 at 1 M rows: 74 us a query for 59 us of kernels).
-    if (!sl.ev) GSIM_HIP(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+    GSIM_HIP(sl.ev.create(hipEventDisableTiming));
     GSIM_HIP(hipEventRecord(sl.ev, s.stream));
     sl.ev_set = true;
     return GSIM_OK;
 }
 } // namespace
+
+// A previous enqueue failed half way (state_dirty): the per-query state may not be zero -- re-zeroed before the next one
+int rezero_dirty_state(Shard& s)
+{
+    if (!s.state_dirty) return GSIM_OK;
+    GSIM_HIP(hipMemsetAsync(s.d_state, 0, offsetof(gsim::QueryState, redo_why), s.stream)); // (the per-query part)
+    if (s.d_lk) GSIM_HIP(hipMemsetAsync(s.d_lk, 0, sizeof(gsim::LargeKState), s.stream));   // (a large-k enqueue may have failed between its radix passes)
+    GSIM_HIP(hipMemsetAsync(s.d_summ, 0, kSummBytes, s.stream));
+    if (s.d_bincur) GSIM_HIP(hipMemsetAsync(s.d_bincur, 0, static_cast<size_t>(gsim::kScanBins) * 4, s.stream));
+    s.state_dirty = false;
+    return GSIM_OK;
+}
+
+// A query's kernel arguments on a shard: `query_words` on the host (for its popcount), `query` / `query_dev` as the kernels read it
+gsim::ScanArgs scan_args(const Shard& s, const uint32_t* query_words, const uint32_t* query, uint32_t* query_dev, uint32_t k, float cutoff, int metric,
+                         float alpha, float beta)
+{
+    gsim::ScanArgs a{};
+    a.rows = s.d_rows;
+    a.nrows = s.nrows;
+    a.W = s.W;
+    a.query = query;
+    a.query_dev = query_dev;
+    a.qpop = popcount_words(query_words, s.W);
+    a.k = k;
+    a.cutoff = cutoff;
+    a.metric = metric;
+    a.alpha = alpha;
+    a.beta = beta;
+    a.cand = s.d_cand;
+    a.cand_cb = s.d_cand_cb;
+    a.seg_count = s.d_seg_count;
+    a.state = s.d_state; // (zero between queries: a query's last kernel re-zeroes it)
+    return a;
+}
 
 // The four-kernel pipeline's tail behind a scan of the caller's own (capi_subset.cpp): compaction of the candidate segments of
 // geometry g, then the select kernel or, above kSelectCap, the large-k select and sort -- as enqueue_classic runs them.
@@ -387,14 +405,7 @@ int enqueue_scan_tail(gsim_db* db, Shard& s, const gsim::ScanArgs& a, const gsim
         GSIM_HIP(gsim::launch_select(a, s.d_final, s.d_final_cb, s.final_cap, row_base, out, s.stream));
         return GSIM_OK;
     }
-    const uint32_t np2 = next_pow2_u32(a.k);
-    const int rc = ensure_largek_scratch(s, false, np2);
-    if (rc != GSIM_OK) return rc;
-    uint32_t* hint = s.h_done + 15; // (enqueue_largek_tail's hint word)
-    const bool one_block = *static_cast<volatile uint32_t*>(hint) <= static_cast<uint32_t>(db->knobs.largek_one_block_max);
-    GSIM_HIP(gsim::launch_largek_select(a, s.d_final, s.final_cap, s.d_lk, s.d_large, np2, hint, one_block, s.stream));
-    GSIM_HIP(gsim::launch_largek_sort_emit(a, s.d_large, np2, s.d_lk, row_base, approx_if_no_cutoff, 1u, out, s.stream));
-    return GSIM_OK;
+    return enqueue_largek_tail(db, s, a, row_base, approx_if_no_cutoff, 1u, out);
 }
 
 int enqueue_query(gsim_db* db, Shard& s, const uint32_t* query, uint32_t k, float cutoff, int metric, float alpha,
@@ -626,8 +637,7 @@ int ensure_lanes(gsim_db* db, Shard& s)
         l.first_row = s.first_row;
         l.nrows = s.nrows;
         l.W = s.W;
-        l.d_rows = s.d_rows;
-        l.owns_rows = false;
+        l.d_rows = s.d_rows; // (borrowed)
         const int rc = setup_shard(db, l);
         if (rc != GSIM_OK) {
             for (auto& x : s.lanes) (void) free_shard(x);
@@ -672,13 +682,7 @@ int search_each_pipelined(gsim_db* db, const uint32_t* queries, uint32_t nq, uin
     }
     auto pipe_blocks = [&](Shard& s) -> int {
         GSIM_HIP(set_device(s.device));
-        if (blk > s.h_pipe_block) {
-            if (s.h_pipe) GSIM_HIP(hipHostFree(s.h_pipe));
-            s.h_pipe = nullptr;
-            s.h_pipe_block = 0;
-            GSIM_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.h_pipe), blk * kPipe, kHostPolled));
-            s.h_pipe_block = blk;
-        }
+        GSIM_HIP(s.h_pipe.grow(blk * kPipe));
         return GSIM_OK;
     };
     for (size_t i = 0; i < nsh; i++) {
@@ -699,7 +703,7 @@ int search_each_pipelined(gsim_db* db, const uint32_t* queries, uint32_t nq, uin
                 Shard& s = state_of(i, issued);
                 const uint32_t slot = slot_of(i, issued);
                 const int rc = enqueue_query(db, s, queries + static_cast<size_t>(issued) * db->W, k, cutoff, metric, alpha, beta,
-                                             db->row_base + static_cast<uint32_t>(s.first_row), s.h_pipe + slot * s.h_pipe_block, true, kAuto, slot);
+                                             db->row_base + static_cast<uint32_t>(s.first_row), s.h_pipe + slot * blk, true, kAuto, slot);
                 if (rc != GSIM_OK) return rc;
                 if (use_lanes[i]) db->lane_queries++;
             }
@@ -710,7 +714,7 @@ int search_each_pipelined(gsim_db* db, const uint32_t* queries, uint32_t nq, uin
             Shard& s = state_of(i, done);
             const uint32_t slot = slot_of(i, done);
             GSIM_HIP(set_device(s.device));
-            void* out = s.h_pipe + slot * s.h_pipe_block;
+            void* out = s.h_pipe + slot * blk;
             const int rc = finish_query_sync(db, s, queries + static_cast<size_t>(done) * db->W, k, cutoff, metric, alpha, beta,
                                              db->row_base + static_cast<uint32_t>(s.first_row), out, slot);
             if (rc != GSIM_OK) return rc;

@@ -11,49 +11,6 @@ namespace gsim_host
 namespace
 {
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf()
-    {
-        if (p) (void) hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-    void* release()
-    {
-        void* q = p;
-        p = nullptr;
-        return q;
-    }
-};
-
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair()
-    {
-        if (a) (void) hipEventDestroy(a);
-        if (b) (void) hipEventDestroy(b);
-    }
-    hipError_t create()
-    {
-        hipError_t e = hipEventCreate(&a);
-        return e == hipSuccess ? hipEventCreate(&b) : e;
-    }
-    double ms() const
-    {
-        float t = 0.0f;
-        return hipEventElapsedTime(&t, a, b) == hipSuccess ? static_cast<double>(t) : 0.0;
-    }
-};
-
-#define GSIM_ALLOC(buf, bytes, what)                            \
-    do {                                                        \
-        if ((buf).alloc(bytes) != hipSuccess) {                 \
-            (void) hipGetLastError();                           \
-            return fail(GSIM_ERR_NOMEM, "device memory for " what); \
-        }                                                       \
-    } while (0)
-
 // what both constructors check after their own arguments, in this order
 int check_rowset_state(const gsim_db* db)
 {
@@ -76,37 +33,38 @@ int build_rowset(gsim_db* db, const uint32_t* rows, uint64_t n, const uint32_t* 
     rs->device = s.device;
     rs->nrows = N;
     rs->row_base = db->row_base;
-    DevBuf d_bits, d_in, d_popc, d_offs, d_tmp, d_list;
+    DevBuf<uint32_t>& d_bits = rs->d_bits; // (the set keeps these two; the others are freed on return)
+    DevBuf<uint32_t>& d_list = rs->d_list;
+    DevBuf<uint32_t> d_in, d_popc, d_offs;
+    DevBuf<> d_tmp;
     GSIM_ALLOC(d_bits, nalloc * 4, "the row set's bitmap");
     GSIM_ALLOC(d_popc, (nwords + 1) * 4, "the row set's word counts");
     GSIM_ALLOC(d_offs, (nwords + 1) * 4, "the row set's word offsets");
     if (bits) {
         GSIM_ALLOC(d_in, nwords * 4, "the caller's bitmap");
-        GSIM_HIP(hipMemcpyAsync(d_in.p, bits, nwords * 4, hipMemcpyHostToDevice, st));
+        GSIM_HIP(hipMemcpyAsync(d_in, bits, nwords * 4, hipMemcpyHostToDevice, st));
     } else {
-        GSIM_HIP(hipMemsetAsync(d_bits.p, 0, nalloc * 4, st));
+        GSIM_HIP(hipMemsetAsync(d_bits, 0, nalloc * 4, st));
         if (n) {
             GSIM_ALLOC(d_in, n * 4, "the caller's rows");
-            GSIM_HIP(hipMemcpyAsync(d_in.p, rows, n * 4, hipMemcpyHostToDevice, st));
-            GSIM_HIP(gsim::launch_rowset_mark(d_in.as<uint32_t>(), n, db->row_base, N, d_bits.as<uint32_t>(), st));
+            GSIM_HIP(hipMemcpyAsync(d_in, rows, n * 4, hipMemcpyHostToDevice, st));
+            GSIM_HIP(gsim::launch_rowset_mark(d_in, n, db->row_base, N, d_bits, st));
         }
     }
-    GSIM_HIP(gsim::launch_rowset_finish(d_bits.as<uint32_t>(), bits ? d_in.as<uint32_t>() : nullptr, N, nalloc, exclude ? 1 : 0,
-                                        d_popc.as<uint32_t>(), st));
+    GSIM_HIP(gsim::launch_rowset_finish(d_bits, bits ? d_in.as<uint32_t>() : nullptr, N, nalloc, exclude ? 1 : 0,
+                                        d_popc, st));
     size_t tmp_bytes = 0;
     GSIM_HIP(gsim::rowset_scan_bytes(nwords + 1, &tmp_bytes));
     GSIM_ALLOC(d_tmp, tmp_bytes, "the row set's prefix sums");
-    GSIM_HIP(gsim::launch_rowset_offsets(d_tmp.p, tmp_bytes, d_popc.as<uint32_t>(), d_offs.as<uint32_t>(), nwords + 1, st));
+    GSIM_HIP(gsim::launch_rowset_offsets(d_tmp, tmp_bytes, d_popc, d_offs, nwords + 1, st));
     uint32_t count = 0;
-    GSIM_HIP(hipMemcpyAsync(&count, d_offs.as<uint32_t>() + nwords, 4, hipMemcpyDeviceToHost, st));
+    GSIM_HIP(hipMemcpyAsync(&count, d_offs + nwords, 4, hipMemcpyDeviceToHost, st));
     GSIM_HIP(hipStreamSynchronize(st));
     // (a full 2^32 - 1-row table selected whole still fits: the sum is < 2^32)
     GSIM_ALLOC(d_list, static_cast<size_t>(count) * 4, "the row set's list");
-    GSIM_HIP(gsim::launch_rowset_list(d_bits.as<uint32_t>(), d_offs.as<uint32_t>(), nwords, d_list.as<uint32_t>(), st));
+    GSIM_HIP(gsim::launch_rowset_list(d_bits, d_offs, nwords, d_list, st));
     GSIM_HIP(hipStreamSynchronize(st)); // (the temporaries are freed on return)
     rs->count = count;
-    rs->d_bits = static_cast<uint32_t*>(d_bits.release());
-    rs->d_list = static_cast<uint32_t*>(d_list.release());
     return GSIM_OK;
 }
 
@@ -117,8 +75,6 @@ int make_rowset(gsim_db* db, const uint32_t* rows, uint64_t n, const uint32_t* b
     if (!rs) return fail(GSIM_ERR_NOMEM, "row set");
     const int rc = build_rowset(db, rows, n, bits, (flags & GSIM_ROWSET_EXCLUDE) != 0, rs);
     if (rc != GSIM_OK) {
-        if (rs->d_bits) (void) hipFree(rs->d_bits);
-        if (rs->d_list) (void) hipFree(rs->d_list);
         delete rs;
         return rc;
     }
@@ -138,27 +94,14 @@ int ensure_subset_scratch(Shard& s, const gsim::ScanGeometry& g)
     const uint64_t need = static_cast<uint64_t>(g.nwaves) * g.seg_cap;
     if (need <= have && g.nwaves <= have_waves) return GSIM_OK;
     GSIM_HIP(hipStreamSynchronize(s.stream)); // (nothing of this handle is in flight under the lock -- but a free must not overtake a kernel)
-    if (need > have) {
-        void *cand = nullptr, *cb = nullptr;
-        if (hipMalloc(&cand, static_cast<size_t>(need) * 8) != hipSuccess || hipMalloc(&cb, static_cast<size_t>(need) * 4) != hipSuccess) {
-            (void) hipGetLastError();
-            if (cand) (void) hipFree(cand);
+    if (need > have) { // (allocate, then swap: a failure leaves the classic route's scratch standing)
+        if (s.d_cand.grow_keep(static_cast<size_t>(need) * 8) != hipSuccess || s.d_cand_cb.grow_keep(static_cast<size_t>(need) * 4) != hipSuccess)
             return fail(GSIM_ERR_NOMEM, "device memory for the candidate segments of a row-set search");
-        }
-        (void) hipFree(s.d_cand);
-        (void) hipFree(s.d_cand_cb);
-        s.d_cand = static_cast<unsigned long long*>(cand);
-        s.d_cand_cb = static_cast<uint32_t*>(cb);
         s.cand_slots = need;
     }
     if (g.nwaves > have_waves) {
-        void* sc = nullptr;
-        if (hipMalloc(&sc, static_cast<size_t>(g.nwaves) * 4) != hipSuccess) {
-            (void) hipGetLastError();
+        if (s.d_seg_count.grow_keep(static_cast<size_t>(g.nwaves) * 4) != hipSuccess)
             return fail(GSIM_ERR_NOMEM, "device memory for the segment counts of a row-set search");
-        }
-        (void) hipFree(s.d_seg_count);
-        s.d_seg_count = static_cast<uint32_t*>(sc);
         s.seg_waves = g.nwaves;
     }
     return GSIM_OK;
@@ -195,38 +138,18 @@ int search_rows(gsim_db* db, Shard& s, const gsim_rowset* rs, const uint32_t* qu
     const gsim::ScanGeometry g = gather ? gsim::subset_gather_geometry(sel, s.W, s.num_cus) : gsim::subset_scan_geometry(s.nrows, s.W, s.num_cus);
     int rc = ensure_subset_scratch(s, g);
     if (rc == GSIM_OK) rc = ensure_result_capacity(s, k);
+    if (rc == GSIM_OK) rc = rezero_dirty_state(s);
     if (rc != GSIM_OK) return rc;
-    if (s.state_dirty) { // a previous enqueue failed half way (enqueue_query_impl's rule)
-        GSIM_HIP(hipMemsetAsync(s.d_state, 0, offsetof(gsim::QueryState, redo_why), stream));
-        if (s.d_lk) GSIM_HIP(hipMemsetAsync(s.d_lk, 0, sizeof(gsim::LargeKState), stream));
-        GSIM_HIP(hipMemsetAsync(s.d_summ, 0, kSummBytes, stream));
-        if (s.d_bincur) GSIM_HIP(hipMemsetAsync(s.d_bincur, 0, static_cast<size_t>(gsim::kScanBins) * 4, stream));
-        s.state_dirty = false;
-    }
-    DevBuf d_q; // the call's queries (16-byte aligned rows when W % 4 == 0)
+    DevBuf<uint32_t> d_q; // the call's queries (16-byte aligned rows when W % 4 == 0)
     GSIM_ALLOC(d_q, static_cast<size_t>(nq) * s.W * 4, "the queries of a row-set search");
-    GSIM_HIP(hipMemcpyAsync(d_q.p, queries, static_cast<size_t>(nq) * s.W * 4, hipMemcpyHostToDevice, stream));
+    GSIM_HIP(hipMemcpyAsync(d_q, queries, static_cast<size_t>(nq) * s.W * 4, hipMemcpyHostToDevice, stream));
     EventPair ev;
     if (st) GSIM_HIP(ev.create());
     const uint32_t row_base = db->row_base + static_cast<uint32_t>(s.first_row);
     for (uint32_t q = 0; q < nq; q++) {
         const uint32_t* query = queries + static_cast<size_t>(q) * s.W;
-        gsim::ScanArgs a{};
-        a.rows = s.d_rows;
-        a.nrows = s.nrows;
-        a.W = s.W;
-        a.query = d_q.as<uint32_t>() + static_cast<size_t>(q) * s.W;
-        a.query_dev = const_cast<uint32_t*>(a.query); // (the tail reads the same copy: nothing to write)
-        a.qpop = popcount_words(query, s.W);
-        a.k = k;
-        a.cutoff = cutoff;
-        a.metric = metric;
-        a.alpha = alpha;
-        a.beta = beta;
-        a.cand = s.d_cand;
-        a.cand_cb = s.d_cand_cb;
-        a.seg_count = s.d_seg_count;
-        a.state = s.d_state; // zero between queries: the tail's last workgroup re-zeroes it
+        uint32_t* dq = d_q + static_cast<size_t>(q) * s.W; // (the tail reads the same copy: nothing to write)
+        gsim::ScanArgs a = scan_args(s, query, dq, dq, k, cutoff, metric, alpha, beta);
         if (st) GSIM_HIP(hipEventRecord(ev.a, stream));
         // No seed: sample_kernel's threshold counts rows of the whole table and may lie above the set's k-th best (DESIGN.md
         // section 12); both scans start from gtau = 0 and raise it through the histogram of SELECTED rows.
@@ -238,7 +161,7 @@ int search_rows(gsim_db* db, Shard& s, const gsim_rowset* rs, const uint32_t* qu
         if (st) GSIM_HIP(hipEventRecord(ev.b, stream));
         rc = wait_stream(stream);
         if (rc != GSIM_OK) return rc;
-        const gsim_result_header* h = reinterpret_cast<const gsim_result_header*>(s.h_result);
+        const gsim_result_header* h = s.h_result.as<const gsim_result_header>();
         const uint32_t n = std::min(h->count, k);
         std::memcpy(hits + static_cast<size_t>(q) * kout, h + 1, sizeof(gsim_hit) * n);
         counts[q] = n;
@@ -306,11 +229,7 @@ int gsim_rowset_rows(const gsim_rowset* rs, uint32_t* rows)
 int gsim_rowset_destroy(gsim_rowset* rs)
 {
     if (!rs) return GSIM_OK;
-    if (rs->d_bits || rs->d_list) {
-        (void) set_device(rs->device);
-        if (rs->d_bits) (void) hipFree(rs->d_bits);
-        if (rs->d_list) (void) hipFree(rs->d_list);
-    }
+    (void) set_device(rs->device);
     delete rs;
     return GSIM_OK;
 }
