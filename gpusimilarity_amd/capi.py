@@ -25,8 +25,13 @@ SYNTH_SPARSE = 0
 SYNTH_DENSE = 1
 SYNTH_MORGAN = 2
 SELECT_CAP = 8192
+GROUP_MAX = 0
+GROUP_MIN = 1
+GROUP_MEAN = 2
+GROUP_MAX_QUERIES = 1024
 
 HIT_DTYPE = np.dtype([("row", "<u4"), ("score", "<f4"), ("common", "<u2"), ("popc_db", "<u2")])
+GROUP_HIT_DTYPE = np.dtype([("row", "<u4"), ("score", "<f4"), ("which", "<u2"), ("popc_db", "<u2")])
 HEADER_DTYPE = np.dtype([("count", "<u4"), ("flags", "<u4"), ("approx", "<u8")])
 
 
@@ -62,6 +67,11 @@ class GsimRowsetStats(C.Structure):
                 ("kernel_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
+class GsimGroupStats(C.Structure):
+    _fields_ = [("queries", C.c_uint64), ("launches", C.c_uint64), ("pairs", C.c_uint64), ("scan_ms", C.c_double),
+                ("kernel_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -84,6 +94,7 @@ EXPORTS = [
     "gsim_db_join_queries", "gsim_db_join", "gsim_graph_get_join_stats",
     "gsim_db_maxmin",
     "gsim_rowset_from_rows", "gsim_rowset_from_bitmap", "gsim_rowset_count", "gsim_rowset_rows", "gsim_rowset_destroy", "gsim_db_search_rows",
+    "gsim_db_search_group",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -177,6 +188,8 @@ def load():
         "gsim_rowset_destroy": (C.c_int, [vp]),
         "gsim_db_search_rows": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, vp, u32p, u64p,
                                           C.POINTER(GsimRowsetStats)]),
+        "gsim_db_search_group": (C.c_int, [vp, u32p, C.c_uint32, C.c_int, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, vp, u32p, u64p,
+                                           C.POINTER(GsimGroupStats)]),
         "gsim_last_error": (C.c_char_p, []),
         "gsim_version": (C.c_char_p, []),
     }
@@ -456,6 +469,21 @@ class Table:
         out = [hits[i, :counts[i]].copy() for i in range(nq)], approx
         if stats:
             out += ({f: getattr(st, f) for f, _ in GsimRowsetStats._fields_},)
+        return out
+
+    def search_group(self, queries, k, mode=GROUP_MAX, cutoff=0.0, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, stats=False):
+        """gsim_db_search_group: the top k rows by the MAX, MIN or MEAN of their scores against the set `queries` ->
+        (GROUP_HIT_DTYPE array, approx); with stats=True a third item, the call's gsim_group_stats as a dict."""
+        q = np.ascontiguousarray(queries, dtype=np.uint32).reshape(-1, self.W)
+        hits = np.zeros(max(k, 1), dtype=GROUP_HIT_DTYPE)
+        count = C.c_uint32(0)
+        approx = C.c_uint64(0)
+        st = GsimGroupStats()
+        check(self._L.gsim_db_search_group(self._h, _u32(q), q.shape[0], mode, k, cutoff, metric, alpha, beta,
+                                           hits.ctypes.data_as(C.c_void_p), C.byref(count), C.byref(approx), C.byref(st)))
+        out = hits[:count.value].copy(), approx.value
+        if stats:
+            out += ({f: getattr(st, f) for f, _ in GsimGroupStats._fields_},)
         return out
 
     def make_search_buffers(self, nq, k):

@@ -156,6 +156,8 @@ struct Shard {
     Backoff publish_backoff{1, 1, 0};  // the publishing launch: 2, 4, ... 64
     Backoff binrank_backoff{16, 0, 0}; // the bin-ranked emission (ties in the top bins): 16, 32, ... 1024, by the radix tail instead
     DevBuf<unsigned long long> d_dbg; // GSIM_FUSED_DEBUG: per-workgroup phase timestamps
+    DevBuf<uint32_t> d_gqueries; // gsim_db_search_group: the call's queries and, behind them, their popcounts (grown, never shrunk)
+    HostBuf<uint32_t> h_gqpop{kHostPinned}; // ... the popcounts' pinned staging
     DevBuf<> d_result;
     // pinned host staging; queries go through a ring so that back-to-back
     // asynchronous searches never overwrite a query whose upload is still queued
@@ -310,6 +312,8 @@ gsim::ScanArgs scan_args(const Shard& s, const uint32_t* query_words, const uint
                          float alpha, float beta);
 int enqueue_scan_tail(gsim_db* db, Shard& s, const gsim::ScanArgs& a, const gsim::ScanGeometry& g, uint32_t row_base, uint64_t approx_if_no_cutoff,
                       void* out);
+// capi_subset.cpp: the candidate scratch for a scan of geometry g behind which enqueue_scan_tail runs (row sets, group queries)
+int ensure_subset_scratch(Shard& s, const gsim::ScanGeometry& g);
 // capi_batch.cpp: multi-query passes
 int enqueue_batch(gsim_db* db, Shard& s, const uint32_t* queries, uint32_t nq, uint32_t k, float cutoff, int metric, float alpha,
                   float beta, uint32_t row_base, void* results, bool allow_mfma = true);

@@ -70,6 +70,7 @@ gsim::Knobs read_knobs()
     if (const char* v = std::getenv("GSIM_FOLD_RESCORE")) k.fold_rescore_host = std::string(v) == "host" ? 1 : 0;
     k.join_stream_max_rows = env_value("GSIM_JOIN_STREAM_MAX_ROWS", k.join_stream_max_rows);
     k.subset_gather_max_permille = std::max(env_value("GSIM_SUBSET_GATHER_MAX_PERMILLE", k.subset_gather_max_permille), 0);
+    if (const char* v = std::getenv("GSIM_GROUP_LAUNCH_PAIRS")) k.group_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
     return k;
 }
 

@@ -82,9 +82,12 @@ int make_rowset(gsim_db* db, const uint32_t* rows, uint64_t n, const uint32_t* b
     return GSIM_OK;
 }
 
+} // namespace
+
 // The candidate scratch of the four-kernel pipeline (allocated on first use, as the classic route does), grown where a row-set
 // geometry has more waves or slots than the shard's own (widths whose masked scan takes another loop than launch_scan's; a
-// gather grid's rounding) -- larger buffers are invisible to the classic kernels, which address them with their own geometry.
+// gather grid's rounding; a group query's grid) -- larger buffers are invisible to the classic kernels, which address them with
+// their own geometry.
 int ensure_subset_scratch(Shard& s, const gsim::ScanGeometry& g)
 {
     const int rc = ensure_classic_scratch(s);
@@ -106,6 +109,9 @@ int ensure_subset_scratch(Shard& s, const gsim::ScanGeometry& g)
     }
     return GSIM_OK;
 }
+
+namespace
+{
 
 // gather when selected x max(row bytes, 128) x 1000 <= permille x N x row bytes
 bool gather_applies(const gsim_db* db, const Shard& s, uint64_t selected)

@@ -197,6 +197,9 @@ struct Knobs {
     int subset_gather_max_permille = 250; // GSIM_SUBSET_GATHER_MAX_PERMILLE  gsim_db_search_rows gathers the selected rows when
                                      // selected x max(row bytes, 128) x 1000 <= this x N x row bytes, else streams the table under the
                                      // mask (0: always stream, 1000 or more: always gather; DESIGN.md section 12 has the crossover)
+    long long group_launch_pairs = 0; // GSIM_GROUP_LAUNCH_PAIRS  a launch of gsim_db_search_group scores at most this many row x query
+                                     // pairs (at least one chunk of rows); 0: by the row width (capi_group.cpp group_launch_pairs;
+                                     // DESIGN.md section 13 has the rates and the arithmetic)
 };
 
 ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll, bool ragged = true);
@@ -438,6 +441,22 @@ ScanGeometry subset_scan_geometry(uint64_t nrows, uint32_t W, int num_cus);  // 
 ScanGeometry subset_gather_geometry(uint64_t nsel, uint32_t W, int num_cus); // gather: the list
 hipError_t launch_subset_scan(const ScanArgs& a, const ScanGeometry& g, const uint32_t* bits, hipStream_t s);
 hipError_t launch_subset_gather(const ScanArgs& a, const ScanGeometry& g, const uint32_t* list, uint32_t nsel, hipStream_t s);
+
+// ---- group queries (gsim_group.hip, gsim_db_search_group) --------------------------------------------------------------------------
+struct GroupArgs {
+    const uint32_t* queries; // device, nq x W words
+    const uint32_t* qpop;    // device, nq popcounts
+    uint32_t nq;
+    int mode;                // GSIM_GROUP_MAX / _MIN / _MEAN
+    uint64_t c0, c1;         // this launch: chunks [c0, c1) of g.chunk_rows rows
+    uint32_t first;          // 1: the pass's first launch (the waves' segments start empty)
+};
+// The grid of every launch of a pass (chunk c belongs to wave c % nwaves in all of them); seg_cap holds every row of a wave's share.
+ScanGeometry group_geometry(uint64_t nrows, uint32_t W, int num_cus);
+// One launch of the pass: leaves what launch_scan leaves (candidate segments, seg_count, QueryState) once the last one has run.
+hipError_t launch_group_scan(const ScanArgs& a, const ScanGeometry& g, const GroupArgs& ga, hipStream_t s);
+// Behind the tail: `which` of hits [h0, h1) of a block whose header carries flag 1 (device-side test; ga.c0 / c1 / first unused).
+hipError_t launch_group_which(const ScanArgs& a, const GroupArgs& ga, uint32_t row_base, void* block, uint32_t h0, uint32_t h1, hipStream_t s);
 
 hipError_t launch_generate(void* rows, uint64_t seed, int kind, uint64_t first_row, uint64_t nrows,
                            uint32_t W, hipStream_t s);

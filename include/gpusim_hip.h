@@ -492,6 +492,55 @@ int gsim_rowset_destroy(gsim_rowset* rs);
 int gsim_db_search_rows(gsim_db* db, const gsim_rowset* rs, const uint32_t* queries, uint32_t nq, uint32_t k, float cutoff, int metric,
                         float alpha, float beta, gsim_hit* hits, uint32_t* counts, uint64_t* approx, gsim_rowset_stats* stats /* or NULL */);
 
+/* ---- group queries: exact top-k by MAX, MIN or MEAN similarity to a set of queries ---------------------------------------------- */
+/* gsim_db_search_group ranks the table by its similarity to a SET of nq queries ("the known actives") in one pass over the table:
+ * by the nearest of them (MAX: group fusion, 1-NN scoring), by the farthest (MIN: "similar to all of them") or by their mean (MEAN).
+ * Single-shard, unfolded handles.  No counterpart in the reference.
+ * THE RESULT RULE:
+ *   - pair score: s_i(r) is the `score` gsim_db_search returns for query i and row r at cutoff 0, bit for bit; NaN (0 / 0) counts as 0.0;
+ *   - GSIM_GROUP_MAX:  g(r) = max_i s_i(r), `which` = the lowest i that attains it;
+ *     GSIM_GROUP_MIN:  g(r) = min_i s_i(r), `which` = the lowest i that attains it;
+ *     GSIM_GROUP_MEAN: g(r) = fdiv_rn(acc_M, (float) M) with acc_0 = 0.0f, acc_{i+1} = fadd_rn(acc_i, s_i(r)) -- one IEEE f32 rounding per
+ *     step, in query order 0 ... M-1, no contraction (the order is part of the rule: another order gives other bits); `which` = 0;
+ *   - cutoff and approx: the group score is then treated exactly as a single query's score: g = g >= cutoff ? g : 0; with cutoff <= 0
+ *     every row is kept, otherwise the rows with g != 0; *approx (may be NULL) = the number kept.  The cutoff applies to the group
+ *     score, never to a pair score;
+ *   - hits: the first min(k, kept) kept rows in (score descending, row ascending) order -- the boundary tie group keeps its lowest
+ *     rows; *count = their number; `row` includes the handle's row base, popc_db = popc(row);
+ *   - k == 0 is legal and returns no hits; nq == 1 gives gsim_db_search's rows, scores and popc_db, with which = 0;
+ *   - the output is byte-identical from run to run.
+ * Alpha and beta: every pair score must lie in [0, 1] (or be NaN) -- the streaming filter's range, and what makes acc_M <= M, so
+ * g <= 1, by the monotonicity of rounding.  Tanimoto always does.  Tversky is accepted with finite alpha >= 0, beta >= 0 and
+ * alpha + beta >= 1 (compared in double).  The bound itself rests on alpha >= 0 and beta >= 0 alone: common <= popc of either side, so
+ * both products are >= 0 in f32, a sum of non-negative terms rounds to something >= each term, hence den >= (float) common and
+ * fdiv_rn(common, den) <= 1 (a product that overflows to +inf gives score 0; den == 0 only with common == 0: NaN, counted as 0).
+ * Merging: `row` carries the row base and the order is the canonical one, so the blocks of several single-shard handles over slices
+ * of one table ({gsim_result_header; hits}, gsim_group_hit has gsim_hit's layout) merge with gsim_merge_host.
+ * Execution: on the handle's stream under the one-call-at-a-time rule; the pass is cut into launches of at most
+ * GSIM_GROUP_LAUNCH_PAIRS row x query pairs (read once per handle; unset: by the row width).  The call leaves the search state as it found
+ * it: a gsim_db_search before and after returns identical bytes; the back-off counters, the lanes and the pipeline slots are
+ * untouched.  Tables made by gsim_db_generate or gsim_db_attach_device_rows work as any other: no host copy is needed.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / queries / hits / count, nq == 0 or nq > GSIM_GROUP_MAX_QUERIES, an
+ * unknown mode or metric, the alpha / beta condition, rows wider than 4096 bits, a table of 2^32 rows or more.
+ * GSIM_ERR_STATE: a table not on a GPU, a multi-shard handle, a folded table.  GSIM_ERR_NOMEM as elsewhere. */
+#define GSIM_GROUP_MAX  0
+#define GSIM_GROUP_MIN  1
+#define GSIM_GROUP_MEAN 2
+#define GSIM_GROUP_MAX_QUERIES 1024u
+typedef struct { uint32_t row; float score; uint16_t which; uint16_t popc_db; } gsim_group_hit;  /* 12 bytes, gsim_hit's layout */
+typedef struct {
+    uint64_t queries;   /* M                                                                                                  */
+    uint64_t launches;  /* kernel launches: the scan's + the tail's (compaction, select; k > 8192: three for it) + `which`'s  */
+    uint64_t pairs;     /* rows x M scored                                                                                    */
+    double   scan_ms;   /* HIP events around the scan launches                                                                */
+    double   kernel_ms; /* scan + tail                                                                                        */
+    double   wall_ms;   /* the whole call, host clock                                                                         */
+} gsim_group_stats;
+int gsim_db_search_group(gsim_db* db, const uint32_t* queries, uint32_t nq, int mode, uint32_t k, float cutoff,
+                         int metric, float alpha, float beta,
+                         gsim_group_hit* hits, uint32_t* count, uint64_t* approx /* or NULL */,
+                         gsim_group_stats* stats /* or NULL */);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
