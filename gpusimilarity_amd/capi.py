@@ -29,6 +29,7 @@ GROUP_MAX = 0
 GROUP_MIN = 1
 GROUP_MEAN = 2
 GROUP_MAX_QUERIES = 1024
+LEADER_NONE = 0xFFFFFFFF
 
 HIT_DTYPE = np.dtype([("row", "<u4"), ("score", "<f4"), ("common", "<u2"), ("popc_db", "<u2")])
 GROUP_HIT_DTYPE = np.dtype([("row", "<u4"), ("score", "<f4"), ("which", "<u2"), ("popc_db", "<u2")])
@@ -72,6 +73,12 @@ class GsimGroupStats(C.Structure):
                 ("kernel_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
+class GsimLeaderStats(C.Structure):
+    _fields_ = [("leaders", C.c_uint64), ("rounds", C.c_uint64), ("launches", C.c_uint64), ("pairs", C.c_uint64),
+                ("assigned", C.c_uint64), ("kernel_ms", C.c_double), ("d2h_ms", C.c_double), ("wall_ms", C.c_double),
+                ("resolve_ms", C.c_double), ("compact_ms", C.c_double)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -95,6 +102,7 @@ EXPORTS = [
     "gsim_db_maxmin",
     "gsim_rowset_from_rows", "gsim_rowset_from_bitmap", "gsim_rowset_count", "gsim_rowset_rows", "gsim_rowset_destroy", "gsim_db_search_rows",
     "gsim_db_search_group",
+    "gsim_db_leader",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -190,6 +198,8 @@ def load():
                                           C.POINTER(GsimRowsetStats)]),
         "gsim_db_search_group": (C.c_int, [vp, u32p, C.c_uint32, C.c_int, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, vp, u32p, u64p,
                                            C.POINTER(GsimGroupStats)]),
+        "gsim_db_leader": (C.c_int, [vp, C.c_float, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, u32p, u32p, u32p,
+                                     C.POINTER(C.c_float), C.POINTER(GsimLeaderStats)]),
         "gsim_last_error": (C.c_char_p, []),
         "gsim_version": (C.c_char_p, []),
     }
@@ -435,6 +445,25 @@ class Table:
             stats.update({f: getattr(st, f) for f, _ in GsimMaxMinStats._fields_})
         out = (picks[:n.value].copy(), scores[:n.value].copy())
         return out + (row_score, nearest) if assign else out
+
+    def leader(self, cutoff, seeds=(), max_leaders=None, assign=True, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0):
+        """gsim_db_leader: leader (sphere-exclusion) clustering at `cutoff` -> (leaders uint32 (+ row base), leader_of uint32 [N],
+        row_score float32 [N], stats dict); leader_of holds positions in `leaders`, LEADER_NONE for a row left unassigned by the
+        cap.  max_leaders=None: no cap.  assign=False: leader_of and row_score are None (nothing but the leaders is copied back)."""
+        sd = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+        n = self.count()
+        cap = n if max_leaders is None else int(max_leaders)
+        leaders = np.zeros(max(min(cap, n), 1), dtype=np.uint32)
+        nl = C.c_uint32(0)
+        leader_of = row_score = None
+        if assign:
+            leader_of = np.empty(n, dtype=np.uint32)
+            row_score = np.empty(n, dtype=np.float32)
+        st = GsimLeaderStats()
+        check(self._L.gsim_db_leader(self._h, cutoff, _u32(sd) if len(sd) else None, len(sd), cap, metric, alpha, beta, _u32(leaders),
+                                     C.byref(nl), _u32(leader_of) if assign else None,
+                                     row_score.ctypes.data_as(C.POINTER(C.c_float)) if assign else None, C.byref(st)))
+        return leaders[:nl.value].copy(), leader_of, row_score, {f: getattr(st, f) for f, _ in GsimLeaderStats._fields_}
 
     def rowset(self, rows=None, bitmap=None, exclude=False) -> RowSet:
         """gsim_rowset_from_rows / _from_bitmap: `rows` are row indices including the row base (gsim_hit.row values), any order,

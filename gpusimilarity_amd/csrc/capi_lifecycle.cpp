@@ -71,6 +71,8 @@ gsim::Knobs read_knobs()
     k.join_stream_max_rows = env_value("GSIM_JOIN_STREAM_MAX_ROWS", k.join_stream_max_rows);
     k.subset_gather_max_permille = std::max(env_value("GSIM_SUBSET_GATHER_MAX_PERMILLE", k.subset_gather_max_permille), 0);
     if (const char* v = std::getenv("GSIM_GROUP_LAUNCH_PAIRS")) k.group_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
+    k.leader_round = std::min(std::max(env_value("GSIM_LEADER_ROUND", k.leader_round), 1), static_cast<int>(gsim::kLeaderMaxRound));
+    if (const char* v = std::getenv("GSIM_LEADER_LAUNCH_PAIRS")) k.leader_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
     return k;
 }
 

@@ -200,6 +200,10 @@ struct Knobs {
     long long group_launch_pairs = 0; // GSIM_GROUP_LAUNCH_PAIRS  a launch of gsim_db_search_group scores at most this many row x query
                                      // pairs (at least one chunk of rows); 0: by the row width (capi_group.cpp group_launch_pairs;
                                      // DESIGN.md section 13 has the rates and the arithmetic)
+    int leader_round = 256;          // GSIM_LEADER_ROUND        candidates per round of gsim_db_leader (1 ... kLeaderMaxRound); the result
+                                     // does not depend on it
+    long long leader_launch_pairs = 0; // GSIM_LEADER_LAUNCH_PAIRS  a launch of a gsim_db_leader pass scores at most this many row x leader
+                                     // pairs (at least one chunk of rows); 0: by the row width, as group_launch_pairs
 };
 
 ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll, bool ragged = true);
@@ -457,6 +461,48 @@ ScanGeometry group_geometry(uint64_t nrows, uint32_t W, int num_cus);
 hipError_t launch_group_scan(const ScanArgs& a, const ScanGeometry& g, const GroupArgs& ga, hipStream_t s);
 // Behind the tail: `which` of hits [h0, h1) of a block whose header carries flag 1 (device-side test; ga.c0 / c1 / first unused).
 hipError_t launch_group_which(const ScanArgs& a, const GroupArgs& ga, uint32_t row_base, void* block, uint32_t h0, uint32_t h1, hipStream_t s);
+
+// ---- leader (sphere-exclusion) clustering (gsim_leader.hip, gsim_db_leader) --------------------------------------------------------
+constexpr uint32_t kLeaderMaxRound = 4096; // largest GSIM_LEADER_ROUND (the resolve's leader mask: one 64-bit word per lane of a wave)
+// ctl words of a call (device memory; the host reads them once per round)
+constexpr uint32_t kLdrActive = 0;   // entries of the active list after the round's compaction (written by the compaction)
+constexpr uint32_t kLdrLeaders = 1;  // leaders made so far
+constexpr uint32_t kLdrRoundNl = 2;  // this round's leaders: the rows in the round buffer
+constexpr uint32_t kLdrRoundPos = 3; // ... and the position in `leaders` of the first of them
+constexpr uint32_t kLdrPairs = 4;    // (u64) leader x row scores evaluated
+constexpr uint32_t kLdrAssigned = 6; // (u64) rows with a leader (leaders included)
+constexpr uint32_t kLdrCtlWords = 8;
+struct LeaderArgs {
+    const void* rows;       // the whole table, nrows x W words
+    uint32_t W;
+    int metric;
+    float alpha, beta, cutoff;
+    uint32_t* leaders;      // max_leaders rows (without the row base); the seeds are there before the first round
+    uint32_t* leader_of;    // nrows: position in `leaders`, GSIM_LEADER_NONE while unassigned
+    float* row_score;       // nrows or nullptr
+    uint32_t* round_fp;     // the round buffer: round x W words, the round's leaders densely, in order ...
+    uint32_t* round_pop;    // ... and their popcounts
+    unsigned long long* cover; // round x ceil(round / 64) words: bit i of row j = candidate i (< j) covers candidate j
+    uint32_t* ctl;          // kLdrCtlWords words
+    uint32_t max_leaders;
+};
+// bytes of the order-preserving compaction's scratch for lists of up to n entries
+hipError_t leader_select_bytes(uint64_t n, size_t* bytes);
+// leaders[0 .. nseeds) (the seeds) get leader_of / row_score; list_out = every other row, ascending; ctl[kLdrActive] = their number
+// (leader_of: none everywhere, row_score: 0 everywhere before the call)
+hipError_t launch_leader_first_list(const LeaderArgs& a, void* tmp, size_t tmp_bytes, uint64_t nrows, uint32_t nseeds, uint32_t* list_out,
+                                    hipStream_t s);
+// A seed round: leaders[pos0 .. pos0 + nc) (seeds) become the round's leaders as they are.
+hipError_t launch_leader_seed_round(const LeaderArgs& a, uint32_t pos0, uint32_t nc, hipStream_t s);
+// A round's resolve over the candidates list[0 .. nc): the cover bits of the nc x nc candidate pairs (one launch), then one
+// workgroup that walks them in order, appends the new leaders, fills the round buffer and writes the candidates' outputs.
+hipError_t launch_leader_resolve(const LeaderArgs& a, const uint32_t* list, uint32_t nc, hipStream_t s);
+// One launch of a round's pass: list entries [e0, e1) against the round's leaders.  nt: non-temporal row loads.
+uint32_t leader_chunk_rows(uint32_t W);
+hipError_t launch_leader_pass(const LeaderArgs& a, const uint32_t* list, uint64_t e0, uint64_t e1, int num_cus, bool nt, hipStream_t s);
+// list_out = the entries of list_in[0 .. n) that still have no leader, in order; ctl[kLdrActive] = their number
+hipError_t launch_leader_compact(const LeaderArgs& a, void* tmp, size_t tmp_bytes, const uint32_t* list_in, uint64_t n, uint32_t* list_out,
+                                 hipStream_t s);
 
 hipError_t launch_generate(void* rows, uint64_t seed, int kind, uint64_t first_row, uint64_t nrows,
                            uint32_t W, hipStream_t s);

@@ -150,6 +150,21 @@ class FingerprintDB:
                 members[j].append(r)
         return picks, [(p,) + tuple(m) for p, m in zip(picks, members)]
 
+    def leader(self, cutoff: float, seeds=(), max_leaders=None, metric: int = capi.METRIC_TANIMOTO, alpha: float = 1.0,
+               beta: float = 1.0, assign: bool = False):
+        """Leader (sphere-exclusion) clustering (gsim_db_leader) -> the leaders, in the order they were made.  assign=True:
+        (leaders, clusters), one tuple per leader -- the leader first, then the rows it covers, ascending (the shape of butina());
+        rows a cap left unassigned are in no cluster."""
+        leaders, leader_of, _, _ = self._table.leader(float(cutoff), seeds, max_leaders, assign, metric, alpha, beta)
+        leaders = leaders.tolist()
+        if not assign:
+            return leaders
+        members = [[] for _ in leaders]
+        for r, j in enumerate(leader_of.tolist()):
+            if j != capi.LEADER_NONE and r != leaders[j]:
+                members[j].append(r)
+        return leaders, [(p,) + tuple(m) for p, m in zip(leaders, members)]
+
     def search_cpu(self, query, dbkey: str, max_return_count: int, similarity_cutoff: float
                    ) -> Tuple[List[bytes], List[bytes], List[float]]:
         """fingerprintdb_cuda.cpp:20-54 (cutoff ignored, approx not produced)."""

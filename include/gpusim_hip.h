@@ -541,6 +541,51 @@ int gsim_db_search_group(gsim_db* db, const uint32_t* queries, uint32_t nq, int 
                          gsim_group_hit* hits, uint32_t* count, uint64_t* approx /* or NULL */,
                          gsim_group_stats* stats /* or NULL */);
 
+/* ---- leader (sphere-exclusion) clustering ----------------------------------------------------------------------------------------- */
+/* gsim_db_leader clusters a single-shard, unfolded handle with N rows by the leader rule (sphere exclusion; RDKit's LeaderPicker; no
+ * counterpart in the reference): it takes a radius, needs no neighbour graph, and uses O(N) memory.
+ * THE RULE:
+ *   - pair score: score(p, i) is bit for bit the `score` gsim_db_search returns for query = row p against row i; NaN (0 / 0) is never
+ *     >= cutoff.  Metrics: GSIM_METRIC_TANIMOTO, and GSIM_METRIC_TVERSKY with alpha == beta, finite and >= 0 (gsim_db_maxmin's: these
+ *     are symmetric bit for bit).  cutoff is in (0, 1];
+ *   - seeds: leaders 0 .. nseeds-1 are the seeds (rows including the row base), in the order given -- leaders even where one covers
+ *     another (RDKit's firstPicks), each its own cluster's leader;
+ *   - the walk: every non-seed row i is then taken in ascending order.  Row i is COVERED if some leader p made so far has
+ *     score(p, i) >= cutoff, and then belongs to the earliest such leader, by position in `leaders`; a row that is not covered
+ *     becomes the next leader.  A leader belongs to itself by definition, not by score: every all-zero row is the leader of a
+ *     singleton; a duplicate of a leader is covered by it, 1.0;
+ *   - the cap: max_leaders >= 1, >= nseeds and <= N (N: no cap).  The walk stops right after leader number max_leaders has been made
+ *     and has covered its rows; rows that nothing covers by then stay unassigned;
+ *   - leaders[0 .. *nleaders): rows plus the row base (capacity: max_leaders); leader_of[N] (or NULL): the position in `leaders` of
+ *     the row's leader, GSIM_LEADER_NONE when unassigned; row_score[N] (or NULL): score(leader, row) for a covered row, 1.0 for a
+ *     leader, 0.0 for an unassigned row;
+ *   - the output is byte-identical from run to run, and does not depend on GSIM_LEADER_ROUND (candidates per round) or
+ *     GSIM_LEADER_LAUNCH_PAIRS (how a pass is cut into launches); both are read once per handle.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / leaders / nleaders (NULL seeds with nseeds > 0), cutoff outside (0, 1]
+ * or NaN, an unknown metric, asymmetric weights or weights that are negative or not finite, a seed outside [row_base, row_base + N) or
+ * repeated, max_leaders outside [max(1, nseeds), N], N >= 2^32, rows wider than 4096 bits.  N == 0 does nothing and returns GSIM_OK.
+ * GSIM_ERR_STATE: a table not on a GPU, a multi-shard handle, a folded table.  GSIM_ERR_NOMEM as elsewhere.
+ * Execution: on the handle's stream under the one-call-at-a-time rule; the search state is left as it was found (back-offs, lanes and
+ * slots untouched); device memory for the call (12 B per row, 16 B with row_score, and the compaction's scratch) is allocated and
+ * freed by the call.  The host reads one small control block per round. */
+#define GSIM_LEADER_NONE 0xFFFFFFFFu
+typedef struct {
+    uint64_t leaders;   /* leaders made (seeds included)                                                                       */
+    uint64_t rounds;    /* rounds: seed rounds + candidate rounds                                                              */
+    uint64_t launches;  /* kernel launches of the call's own kernels; a compaction counts as one                               */
+    uint64_t pairs;     /* (leader, row) scores the rule needed: per listed row up to its first covering leader, plus the      */
+                        /* candidate pairs i < j of every round's resolve                                                      */
+    uint64_t assigned;  /* rows with a leader, the leaders among them                                                          */
+    double kernel_ms;   /* HIP events around every round's launches, summed                                                    */
+    double d2h_ms;      /* outputs to the host                                                                                 */
+    double wall_ms;     /* the whole call, host clock; wall_ms - kernel_ms - d2h_ms: the per-round control reads and set-up    */
+    double resolve_ms;  /* of kernel_ms: the rounds' resolves (and seed rounds' copies)                                        */
+    double compact_ms;  /* of kernel_ms: the rounds' compactions                                                               */
+} gsim_leader_stats;
+int gsim_db_leader(gsim_db* db, float cutoff, const uint32_t* seeds, uint32_t nseeds, uint32_t max_leaders, int metric, float alpha,
+                   float beta, uint32_t* leaders, uint32_t* nleaders, uint32_t* leader_of /* or NULL */, float* row_score /* or NULL */,
+                   gsim_leader_stats* stats /* or NULL */);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
