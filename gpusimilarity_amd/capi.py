@@ -30,6 +30,7 @@ GROUP_MIN = 1
 GROUP_MEAN = 2
 GROUP_MAX_QUERIES = 1024
 LEADER_NONE = 0xFFFFFFFF
+KNN_MAX_K = 128
 
 HIT_DTYPE = np.dtype([("row", "<u4"), ("score", "<f4"), ("common", "<u2"), ("popc_db", "<u2")])
 GROUP_HIT_DTYPE = np.dtype([("row", "<u4"), ("score", "<f4"), ("which", "<u2"), ("popc_db", "<u2")])
@@ -79,6 +80,12 @@ class GsimLeaderStats(C.Structure):
                 ("resolve_ms", C.c_double), ("compact_ms", C.c_double)]
 
 
+class GsimKnnStats(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("launches", C.c_uint64), ("pairs", C.c_uint64), ("inserts", C.c_uint64),
+                ("entries", C.c_uint64), ("kernel_ms", C.c_double), ("csr_ms", C.c_double), ("d2h_ms", C.c_double),
+                ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -103,6 +110,7 @@ EXPORTS = [
     "gsim_rowset_from_rows", "gsim_rowset_from_bitmap", "gsim_rowset_count", "gsim_rowset_rows", "gsim_rowset_destroy", "gsim_db_search_rows",
     "gsim_db_search_group",
     "gsim_db_leader",
+    "gsim_db_knn", "gsim_graph_get_knn_stats",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -198,6 +206,8 @@ def load():
                                           C.POINTER(GsimRowsetStats)]),
         "gsim_db_search_group": (C.c_int, [vp, u32p, C.c_uint32, C.c_int, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, vp, u32p, u64p,
                                            C.POINTER(GsimGroupStats)]),
+        "gsim_db_knn": (C.c_int, [vp, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
+        "gsim_graph_get_knn_stats": (C.c_int, [vp, C.POINTER(GsimKnnStats)]),
         "gsim_db_leader": (C.c_int, [vp, C.c_float, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, u32p, u32p, u32p,
                                      C.POINTER(C.c_float), C.POINTER(GsimLeaderStats)]),
         "gsim_last_error": (C.c_char_p, []),
@@ -383,6 +393,17 @@ class Table:
         g = C.c_void_p()
         check(self._L.gsim_db_neighbors(self._h, cutoff, metric, alpha, beta, row_begin, row_end, C.byref(g)))
         return self._take_graph(g, stats, GsimGraphStats, self._L.gsim_graph_get_stats)
+
+    def knn(self, k, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, row_begin=0, row_end=None, stats=None):
+        """gsim_db_knn: for the rows i of [row_begin, row_end), the k most similar other rows j with
+        score(query = row i, row j) >= cutoff -- gsim_db_search(row i, k + 1, cutoff) minus row i, cut to k
+        -> CSR (indptr uint64 [n + 1], indices uint32 (+ row base), scores float32), each list by (score descending, row ascending).
+        `stats`: a dict that receives the call's gsim_knn_stats."""
+        if row_end is None:
+            row_end = self.count()
+        g = C.c_void_p()
+        check(self._L.gsim_db_knn(self._h, k, cutoff, metric, alpha, beta, row_begin, row_end, C.byref(g)))
+        return self._take_graph(g, stats, GsimKnnStats, self._L.gsim_graph_get_knn_stats)
 
     def _take_graph(self, g, stats, stats_type, get_stats):
         """A gsim_graph -> (indptr, indices, scores) (+ its stats into the dict `stats`); the graph is destroyed."""

@@ -39,7 +39,7 @@ int join(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, float cutof
 {
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t N = s.nrows;
-    g->is_join = true;
+    g->kind = gsim_graph::Kind::kJoin;
     g->indptr.assign(nl + 1, 0);
     if (nl == 0 || N == 0) {
         g->join.wall_ms = g->stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -73,6 +73,7 @@ gsim::Knobs read_knobs()
     if (const char* v = std::getenv("GSIM_GROUP_LAUNCH_PAIRS")) k.group_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
     k.leader_round = std::min(std::max(env_value("GSIM_LEADER_ROUND", k.leader_round), 1), static_cast<int>(gsim::kLeaderMaxRound));
     if (const char* v = std::getenv("GSIM_LEADER_LAUNCH_PAIRS")) k.leader_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
+    if (const char* v = std::getenv("GSIM_KNN_LAUNCH_PAIRS")) k.knn_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
     return k;
 }
 

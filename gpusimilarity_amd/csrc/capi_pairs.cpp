@@ -18,10 +18,15 @@ constexpr double kNbrEmitCost = 150.0;
 // Consecutive tile rows share a launch while their tiles fit the budget; a tile row longer than the budget is cut into
 // column pieces.  Triangle: tile row r holds the tiles r .. nct - 1 (the grid of a group starts at its first row's diagonal;
 // the tiles left of a later row's diagonal return at once).
-std::vector<NbrLaunch> plan_launches(uint64_t nlt, uint64_t nct, bool tri, uint32_t WP)
+uint64_t launch_tile_budget(uint32_t WP)
 {
     const double per_tile = static_cast<double>(gsim::kNbrTile) * gsim::kNbrTile * (2.0 * (WP + 8) + kNbrEmitCost);
-    const uint64_t max_tiles = std::max<uint64_t>(1, static_cast<uint64_t>(kNbrLaunchBudget / per_tile));
+    return std::max<uint64_t>(1, static_cast<uint64_t>(kNbrLaunchBudget / per_tile));
+}
+
+std::vector<NbrLaunch> plan_launches(uint64_t nlt, uint64_t nct, bool tri, uint32_t WP)
+{
+    const uint64_t max_tiles = launch_tile_budget(WP);
     std::vector<NbrLaunch> out;
     uint64_t rt = 0;
     while (rt < nlt) {
@@ -214,8 +219,16 @@ int gsim_graph_get_stats(const gsim_graph* g, gsim_graph_stats* out)
 int gsim_graph_get_join_stats(const gsim_graph* g, gsim_join_stats* out)
 {
     if (!g || !out) return fail(GSIM_ERR_INVALID, "NULL argument");
-    if (!g->is_join) return fail(GSIM_ERR_INVALID, "not the result of a join");
+    if (g->kind != gsim_graph::Kind::kJoin) return fail(GSIM_ERR_INVALID, "not the result of a join");
     *out = g->join;
+    return GSIM_OK;
+}
+
+int gsim_graph_get_knn_stats(const gsim_graph* g, gsim_knn_stats* out)
+{
+    if (!g || !out) return fail(GSIM_ERR_INVALID, "NULL argument");
+    if (g->kind != gsim_graph::Kind::kKnn) return fail(GSIM_ERR_INVALID, "not the result of gsim_db_knn");
+    *out = g->knn;
     return GSIM_OK;
 }
 

@@ -12,8 +12,10 @@ struct gsim_graph {
     std::vector<uint32_t> indices;
     std::vector<float> scores;
     gsim_graph_stats stats{};
-    bool is_join = false; // made by gsim_db_join / gsim_db_join_queries: `join` is filled
-    gsim_join_stats join{};
+    enum class Kind : uint8_t { kNeighbors, kJoin, kKnn }; // who made it: which of the *_get_*_stats accessors answers for it
+    Kind kind = Kind::kNeighbors;
+    gsim_join_stats join{}; // kJoin (gsim_db_join / gsim_db_join_queries)
+    gsim_knn_stats knn{};   // kKnn (gsim_db_knn, capi_knn.cpp)
 };
 
 namespace gsim_host
@@ -22,6 +24,8 @@ namespace gsim_host
 struct NbrLaunch {
     uint32_t rt0, nrt, ct0, nct;
 };
+// Tiles (kNbrTile x kNbrTile pairs of rows of WP words) one launch may cover: the work budget over a tile's price.
+uint64_t launch_tile_budget(uint32_t WP);
 // Tile launches of a call over nlt tile rows x nct tile columns (rows of WP words), each within the work budget.
 std::vector<NbrLaunch> plan_launches(uint64_t nlt, uint64_t nct, bool tri, uint32_t WP);
 

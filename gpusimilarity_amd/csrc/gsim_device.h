@@ -204,6 +204,9 @@ struct Knobs {
                                      // does not depend on it
     long long leader_launch_pairs = 0; // GSIM_LEADER_LAUNCH_PAIRS  a launch of a gsim_db_leader pass scores at most this many row x leader
                                      // pairs (at least one chunk of rows); 0: by the row width, as group_launch_pairs
+    long long knn_launch_pairs = 0;  // GSIM_KNN_LAUNCH_PAIRS    a launch of gsim_db_knn's fold kernel scores at most this many owner x candidate
+                                     // pairs (at least one column tile of 256 candidates); 0: by the row width, with the tile
+                                     // kernel's pricing and budget (capi_knn.cpp).  The result does not depend on it
 };
 
 ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll, bool ragged = true);
@@ -369,6 +372,38 @@ hipError_t nbr_sort_bytes(uint64_t n, uint32_t end_bit, size_t* bytes);
 hipError_t launch_nbr_csr(void* tmp, size_t tmp_bytes, const unsigned long long* keys, const float* vals, unsigned long long* keys_sorted,
                           float* vals_sorted, uint64_t n, uint32_t end_bit, uint64_t nrows_out, uint32_t row_base, uint64_t* indptr,
                           uint32_t* indices, hipStream_t s);
+
+// ---- exact k-nearest-neighbour lists of the table's own rows (gsim_knn.hip, gsim_db_knn) ----------------------------------
+constexpr int kKnnTile = 256;   // owner rows of one workgroup
+constexpr int kKnnBlock = 256;  // 4 waves, 64 owners each, all walking the same candidates
+constexpr uint32_t kKnnColTile = 256; // launches are cut at multiples of this many candidate rows
+struct KnnEntry {
+    float score;
+    uint32_t row; // table row, without the row base
+};
+struct KnnArgs {
+    const uint32_t* rows;        // nrows x WP words, 16-byte aligned (the table itself when W == WP, else a zero-padded copy)
+    const uint32_t* pop;         // popc of every row
+    uint64_t nrows;
+    uint64_t row_begin, row_end; // the owners: list o belongs to table row row_begin + o
+    uint32_t WP;                 // words per row as the kernel reads them (4, 8, ... 128)
+    uint32_t k;                  // 1 ... GSIM_KNN_MAX_K
+    int metric;
+    float alpha, beta, cutoff;
+    KnnEntry* lists;             // (row_end - row_begin) x k entries, each list in (score descending, row ascending) order
+    uint32_t* len;               // entries held per list (zero before the first launch)
+    unsigned long long* inserts; // list insertions made so far
+    unsigned long long* clk;     // this launch's {s_memtime, wall clock} at the start and end of its first workgroup (nullptr: none)
+};
+// Owner tiles ot0 .. ot0 + not_ - 1 (tile t = owners t * kKnnTile ..) fold the candidate rows [c0, c1) into their lists.  The
+// pieces of the same owners must be launched in ascending column order on one stream.
+hipError_t launch_knn_fold(const KnnArgs& a, uint32_t ot0, uint32_t not_, uint64_t c0, uint64_t c1, hipStream_t s);
+// indptr[0 .. n) = exclusive prefix sums of len[0 .. n) (n = lists + 1 with len[lists] = 0: indptr[lists] is the total)
+hipError_t knn_scan_bytes(uint64_t n, size_t* bytes);
+hipError_t launch_knn_offsets(void* tmp, size_t tmp_bytes, const uint32_t* len, uint64_t n, uint64_t* indptr, hipStream_t s);
+// every held entry to its place: indices (+ row_base) and scores
+hipError_t launch_knn_compact(const KnnEntry* lists, const uint32_t* len, const uint64_t* indptr, uint64_t nown, uint32_t k, uint32_t row_base,
+                              uint32_t* indices, float* scores, hipStream_t s);
 
 // ---- MaxMin diversity picking (gsim_maxmin.hip, gsim_db_maxmin) ----------------------------------------------------------
 // ctl words of a call (zeroed by the host before the first pass; the ticket on its own 128-byte line)

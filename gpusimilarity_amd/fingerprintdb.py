@@ -113,6 +113,12 @@ class FingerprintDB:
         [row_begin, row_end), each row's list sorted by column.  No counterpart in the reference."""
         return self._table.neighbors(float(cutoff), metric, alpha, beta, row_begin, row_end)
 
+    def knn(self, k: int, cutoff: float, metric: int = capi.METRIC_TANIMOTO, alpha: float = 1.0, beta: float = 1.0,
+            row_begin: int = 0, row_end=None):
+        """Each row's k most similar other rows at or above `cutoff` (gsim_db_knn) -> CSR (indptr, indices, scores) for the rows
+        [row_begin, row_end), each row's list by (score descending, row ascending).  No counterpart in the reference."""
+        return self._table.knn(int(k), float(cutoff), metric, alpha, beta, row_begin, row_end)
+
     def join(self, left, cutoff: float, metric: int = capi.METRIC_TANIMOTO, alpha: float = 1.0, beta: float = 1.0,
              order: int = capi.JOIN_BY_ROW, row_begin: int = 0, row_end=None):
         """Every row of this table at or above `cutoff`, per left row (gsim_db_join / gsim_db_join_queries) -> CSR

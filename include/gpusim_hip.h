@@ -586,6 +586,59 @@ int gsim_db_leader(gsim_db* db, float cutoff, const uint32_t* seeds, uint32_t ns
                    float beta, uint32_t* leaders, uint32_t* nleaders, uint32_t* leader_of /* or NULL */, float* row_score /* or NULL */,
                    gsim_leader_stats* stats /* or NULL */);
 
+/* ---- exact k-nearest-neighbour graphs: each row's k most similar other rows ------------------------------------------------------ */
+/* gsim_db_knn: for every row i of [row_begin, row_end) of a single-shard, unfolded handle with N rows, its k most similar OTHER rows
+ * (no counterpart in the reference).  Unlike a threshold graph (gsim_db_neighbors) the output is bounded by N x k whatever the data
+ * looks like.  The result is a gsim_graph: gsim_graph_shape / _copy / _destroy work on it, gsim_graph_get_stats reports the call's
+ * totals (fold launches, their time in tile_ms, entries in pairs), gsim_graph_get_knn_stats the details; gsim_graph_get_join_stats
+ * returns GSIM_ERR_INVALID for it.
+ * THE RESULT RULE:
+ *   - list i - row_begin is exactly the hits of gsim_db_search(query = row i, k + 1, cutoff, metric, alpha, beta) with the hit whose
+ *     row is i removed, cut to the first k.  Written out: it holds rows j != i with score(query = row i, row j) >= cutoff, where the
+ *     score is bit for bit what gsim_db_search returns for that pair (a = popc(row i), b = popc(row j)); its order is (score
+ *     descending, row ascending); the boundary tie group keeps its lowest rows; it is shorter than k when fewer rows qualify;
+ *   - NaN (0 / 0) is never >= cutoff: an all-zero row has an empty list and is in nobody's list.  Duplicates of row i are listed at
+ *     1.0, row i itself never is;
+ *   - cutoff must be in (0, 1], as for neighbours and joins.  The smallest positive float means "every row with a non-zero score": a
+ *     row that shares no bit with row i is never a neighbour;
+ *   - metrics: GSIM_METRIC_TANIMOTO, and GSIM_METRIC_TVERSKY with any finite alpha >= 0, beta >= 0 -- asymmetric included, as in
+ *     gsim_db_join: the owner row i is the query and every (i, j) is computed from i's side, so no symmetry is needed;
+ *   - rows of up to 4096 bits; 1 <= k <= GSIM_KNN_MAX_K;
+ *   - indices = row + the handle's row base (as gsim_hit.row); indptr has row_end - row_begin + 1 entries;
+ *   - the output is byte-identical from run to run and does not depend on how the work is cut into launches
+ *     (GSIM_KNN_LAUNCH_PAIRS, read once per handle).  Pieces of a table (ranges), concatenated, give the full call's
+ *     lists -- and ranges are how a large table is done in pieces: the call allocates about (row_end - row_begin) x k x 8 bytes for
+ *     the lists plus a few words per owner row, at most as much again for the compacted CSR while it is copied out, and -- as
+ *     gsim_db_neighbors -- 4 bytes per TABLE row (popcounts) and a zero-padded copy of the table where its rows are not 128, 256,
+ *     512, 1024, 2048 or 4096 bits wide.  All of it is freed by the call.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / out, k == 0 or k > GSIM_KNN_MAX_K, cutoff outside (0, 1] or NaN,
+ * unknown metric, Tversky alpha / beta negative or not finite, row_begin > row_end or row_end past the count, rows wider than 4096
+ * bits, a table of 2^32 rows or more.  *out is cleared on failure.  GSIM_ERR_STATE: a table not on a GPU, a multi-shard handle, a
+ * folded table.  GSIM_ERR_NOMEM: the call's device memory cannot be had; nothing is truncated, nothing leaked.  row_begin == row_end
+ * gives an empty graph (indptr = {0}) and GSIM_OK; N == 1 gives one empty list.
+ * Execution: on the handle's stream under the one-call-at-a-time rule; the search state is left as it was found (a gsim_db_search
+ * before and after returns identical bytes; back-off counters, lanes and slots untouched).  Tables from gsim_db_generate and
+ * gsim_db_attach_device_rows work; no host copy is needed.  The work is (row_end - row_begin) x N pair scores, cut into launches of a
+ * bounded length; owner rows are spread over the device 256 to a workgroup and every workgroup walks all N candidate rows itself, so a
+ * range of a few hundred rows against a very long table uses a small part of the device (its columns are not split over workgroups;
+ * for such a range gsim_db_search with the rows as queries at k + 1 is the faster route -- DESIGN.md section 15 has the crossover). */
+#define GSIM_KNN_MAX_K 128u
+typedef struct {
+    uint64_t rows;      /* owner rows of the call (row_end - row_begin)                                  */
+    uint64_t launches;  /* launches of the fold kernel                                                   */
+    uint64_t pairs;     /* owner x candidate pairs scored                                                */
+    uint64_t inserts;   /* list insertions made (the kernel's slow path)                                 */
+    uint64_t entries;   /* entries listed (nnz)                                                          */
+    double kernel_ms;   /* HIP events on the handle's stream around all fold launches                    */
+    double csr_ms;      /* offsets + compaction on the device                                            */
+    double d2h_ms;      /* CSR into host memory                                                          */
+    double wall_ms;     /* the whole call, host clock                                                    */
+    double clock_mhz;   /* shader clock the fold kernel ran at (as gsim_graph_stats.clock_mhz)           */
+} gsim_knn_stats;
+int gsim_db_knn(gsim_db* db, uint32_t k, float cutoff, int metric, float alpha, float beta,
+                uint64_t row_begin, uint64_t row_end, gsim_graph** out);
+int gsim_graph_get_knn_stats(const gsim_graph* g, gsim_knn_stats* out); /* GSIM_ERR_INVALID for any other graph */
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
