@@ -31,6 +31,8 @@ GROUP_MEAN = 2
 GROUP_MAX_QUERIES = 1024
 LEADER_NONE = 0xFFFFFFFF
 KNN_MAX_K = 128
+HIST_MAX_EDGES = 128
+HIST_EXCLUDE_SELF = 1
 
 HIT_DTYPE = np.dtype([("row", "<u4"), ("score", "<f4"), ("common", "<u2"), ("popc_db", "<u2")])
 GROUP_HIT_DTYPE = np.dtype([("row", "<u4"), ("score", "<f4"), ("which", "<u2"), ("popc_db", "<u2")])
@@ -86,6 +88,12 @@ class GsimKnnStats(C.Structure):
                 ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
 
 
+class GsimHistStats(C.Structure):
+    _fields_ = [("left_rows", C.c_uint64), ("rows_streamed", C.c_uint64), ("rows_tiled", C.c_uint64), ("stream_launches", C.c_uint64),
+                ("tile_launches", C.c_uint64), ("pairs", C.c_uint64), ("stream_ms", C.c_double), ("tile_ms", C.c_double),
+                ("reduce_ms", C.c_double), ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -111,6 +119,7 @@ EXPORTS = [
     "gsim_db_search_group",
     "gsim_db_leader",
     "gsim_db_knn", "gsim_graph_get_knn_stats",
+    "gsim_db_histogram_queries", "gsim_db_histogram",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -208,6 +217,10 @@ def load():
                                            C.POINTER(GsimGroupStats)]),
         "gsim_db_knn": (C.c_int, [vp, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
         "gsim_graph_get_knn_stats": (C.c_int, [vp, C.POINTER(GsimKnnStats)]),
+        "gsim_db_histogram_queries": (C.c_int, [vp, u32p, C.c_uint64, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.c_float, C.c_float, u64p, u64p,
+                                                C.POINTER(GsimHistStats)]),
+        "gsim_db_histogram": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.c_float, C.c_float,
+                                        C.c_uint32, u64p, u64p, C.POINTER(GsimHistStats)]),
         "gsim_db_leader": (C.c_int, [vp, C.c_float, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, u32p, u32p, u32p,
                                      C.POINTER(C.c_float), C.POINTER(GsimLeaderStats)]),
         "gsim_last_error": (C.c_char_p, []),
@@ -443,6 +456,44 @@ class Table:
             check(self._L.gsim_db_join_queries(self._h, _u32(q) if len(q) else None, len(q), cutoff, metric, alpha, beta, order,
                                                C.byref(g)))
         return self._take_graph(g, stats, GsimJoinStats, self._L.gsim_graph_get_join_stats)
+
+    def histogram(self, left, edges, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, row_begin=0, row_end=None, exclude_self=False,
+                  per_row=True, total=True, stats=None):
+        """gsim_db_histogram / gsim_db_histogram_queries: for every left row, the number of rows j of THIS table in each bin of
+        score(query = left row, row j), bin(s) = the number of `edges` e with s >= e -> (hist uint64 [nl, len(edges) + 1] or None,
+        total uint64 [len(edges) + 1] or None).  `left`: a Table on the same device (its rows [row_begin, row_end)) or a (nq, W) /
+        (W,) uint32 array.  `exclude_self` (only with left being this table): the pair (row i, row i) is not counted.
+        `per_row` / `total`: which of the two outputs to make.  `stats`: a dict that receives the call's gsim_hist_stats."""
+        e = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1)
+        nb = len(e) + 1
+        ep = e.ctypes.data_as(C.POINTER(C.c_float)) if len(e) else None
+        u64p = C.POINTER(C.c_uint64)
+        st = GsimHistStats()
+        if isinstance(left, Table):
+            if row_end is None:
+                row_end = left.count()
+            nl = max(row_end - row_begin, 0)
+        else:
+            q = np.ascontiguousarray(left, dtype=np.uint32).reshape(-1, self.W)
+            if row_end is None:
+                row_end = q.shape[0]
+            q = np.ascontiguousarray(q[row_begin:row_end])
+            nl = len(q)
+        hist = np.zeros((nl, nb), dtype=np.uint64) if per_row else None
+        tot = np.zeros(nb, dtype=np.uint64) if total else None
+        hp = hist.ctypes.data_as(u64p) if per_row else None
+        tp = tot.ctypes.data_as(u64p) if total else None
+        if isinstance(left, Table):
+            check(self._L.gsim_db_histogram(self._h, left._h, row_begin, row_end, ep, len(e), metric, alpha, beta,
+                                            HIST_EXCLUDE_SELF if exclude_self else 0, hp, tp, C.byref(st)))
+        else:
+            if exclude_self:
+                raise GsimError(-1, "exclude_self needs the table itself as the left side")
+            check(self._L.gsim_db_histogram_queries(self._h, _u32(q) if nl else None, nl, ep, len(e), metric, alpha, beta, hp, tp,
+                                                    C.byref(st)))
+        if stats is not None:
+            stats.update({f: getattr(st, f) for f, _ in GsimHistStats._fields_})
+        return hist, tot
 
     def maxmin(self, npicks, seeds=(), metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, max_score=1.0, assign=False, stats=None):
         """gsim_db_maxmin: MaxMin diversity picking, one pass over the table per pick -> (picks uint32 (+ row base),

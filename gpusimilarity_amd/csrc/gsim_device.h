@@ -207,6 +207,14 @@ struct Knobs {
     long long knn_launch_pairs = 0;  // GSIM_KNN_LAUNCH_PAIRS    a launch of gsim_db_knn's fold kernel scores at most this many owner x candidate
                                      // pairs (at least one column tile of 256 candidates); 0: by the row width, with the tile
                                      // kernel's pricing and budget (capi_knn.cpp).  The result does not depend on it
+    int hist_stream_max_rows = 32;   // GSIM_HIST_STREAM_MAX_ROWS  histogram calls of at most this many left rows stream the table once per left
+                                     // row, larger ones take the owner-tile kernel (0: always tiles; DESIGN.md section 16 has the crossover:
+                                     // between 32 and 64 left rows at 1 M and at 100 M x 1024-bit rows)
+    long long hist_launch_pairs = 0; // GSIM_HIST_LAUNCH_PAIRS   a launch of either histogram kernel scores at most this many left x table
+                                     // pairs (at least one 256 x 256 tile / 64 table rows); 0: by the row width, as knn_launch_pairs.
+                                     // The result does not depend on it
+    int hist_naive_add = 0;          // GSIM_HIST_NAIVE_ADD      1: the streaming kernel adds with one LDS atomic per lane instead of one per
+                                     // distinct bin of the wave (for timing the two forms; same counts)
 };
 
 ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll, bool ragged = true);
@@ -404,6 +412,54 @@ hipError_t launch_knn_offsets(void* tmp, size_t tmp_bytes, const uint32_t* len, 
 // every held entry to its place: indices (+ row_base) and scores
 hipError_t launch_knn_compact(const KnnEntry* lists, const uint32_t* len, const uint64_t* indptr, uint64_t nown, uint32_t k, uint32_t row_base,
                               uint32_t* indices, float* scores, hipStream_t s);
+
+// ---- similarity histograms (gsim_hist.hip, gsim_db_histogram / gsim_db_histogram_queries) ----------------------------------
+constexpr int kHistTile = 256;           // owner (left) rows of one workgroup of the owner-tile kernel
+constexpr int kHistBlock = 256;          // 4 waves, 64 owners each, all walking the same candidates
+constexpr uint32_t kHistColTile = 256;   // column chunks and launch cuts are multiples of this many table rows
+constexpr uint32_t kHistMaxChunk = 65280; // table rows one workgroup counts before it flushes: < 2^16, two counters share an LDS word
+constexpr uint32_t kHistCoarse = 256;    // cells of the coarse bin table: cell t holds bin(t / 256), the bin search starts there
+struct HistBins {
+    const float* edges;          // nedges floats, strictly ascending, edges[0] > 0
+    const uint8_t* coarse;       // kHistCoarse bytes: coarse[t] = number of edges <= t / kHistCoarse
+    uint32_t nedges;             // 1 ... GSIM_HIST_MAX_EDGES
+    float cut_lo;                // valu_cutoff_lo(edges[0]) when edges[0] <= 1, else 0: a pair with c < cut_lo x den is in bin 0
+};
+// words per owner of the tile kernel's LDS counters (16 bits each, two to a word; odd, so that the 64 lanes' rows start on
+// different banks) and the dynamic LDS of a workgroup
+uint32_t hist_tile_stride(uint32_t nedges);
+size_t hist_tile_lds_bytes(uint32_t nedges);
+struct HistTileArgs {
+    const uint32_t* rows;        // the table: nrows x WP words, 16-byte aligned (zero-padded copy unless W == WP)
+    const uint32_t* pop;         // popc of every table row
+    const uint32_t* lrows;       // the left rows: nl x WP words, 16-byte aligned
+    uint64_t nrows, nl;
+    uint32_t WP;
+    int metric;
+    float alpha, beta;
+    uint64_t self0;              // GSIM_HIST_EXCLUDE_SELF: left row o is table row self0 + o, that pair is skipped; ~0: nothing is
+    HistBins bins;
+    unsigned long long* hist;    // nl x (nedges + 1) counters
+    unsigned long long* clk;     // as KnnArgs.clk
+};
+// Owner tiles ot0 .. ot0 + not_ - 1 against the table rows [c0, c1), `chunk` (a multiple of kHistColTile, <= kHistMaxChunk) to a
+// workgroup: grid = owner tiles x column chunks, every workgroup adds its counts into hist with atomics.
+hipError_t launch_hist_tiles(const HistTileArgs& a, uint32_t ot0, uint32_t not_, uint64_t c0, uint64_t c1, uint32_t chunk, hipStream_t s);
+struct HistStreamArgs {
+    const void* rows;            // the whole table, nrows x W words
+    uint32_t W;
+    int metric;
+    float alpha, beta;
+    const uint32_t* left;        // the left rows, W words each
+    uint64_t self0;              // as HistTileArgs.self0
+    HistBins bins;
+    unsigned long long* hist;
+    int naive;                   // hist_naive_add
+};
+// One launch of left row l's pass: table rows [r0, r0 + nrows), g = maxmin_geometry(nrows, ...), r0 a multiple of 64.
+hipError_t launch_hist_pass(const HistStreamArgs& h, const ScanGeometry& g, uint64_t r0, uint64_t nrows, uint32_t l, hipStream_t s);
+// total[b] = sum over the nl rows of hist[i][b] (total is zeroed by the launch)
+hipError_t launch_hist_total(const unsigned long long* hist, uint64_t nl, uint32_t nbins, unsigned long long* total, hipStream_t s);
 
 // ---- MaxMin diversity picking (gsim_maxmin.hip, gsim_db_maxmin) ----------------------------------------------------------
 // ctl words of a call (zeroed by the host before the first pass; the ticket on its own 128-byte line)

@@ -639,6 +639,70 @@ int gsim_db_knn(gsim_db* db, uint32_t k, float cutoff, int metric, float alpha, 
                 uint64_t row_begin, uint64_t row_end, gsim_graph** out);
 int gsim_graph_get_knn_stats(const gsim_graph* g, gsim_knn_stats* out); /* GSIM_ERR_INVALID for any other graph */
 
+/* ---- similarity histograms and hit counts: how many table rows score in each bin, per left row ------------------------------------ */
+/* gsim_db_histogram_queries / gsim_db_histogram: for each of nl LEFT rows -- the nq fingerprints at `queries` (host memory, nq x
+ * fp_bits / 32 words), or the rows [lrow_begin, lrow_end) of a handle `left` resident on the same device (left == db is allowed) --
+ * the histogram of its scores against ALL N rows of the table `db`, over the bins that `edges` cut (chemfp's count_tanimoto_hits at
+ * several thresholds in one pass; the sizes of a gsim_db_join / gsim_db_neighbors result before it is made; the similarity
+ * distribution of one library against another).  No counterpart in the reference.  The output is nl x (nedges + 1) counters whatever
+ * the data looks like.
+ * THE RESULT RULE:
+ *   - pair score: s(i, j) is bit for bit the `score` gsim_db_search returns for query = left row i against table row j
+ *     (a = popc(left row), b = popc(table row)), as in gsim_db_join;
+ *   - metrics: GSIM_METRIC_TANIMOTO, and GSIM_METRIC_TVERSKY with any finite alpha >= 0, beta >= 0 -- asymmetric included: every pair
+ *     is computed from the left row's side, so no symmetry is needed;
+ *   - edges[0 .. nedges) are finite, strictly ascending, edges[0] > 0; 1 <= nedges <= GSIM_HIST_MAX_EDGES.  Edges above 1 are legal
+ *     (no score reaches them: their bins stay empty);
+ *   - bin(s) = the number of edges e with s >= e, compared in f32: bin 0 is "below edges[0]", bin nedges "at or above the last edge".
+ *     NaN (0 / 0) and 0.0 both land in bin 0, consistent with "NaN is never >= cutoff" everywhere else;
+ *   - hist[i * (nedges + 1) + b] = the number of table rows j, of all N, with bin(s(i, j)) == b.  Row i of hist sums to N (to N - 1
+ *     with GSIM_HIST_EXCLUDE_SELF), and hist[i][b + 1] + ... + hist[i][nedges] is exactly `approx` of gsim_db_search(query = left
+ *     row i, cutoff = edges[b]) and exactly the length of list i of gsim_db_join* at that cutoff;
+ *   - total[b] = the sum over the left rows of hist[i][b], in uint64.  At least one of hist and total must be non-NULL; only what is
+ *     asked for is copied to the host;
+ *   - no pair is excluded by default: left == db counts the self pair (1.0 for a non-zero row: the last bin whose edge is <= 1; NaN
+ *     for an all-zero row: bin 0).  GSIM_HIST_EXCLUDE_SELF (only with left == db) leaves out the pair (left row i, table row i), by
+ *     row identity.  The row base of either handle plays no part: nothing returned names a row;
+ *   - the output is integer: byte-identical from run to run, independent of the route (GSIM_HIST_STREAM_MAX_ROWS) and of how the
+ *     work is cut into launches (GSIM_HIST_LAUNCH_PAIRS; both read once per handle, the table's).  Ranges of left rows
+ *     concatenate to the full call's hist, and their totals add up to its total -- ranges are how a left side too large for the
+ *     call's nl x (nedges + 1) x 8 bytes of device counters is done.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / left (NULL queries with nq > 0), unknown metric, Tversky alpha / beta
+ * negative or not finite, NULL edges, nedges == 0 or > GSIM_HIST_MAX_EDGES, an edge that is not finite, not above its predecessor or
+ * <= 0, both outputs NULL, unknown flag bits, GSIM_HIST_EXCLUDE_SELF with left != db, nl >= 2^32, a table of 2^32 rows or more,
+ * lrow_begin > lrow_end or lrow_end past the left handle's count, handles of different fp_bits, rows wider than 4096 bits.
+ * GSIM_ERR_STATE: either handle multi-shard, folded or not on a GPU; handles on different devices.  GSIM_ERR_NOMEM: the call's device
+ * memory cannot be had; nothing leaked.  nl == 0: GSIM_OK, total zeroed, hist untouched.
+ * Execution: on the table handle's stream under the one-call-at-a-time rule (of both handles); the search state of both is left as
+ * it was found (a gsim_db_search before and after returns identical bytes).  Calls of at most GSIM_HIST_STREAM_MAX_ROWS left rows
+ * stream the table once per left row; larger ones run an owner-tile kernel (256 left rows to a workgroup, the table's rows split over
+ * workgroups as well) that needs, as gsim_db_knn, 4 bytes per TABLE row (popcounts) and zero-padded copies of both sides where the rows
+ * are not 128, 256, 512, 1024, 2048 or 4096 bits wide.  All of it, and the nl x (nedges + 1) x 8 bytes of counters, is freed by the
+ * call.  Tables from gsim_db_generate and gsim_db_attach_device_rows work on either side; no host copy is needed. */
+#define GSIM_HIST_MAX_EDGES 128u
+#define GSIM_HIST_EXCLUDE_SELF 1u   /* only with left == db: the pair (left row i, table row i) is not counted */
+typedef struct {
+    uint64_t left_rows;       /* left rows of the call                                                                          */
+    uint64_t rows_streamed;   /* ... taken by the streaming route (one pass over the table each)                                */
+    uint64_t rows_tiled;      /* ... taken by the owner-tile route                                                              */
+    uint64_t stream_launches; /* launches of the streaming kernel (a pass over a long table is cut into bounded launches)       */
+    uint64_t tile_launches;   /* launches of the owner-tile kernel                                                              */
+    uint64_t pairs;           /* pairs counted = sum of every returned histogram                                                */
+    double stream_ms;         /* HIP events on the table handle's stream: all streaming launches                                */
+    double tile_ms;           /* ... all owner-tile launches                                                                    */
+    double reduce_ms;         /* the totals, on the device                                                                      */
+    double d2h_ms;            /* counters into host memory                                                                      */
+    double wall_ms;           /* the whole call, host clock                                                                     */
+    double clock_mhz;         /* tile route: shader clock the kernel ran at (as gsim_graph_stats.clock_mhz); 0 when streaming   */
+} gsim_hist_stats;
+int gsim_db_histogram_queries(gsim_db* db, const uint32_t* queries, uint64_t nq,
+                              const float* edges, uint32_t nedges, int metric, float alpha, float beta,
+                              uint64_t* hist /* nq x (nedges+1), or NULL */, uint64_t* total /* nedges+1, or NULL */,
+                              gsim_hist_stats* stats /* or NULL */);
+int gsim_db_histogram(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end,
+                      const float* edges, uint32_t nedges, int metric, float alpha, float beta, uint32_t flags,
+                      uint64_t* hist, uint64_t* total, gsim_hist_stats* stats);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
