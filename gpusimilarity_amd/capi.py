@@ -94,6 +94,12 @@ class GsimHistStats(C.Structure):
                 ("reduce_ms", C.c_double), ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
 
 
+class GsimScoresStats(C.Structure):
+    _fields_ = [("left_rows", C.c_uint64), ("right_rows", C.c_uint64), ("launches", C.c_uint64), ("slabs", C.c_uint64),
+                ("pairs", C.c_uint64), ("prepare_ms", C.c_double), ("kernel_ms", C.c_double), ("d2h_ms", C.c_double),
+                ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -120,6 +126,7 @@ EXPORTS = [
     "gsim_db_leader",
     "gsim_db_knn", "gsim_graph_get_knn_stats",
     "gsim_db_histogram_queries", "gsim_db_histogram",
+    "gsim_db_scores", "gsim_db_scores_queries", "gsim_db_scores_device",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -221,6 +228,12 @@ def load():
                                                 C.POINTER(GsimHistStats)]),
         "gsim_db_histogram": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.c_float, C.c_float,
                                         C.c_uint32, u64p, u64p, C.POINTER(GsimHistStats)]),
+        "gsim_db_scores": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_float, C.c_float,
+                                     C.POINTER(C.c_float), C.c_uint64, C.POINTER(GsimScoresStats)]),
+        "gsim_db_scores_queries": (C.c_int, [vp, u32p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_float, C.c_float,
+                                             C.POINTER(C.c_float), C.c_uint64, C.POINTER(GsimScoresStats)]),
+        "gsim_db_scores_device": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_float, C.c_float,
+                                            vp, C.c_uint64, C.POINTER(GsimScoresStats)]),
         "gsim_db_leader": (C.c_int, [vp, C.c_float, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, u32p, u32p, u32p,
                                      C.POINTER(C.c_float), C.POINTER(GsimLeaderStats)]),
         "gsim_last_error": (C.c_char_p, []),
@@ -494,6 +507,47 @@ class Table:
         if stats is not None:
             stats.update({f: getattr(st, f) for f, _ in GsimHistStats._fields_})
         return hist, tot
+
+    def scores(self, left, row_begin=0, row_end=None, col_begin=0, col_end=None, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0,
+               out_ptr=None, ld=None, stats=None):
+        """gsim_db_scores / gsim_db_scores_queries / gsim_db_scores_device: the dense matrix S[i, j] = score(query = left row
+        row_begin + i, row col_begin + j of THIS table) -> float32 [nl, nr].  `left`: a Table on the same device (its rows
+        [row_begin, row_end)) or a (nq, W) / (W,) uint32 array.  `out_ptr`: a device address on this table's device (a torch
+        tensor's data_ptr()) -- the matrix is written there, row i at out_ptr + i * ld * 4 (`ld` floats per row, default nr; only
+        the first nr of a row are written), nothing is copied to the host and None is returned; `left` must then be a Table.
+        `stats`: a dict that receives the call's gsim_scores_stats."""
+        if col_end is None:
+            col_end = self.count()
+        nr = max(col_end - col_begin, 0)
+        st = GsimScoresStats()
+        fp = C.POINTER(C.c_float)
+        out = None
+        if out_ptr is not None:
+            if not isinstance(left, Table):
+                raise GsimError(-1, "out_ptr needs a Table as the left side")
+            if row_end is None:
+                row_end = left.count()
+            check(self._L.gsim_db_scores_device(self._h, left._h, row_begin, row_end, col_begin, col_end, metric, alpha, beta,
+                                                C.c_void_p(out_ptr), nr if ld is None else ld, C.byref(st)))
+        elif ld is not None:
+            raise GsimError(-1, "ld goes with out_ptr: the returned array has nr floats per row")
+        elif isinstance(left, Table):
+            if row_end is None:
+                row_end = left.count()
+            out = np.empty((max(row_end - row_begin, 0), nr), dtype=np.float32)
+            check(self._L.gsim_db_scores(self._h, left._h, row_begin, row_end, col_begin, col_end, metric, alpha, beta,
+                                         out.ctypes.data_as(fp), nr, C.byref(st)))
+        else:
+            q = np.ascontiguousarray(left, dtype=np.uint32).reshape(-1, self.W)
+            if row_end is None:
+                row_end = q.shape[0]
+            q = np.ascontiguousarray(q[row_begin:row_end])
+            out = np.empty((len(q), nr), dtype=np.float32)
+            check(self._L.gsim_db_scores_queries(self._h, _u32(q) if len(q) else None, len(q), col_begin, col_end, metric, alpha, beta,
+                                                 out.ctypes.data_as(fp), nr, C.byref(st)))
+        if stats is not None:
+            stats.update({f: getattr(st, f) for f, _ in GsimScoresStats._fields_})
+        return out
 
     def maxmin(self, npicks, seeds=(), metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, max_score=1.0, assign=False, stats=None):
         """gsim_db_maxmin: MaxMin diversity picking, one pass over the table per pick -> (picks uint32 (+ row base),

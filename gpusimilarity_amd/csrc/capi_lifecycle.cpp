@@ -77,6 +77,8 @@ gsim::Knobs read_knobs()
     k.hist_stream_max_rows = env_value("GSIM_HIST_STREAM_MAX_ROWS", k.hist_stream_max_rows);
     if (const char* v = std::getenv("GSIM_HIST_LAUNCH_PAIRS")) k.hist_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
     k.hist_naive_add = env_value("GSIM_HIST_NAIVE_ADD", k.hist_naive_add) ? 1 : 0;
+    if (const char* v = std::getenv("GSIM_SCORES_LAUNCH_PAIRS")) k.scores_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
+    if (const char* v = std::getenv("GSIM_SCORES_STAGE_BYTES")) k.scores_stage_bytes = std::max(std::atoll(v), 1ll);   // (at least one row anyway)
     return k;
 }
 

@@ -1,0 +1,252 @@
+// capi_scores.cpp -- gsim_db_scores / gsim_db_scores_queries / gsim_db_scores_device: the dense matrix of scores of a block of
+// left rows against a range of table rows.  Two thin fronts (handle rows, host queries) and the device front over one core that
+// takes "left rows in device memory, nl of them", as the histograms; the argument checks, the prepare step, the launch plan and
+// the staging slabs of the host-output calls.  The device side is gsim_scores.hip.  The rule is stated in include/gpusim_hip.h.
+#include "capi_internal.h"
+
+#include <chrono>
+#include <cmath>
+
+namespace gsim_host
+{
+namespace
+{
+
+// Pairs of one launch of the matrix kernel, priced from the measured kernel (1.19 / 1.43 / 1.72 ms per
+// 2^30 pairs at WP = 8 / 32 / 64, i.e. about 8.8e-15 s x (WP + 120) a pair -- a floor set by the epilogue and the output
+// write, plus the matrix pipe's share per word): 5.6e11 / (WP + 120) pairs are about 5 ms at every width, so that no launch
+// comes near 50 ms on a shared GPU.
+constexpr double kScoresLaunchBudget = 5.6e11;
+constexpr double kScoresPairFloor = 120.0;
+
+struct ScoresLaunch {
+    uint64_t l0, l1, r0, r1;
+};
+
+// The launches of nl x nr pairs of rows of WP words: groups of block rows x ranges of block columns, each within the budget;
+// `pairs` > 0 (GSIM_SCORES_LAUNCH_PAIRS) replaces the budget: at most that many pairs, at least one kScoresTile x kScoresTile
+// block.  At most 65 535 block rows to a launch (the grid's second dimension).
+std::vector<ScoresLaunch> plan_scores(uint64_t nl, uint64_t nr, uint32_t WP, long long pairs)
+{
+    const uint64_t tile = gsim::kScoresTile;
+    const uint64_t by = (nl + tile - 1) / tile, bx = (nr + tile - 1) / tile;
+    const double budget = pairs > 0 ? static_cast<double>(pairs) : kScoresLaunchBudget / (WP + kScoresPairFloor);
+    const uint64_t max_blocks = std::max<uint64_t>(static_cast<uint64_t>(budget / static_cast<double>(tile * tile)), 1);
+    const uint64_t gy = std::min<uint64_t>(std::min(by, max_blocks), 65535u);
+    const uint64_t gx = std::min<uint64_t>(std::max<uint64_t>(max_blocks / gy, 1), bx);
+    std::vector<ScoresLaunch> out;
+    for (uint64_t y = 0; y < by; y += gy)
+        for (uint64_t x = 0; x < bx; x += gx)
+            out.push_back({y * tile, std::min((y + gy) * tile, nl), x * tile, std::min((x + gx) * tile, nr)});
+    return out;
+}
+
+struct ScoresCall {
+    uint64_t r0, nr; // the table rows [r0, r0 + nr)
+    int metric;
+    float alpha, beta;
+    float* out;      // host output (nullptr: the device call)
+    float* d_out;    // device output
+    uint64_t ld;
+    gsim_scores_stats* stats;
+};
+
+// left rows d_left[0 .. nl) (W words each, on s's device) against s's table rows [c.r0, c.r0 + c.nr)
+int scores(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, const ScoresCall& c)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    auto wall = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    const uint64_t nr = c.nr;
+    gsim_scores_stats ss{};
+    ss.left_rows = nl;
+    ss.right_rows = nr;
+    ss.pairs = nl * nr;
+    if (nl > 0 && nr > 0) {
+        GSIM_HIP(set_device(s.device));
+        const hipStream_t st = s.stream;
+        const uint32_t W = s.W, WP = gsim::scores_padded_words(W);
+        const uint32_t* d_right = static_cast<const uint32_t*>(s.d_rows) + c.r0 * W;
+
+        // popc of every row of either side, and the rows zero-padded to WP words unless they already are WP words
+        DevBuf<> lpop, rpop, lpad, rpad, stage, ctl;
+        GSIM_ALLOC(lpop, nl * 4, "the score matrix (popcounts of the left rows)");
+        GSIM_ALLOC(rpop, nr * 4, "the score matrix (popcounts of the table rows)");
+        if (WP != W) {
+            GSIM_ALLOC(lpad, nl * WP * 4, "the score matrix (padded left rows)");
+            GSIM_ALLOC(rpad, nr * WP * 4, "the score matrix (padded table rows)");
+        }
+        // host output: slabs of whole left rows through device memory
+        const bool host_out = c.out != nullptr;
+        uint64_t slab_rows = nl;
+        if (host_out) {
+            slab_rows = std::min<uint64_t>(std::max<uint64_t>(static_cast<uint64_t>(db->knobs.scores_stage_bytes) / (nr * 4), 1), nl);
+            GSIM_ALLOC(stage, slab_rows * nr * 4, "the score matrix (staging slab)");
+        }
+        const uint64_t nslabs = (nl + slab_rows - 1) / slab_rows;
+        const std::vector<ScoresLaunch> plan = plan_scores(slab_rows, nr, WP, db->knobs.scores_launch_pairs);
+        const uint64_t last_rows = nl - (nslabs - 1) * slab_rows;
+        const std::vector<ScoresLaunch> plan_last = last_rows == slab_rows ? plan : plan_scores(last_rows, nr, WP, db->knobs.scores_launch_pairs);
+        const size_t nlaunch = plan.size() * (nslabs - 1) + plan_last.size();
+        GSIM_ALLOC(ctl, 4 * nlaunch * 8, "the score matrix (clock stamps)");
+        GSIM_HIP(hipMemsetAsync(ctl, 0, 4 * nlaunch * 8, st));
+
+        EventPair ev_prep, ev_run, ev_d2h;
+        GSIM_HIP(ev_prep.create());
+        GSIM_HIP(ev_run.create());
+        GSIM_HIP(ev_d2h.create());
+        GSIM_HIP(hipEventRecord(ev_prep.a, st));
+        GSIM_HIP(gsim::launch_nbr_prepare(d_left, nl, W, WP, lpad.as<uint32_t>(), lpop.as<uint32_t>(), st));
+        GSIM_HIP(gsim::launch_nbr_prepare(d_right, nr, W, WP, rpad.as<uint32_t>(), rpop.as<uint32_t>(), st));
+        GSIM_HIP(hipEventRecord(ev_prep.b, st));
+
+        gsim::ScoresArgs a{};
+        a.rrows = WP != W ? rpad.as<uint32_t>() : d_right;
+        a.rpop = rpop.as<uint32_t>();
+        a.nr = nr;
+        a.WP = WP;
+        a.metric = c.metric;
+        a.alpha = c.alpha;
+        a.beta = c.beta;
+        size_t launched = 0;
+        for (uint64_t sl = 0; sl < nslabs; sl++) {
+            const uint64_t first = sl * slab_rows, rows = std::min(slab_rows, nl - first);
+            a.lrows = (WP != W ? lpad.as<uint32_t>() : d_left) + first * WP;
+            a.lpop = lpop.as<uint32_t>() + first;
+            a.nl = rows;
+            a.out = host_out ? stage.as<float>() : c.d_out + first * c.ld;
+            a.ld = host_out ? nr : c.ld;
+            GSIM_HIP(hipEventRecord(ev_run.a, st));
+            for (const ScoresLaunch& l : sl + 1 == nslabs ? plan_last : plan) {
+                a.clk = ctl.as<unsigned long long>() + 4 * launched++;
+                GSIM_HIP(gsim::launch_scores(a, l.l0, l.l1, l.r0, l.r1, st));
+            }
+            GSIM_HIP(hipEventRecord(ev_run.b, st));
+            if (host_out) {
+                GSIM_HIP(hipEventRecord(ev_d2h.a, st));
+                float* dst = c.out + first * c.ld;
+                if (c.ld == nr) GSIM_HIP(hipMemcpyAsync(dst, stage, rows * nr * 4, hipMemcpyDeviceToHost, st));
+                else GSIM_HIP(hipMemcpy2DAsync(dst, c.ld * 4, stage, nr * 4, nr * 4, rows, hipMemcpyDeviceToHost, st));
+                GSIM_HIP(hipEventRecord(ev_d2h.b, st));
+            }
+            // (one slab at a time: the next one's kernel overwrites the staging memory, and the events are reused)
+            GSIM_HIP(hipStreamSynchronize(st));
+            ss.kernel_ms += ev_run.ms();
+            if (host_out) ss.d2h_ms += ev_d2h.ms();
+        }
+        ss.launches = nlaunch;
+        ss.slabs = host_out ? nslabs : 0;
+        ss.prepare_ms = ev_prep.ms();
+        std::vector<unsigned long long> clk(4 * nlaunch);
+        GSIM_HIP(hipMemcpyAsync(clk.data(), ctl, clk.size() * 8, hipMemcpyDeviceToHost, st));
+        GSIM_HIP(hipStreamSynchronize(st));
+        double cyc = 0.0, ticks = 0.0;
+        for (size_t l = 0; l < nlaunch; l++) {
+            cyc += static_cast<double>(clk[4 * l + 2] - clk[4 * l]);
+            ticks += static_cast<double>(clk[4 * l + 3] - clk[4 * l + 1]);
+        }
+        ss.clock_mhz = ticks > 0.0 ? cyc / ticks * 100.0 : 0.0; // wall clock: 100 MHz
+    }
+    ss.wall_ms = wall();
+    if (c.stats) *c.stats = ss;
+    return GSIM_OK;
+}
+
+// what every entry point checks before any device state (left == nullptr: the queries entry, nl = nq)
+int check_scores_args(gsim_db* db, const gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, uint64_t rrow_begin, uint64_t rrow_end, int metric,
+                      float alpha, float beta, const void* out, uint64_t ld)
+{
+    if (!db) return fail(GSIM_ERR_INVALID, "NULL argument");
+    if (metric != GSIM_METRIC_TANIMOTO && metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
+    if (metric == GSIM_METRIC_TVERSKY && !(std::isfinite(alpha) && alpha >= 0.0f && std::isfinite(beta) && beta >= 0.0f))
+        return fail(GSIM_ERR_INVALID, "scores: Tversky alpha and beta must be finite and >= 0");
+    if (lrow_begin > lrow_end) return fail(GSIM_ERR_INVALID, "left row range: begin past end");
+    if (left && lrow_end > left->nrows) return fail(GSIM_ERR_INVALID, "left row range outside the left table");
+    if (rrow_begin > rrow_end) return fail(GSIM_ERR_INVALID, "table row range: begin past end");
+    if (rrow_end > db->nrows) return fail(GSIM_ERR_INVALID, "table row range outside the table");
+    const uint64_t nl = lrow_end - lrow_begin, nr = rrow_end - rrow_begin;
+    if (nl > 0xFFFFFFFFull || nr > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "scores: 2^32 rows or more on one side");
+    if (ld < nr) return fail(GSIM_ERR_INVALID, "scores: ld is less than the number of table rows");
+    if (left && left->fp_bits != db->fp_bits) return fail(GSIM_ERR_INVALID, "the two handles have different fp_bits");
+    if (gsim::scores_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, "score matrices support rows of up to 4096 bits");
+    if (!out && nl > 0 && nr > 0) return fail(GSIM_ERR_INVALID, "scores: NULL output");
+    return GSIM_OK;
+}
+
+int check_scores_state(const gsim_db* db, const char* which)
+{
+    if (!db->finalized) return fail(GSIM_ERR_STATE, std::string(which) + " not finalized (no rows on a GPU)");
+    if (db->fold > 1) return fail(GSIM_ERR_STATE, std::string("score matrices do not support folded tables: ") + which);
+    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, std::string("score matrices need single-shard handles: ") + which);
+    return GSIM_OK;
+}
+
+int run_scores(gsim_db* db, const uint32_t* d_left, uint64_t nl, const ScoresCall& c)
+{
+    try {
+        return scores(db, db->shards[0], d_left, nl, c);
+    } catch (const std::bad_alloc&) {
+        return fail(GSIM_ERR_NOMEM, "host memory for the score matrix");
+    }
+}
+
+// the two fronts whose left rows are a handle's: `out` in host memory, or `d_out` in the table's device memory
+int scores_of_handle(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, uint64_t rrow_begin, uint64_t rrow_end, int metric,
+                     float alpha, float beta, float* out, float* d_out, uint64_t ld, gsim_scores_stats* stats)
+{
+    if (!left) return fail(GSIM_ERR_INVALID, "NULL left handle");
+    int rc = check_scores_args(db, left, lrow_begin, lrow_end, rrow_begin, rrow_end, metric, alpha, beta, out ? static_cast<void*>(out) : d_out, ld);
+    if (rc != GSIM_OK) return rc;
+    rc = check_scores_state(db, "table");
+    if (rc == GSIM_OK && left != db) rc = check_scores_state(left, "left table");
+    if (rc != GSIM_OK) return rc;
+    if (left->shards[0].device != db->shards[0].device) return fail(GSIM_ERR_STATE, "the two handles are on different devices");
+    // one call at a time on either handle
+    std::unique_lock<std::mutex> g1(db->search_mutex, std::defer_lock), g2(left->search_mutex, std::defer_lock);
+    if (left != db) std::lock(g1, g2);
+    else g1.lock();
+    const uint32_t* d_left = static_cast<const uint32_t*>(left->shards[0].d_rows) + lrow_begin * left->shards[0].W;
+    const ScoresCall c{rrow_begin, rrow_end - rrow_begin, metric, alpha, beta, out, d_out, ld, stats};
+    return run_scores(db, d_left, lrow_end - lrow_begin, c);
+}
+
+} // namespace
+} // namespace gsim_host
+
+using namespace gsim_host;
+
+extern "C" {
+
+int gsim_db_scores(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, uint64_t rrow_begin, uint64_t rrow_end, int metric,
+                   float alpha, float beta, float* out, uint64_t ld, gsim_scores_stats* stats)
+{
+    return scores_of_handle(db, left, lrow_begin, lrow_end, rrow_begin, rrow_end, metric, alpha, beta, out, nullptr, ld, stats);
+}
+
+int gsim_db_scores_device(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, uint64_t rrow_begin, uint64_t rrow_end, int metric,
+                          float alpha, float beta, void* d_out, uint64_t ld, gsim_scores_stats* stats)
+{
+    return scores_of_handle(db, left, lrow_begin, lrow_end, rrow_begin, rrow_end, metric, alpha, beta, nullptr, static_cast<float*>(d_out), ld, stats);
+}
+
+int gsim_db_scores_queries(gsim_db* db, const uint32_t* queries, uint64_t nq, uint64_t rrow_begin, uint64_t rrow_end, int metric, float alpha,
+                           float beta, float* out, uint64_t ld, gsim_scores_stats* stats)
+{
+    int rc = check_scores_args(db, nullptr, 0, nq, rrow_begin, rrow_end, metric, alpha, beta, out, ld);
+    if (rc != GSIM_OK) return rc;
+    if (nq && !queries) return fail(GSIM_ERR_INVALID, "NULL queries");
+    rc = check_scores_state(db, "table");
+    if (rc != GSIM_OK) return rc;
+    std::lock_guard<std::mutex> guard(db->search_mutex);
+    Shard& s = db->shards[0];
+    DevBuf<> d_left;
+    if (nq && rrow_end > rrow_begin) {
+        GSIM_HIP(set_device(s.device));
+        const size_t bytes = static_cast<size_t>(nq) * s.W * 4;
+        GSIM_ALLOC(d_left, bytes, "the score matrix's left rows");
+        GSIM_HIP(hipMemcpyAsync(d_left, queries, bytes, hipMemcpyHostToDevice, s.stream));
+    }
+    const ScoresCall c{rrow_begin, rrow_end - rrow_begin, metric, alpha, beta, out, nullptr, ld, stats};
+    return run_scores(db, d_left.as<uint32_t>(), nq, c);
+}
+
+} // extern "C"

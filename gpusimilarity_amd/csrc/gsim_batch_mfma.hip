@@ -43,6 +43,7 @@
 
 #include "../../include/gpusim_hip.h"
 #include "gsim_device_common.h"
+#include "gsim_mfma_fp4.h"
 #include "gsim_prefilter.h"
 
 namespace gsim
@@ -50,9 +51,6 @@ namespace gsim
 namespace
 {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -74,10 +72,6 @@ constexpr int kMStage = 96;            // raw candidates staged per wave (proces
 #define MF_T(var)
 #define MF_ACC(slot, t0, t1)
 #endif
-
-constexpr int kScale1 = 0x80808080;  // E8M0 2^1
-constexpr int kScale0 = 0x7F7F7F7F;  // 2^0
-constexpr int kScaleM = 0x7E7E7E7E;  // 2^-1
 
 // LDS of the sample kernel (its own geometry: one 64 KB row block, 64 KB of histograms)
 struct MfmaShared {
@@ -106,32 +100,6 @@ template <int WORDS, int BC, int RING> struct MfmaRing {
     uint32_t stage_cb[kMWaves][kMStage];  // query of the tile -- scored exactly in bulk (drain_stage)
     uint32_t stage_q[kMWaves][kMStage];
 };
-
-// The class masks are passed in VGPRs: v_and_b32 with two vector operands issues in 2 cycles,
-// with a literal or scalar operand in 4 (scripts/valu_op_rate_probe.hip).
-struct ClassMasks {
-    uint32_t m1, m2, m4;
-};
-
-template <int CLS> __device__ __forceinline__ uint32_t fp4_word(uint32_t x, const ClassMasks& k)
-{
-    return CLS == 0 ? (x & k.m1) : CLS == 1 ? (x & k.m2) : CLS == 2 ? (x & k.m4) : ((x >> 3) & k.m1);
-}
-
-// element by element: a vector AND with a splat mask makes hipcc keep four copies of every mask
-template <int CLS> __device__ __forceinline__ v4i fp4_class(u32x4 x, const ClassMasks& k)
-{
-    return v4i{static_cast<int>(fp4_word<CLS>(x.x, k)), static_cast<int>(fp4_word<CLS>(x.y, k)),
-               static_cast<int>(fp4_word<CLS>(x.z, k)), static_cast<int>(fp4_word<CLS>(x.w, k))};
-}
-
-template <int CLS> __device__ __forceinline__ v16f mfma_class(v4i qa, v4i rb, v16f acc)
-{
-    const v8i A = {qa.x, qa.y, qa.z, qa.w, 0, 0, 0, 0};
-    const v8i B = {rb.x, rb.y, rb.z, rb.w, 0, 0, 0, 0};
-    constexpr int sc = CLS == 1 ? kScale0 : (CLS == 2 ? kScaleM : kScale1);
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B, acc, /*A fp4*/ 4, /*B fp4*/ 4, 0, sc, 0, sc);
-}
 
 // element r (wave-uniform) of an accumulator, for the rare path: through a COPY -- a dynamic index into the accumulators
 // themselves made hipcc keep them in scratch memory throughout the kernel

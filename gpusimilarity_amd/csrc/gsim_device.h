@@ -215,6 +215,12 @@ struct Knobs {
                                      // The result does not depend on it
     int hist_naive_add = 0;          // GSIM_HIST_NAIVE_ADD      1: the streaming kernel adds with one LDS atomic per lane instead of one per
                                      // distinct bin of the wave (for timing the two forms; same counts)
+    long long scores_launch_pairs = 0; // GSIM_SCORES_LAUNCH_PAIRS  a launch of gsim_db_scores*'s matrix kernel computes at most this many left x
+                                     // table pairs (at least one 128 x 128 block); 0: by the padded row width (capi_scores.cpp;
+                                     // DESIGN.md section 17).  The result does not depend on it
+    long long scores_stage_bytes = 256ll << 20; // GSIM_SCORES_STAGE_BYTES  device staging of the host-output calls: a slab of whole left rows of
+                                     // at most this many bytes (at least one row) is computed, then copied out.  The result does not
+                                     // depend on it
 };
 
 ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll, bool ragged = true);
@@ -460,6 +466,27 @@ struct HistStreamArgs {
 hipError_t launch_hist_pass(const HistStreamArgs& h, const ScanGeometry& g, uint64_t r0, uint64_t nrows, uint32_t l, hipStream_t s);
 // total[b] = sum over the nl rows of hist[i][b] (total is zeroed by the launch)
 hipError_t launch_hist_total(const unsigned long long* hist, uint64_t nl, uint32_t nbins, unsigned long long* total, hipStream_t s);
+
+// ---- dense similarity matrices (gsim_scores.hip, gsim_db_scores / gsim_db_scores_queries / gsim_db_scores_device) ----------
+constexpr int kScoresTile = 128;  // left rows x table rows of one workgroup's block of the output
+constexpr int kScoresBlock = 256; // 4 waves, a 64 x 64 quarter of the block each
+struct ScoresArgs {
+    const uint32_t* lrows;       // the call's left rows: nl x WP words, 16-byte aligned (zero-padded copy unless W == WP)
+    const uint32_t* rrows;       // the call's table rows: nr x WP words, likewise
+    const uint32_t* lpop;        // popc of every left row
+    const uint32_t* rpop;        // popc of every table row
+    uint64_t nl, nr;
+    uint32_t WP;                 // words per row as the kernel reads them: a multiple of 8 (256 bits), at most kNbrMaxWords
+    int metric;
+    float alpha, beta;
+    float* out;                  // out[i * ld + j] = score(left row i, table row j), device memory; only j < nr is written
+    uint64_t ld;
+    unsigned long long* clk;     // as KnnArgs.clk
+};
+uint32_t scores_padded_words(uint32_t W); // 0: wider than kNbrMaxWords
+// The block of left rows [l0, l1) x table rows [r0, r1) of the call's rectangle: l0 and r0 multiples of kScoresTile, l1 and r1
+// too unless they are nl / nr; at most 65 535 x kScoresTile left rows to a launch.
+hipError_t launch_scores(const ScoresArgs& a, uint64_t l0, uint64_t l1, uint64_t r0, uint64_t r1, hipStream_t s);
 
 // ---- MaxMin diversity picking (gsim_maxmin.hip, gsim_db_maxmin) ----------------------------------------------------------
 // ctl words of a call (zeroed by the host before the first pass; the ticket on its own 128-byte line)

@@ -703,6 +703,61 @@ int gsim_db_histogram(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t 
                       const float* edges, uint32_t nedges, int metric, float alpha, float beta, uint32_t flags,
                       uint64_t* hist, uint64_t* total, gsim_hist_stats* stats);
 
+/* ---- dense similarity matrices: every score of a block of left rows against a range of table rows -------------------------------- */
+/* gsim_db_scores / gsim_db_scores_queries / gsim_db_scores_device: the matrix S[i, j] = score(left row i, table row rrow_begin + j)
+ * for nl LEFT rows -- the rows [lrow_begin, lrow_end) of a handle `left` resident on the same device (left == db is allowed), or the
+ * nq fingerprints at `queries` (host memory, nq x fp_bits / 32 words) -- against the nr = rrow_end - rrow_begin rows
+ * [rrow_begin, rrow_end) of the table `db` (RDKit's BulkTanimotoSimilarity, chemfp's arena-by-arena calls; the input of kernel models,
+ * MDS / t-SNE / UMAP, scipy linkage, library-against-library heat maps).  No counterpart in the reference.  The intersection counts
+ * are a 0/1 matrix product and run on the matrix cores; nothing is filtered, sorted or indexed: the position says which pair it is.
+ * THE RESULT RULE:
+ *   - out[i * ld + j] is the score of left row i against table row rrow_begin + j, with a = popc(left row), b = popc(table row): bit
+ *     for bit what gsim_db_search(query = left row i, k = N, cutoff = 0) returns as that row's `score`, i.e. the reference's one f32
+ *     divide followed by "NaN is never >= cutoff".  Hence a 0 / 0 pair is 0.0f, never NaN; nothing is negative; nothing exceeds 1.0;
+ *   - metrics: GSIM_METRIC_TANIMOTO, and GSIM_METRIC_TVERSKY with any finite alpha >= 0, beta >= 0 -- asymmetric included: every pair
+ *     is computed from the left row's side (alpha weighs the left row's own bits), as in the joins and histograms;
+ *   - only the nl x nr entries are written: the columns nr ... ld - 1 of every row are left as they were found, in host and in
+ *     device memory;
+ *   - no pair is excluded: with left == db the diagonal is 1.0 (0.0 for an all-zero row).  The row base of either handle plays no
+ *     part: nothing returned names a row;
+ *   - blocks concatenate: any cut of the left range and of the table range into pieces gives exactly the slices of the whole matrix
+ *     -- that is how a matrix larger than memory is made;
+ *   - the output is byte-identical from run to run and does not depend on how the call is cut into launches
+ *     (GSIM_SCORES_LAUNCH_PAIRS) or staging slabs (GSIM_SCORES_STAGE_BYTES; both read once per handle, the table's).
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / left (NULL queries with nq > 0), NULL out / d_out when nl * nr > 0,
+ * unknown metric, Tversky alpha / beta negative or not finite, ld < nr, a range with begin past end or end past its handle's count,
+ * nl or nr >= 2^32, handles of different fp_bits, rows wider than 4096 bits.  GSIM_ERR_STATE: either handle multi-shard, folded or
+ * not on a GPU; handles on different devices.  GSIM_ERR_NOMEM: the call's device memory cannot be had; nothing leaked.  nl == 0 or
+ * nr == 0: GSIM_OK, out untouched.
+ * Execution: on the table handle's stream under the one-call-at-a-time rule (of both handles); every call returns with that stream
+ * idle and every temporary freed -- gsim_db_scores_device may be followed at once by work on any stream that reads d_out; the
+ * search state of both handles is left as it was found.  Device memory of a call: 4 bytes per left and per table row of the call
+ * (popcounts), zero-padded copies of both sides where the rows are not a multiple of 256 bits wide, and, for the two host-output
+ * calls, one staging slab of whole left rows of at most GSIM_SCORES_STAGE_BYTES (default 256 MiB; at least one row), computed and
+ * copied out slab by slab.  gsim_db_scores_device writes straight into d_out, memory of the table's device.  Tables from
+ * gsim_db_generate and gsim_db_attach_device_rows work on either side; no host copy is needed. */
+typedef struct {
+    uint64_t left_rows, right_rows;  /* nl, nr of the call                                                   */
+    uint64_t launches;               /* launches of the matrix kernel                                        */
+    uint64_t slabs;                  /* host output: device staging slabs copied out (0 for the device call) */
+    uint64_t pairs;                  /* nl * nr                                                              */
+    double prepare_ms;               /* popcounts and zero-padded copies                                     */
+    double kernel_ms;                /* HIP events on the table handle's stream: all matrix launches         */
+    double d2h_ms;                   /* host output only                                                     */
+    double wall_ms;
+    double clock_mhz;                /* as gsim_graph_stats.clock_mhz                                        */
+} gsim_scores_stats;
+
+int gsim_db_scores(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end,
+                   uint64_t rrow_begin, uint64_t rrow_end, int metric, float alpha, float beta,
+                   float* out /* host, nl rows of ld floats */, uint64_t ld, gsim_scores_stats* stats /* or NULL */);
+int gsim_db_scores_queries(gsim_db* db, const uint32_t* queries, uint64_t nq,
+                           uint64_t rrow_begin, uint64_t rrow_end, int metric, float alpha, float beta,
+                           float* out, uint64_t ld, gsim_scores_stats* stats);
+int gsim_db_scores_device(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end,
+                          uint64_t rrow_begin, uint64_t rrow_end, int metric, float alpha, float beta,
+                          void* d_out /* memory of the table's device */, uint64_t ld, gsim_scores_stats* stats);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
