@@ -100,6 +100,12 @@ class GsimScoresStats(C.Structure):
                 ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
 
 
+class GsimComponentsStats(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("levels", C.c_uint64), ("launches", C.c_uint64), ("pairs", C.c_uint64), ("kept", C.c_uint64),
+                ("unions", C.c_uint64), ("cas_failed", C.c_uint64), ("kernel_ms", C.c_double), ("label_ms", C.c_double),
+                ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -127,6 +133,7 @@ EXPORTS = [
     "gsim_db_knn", "gsim_graph_get_knn_stats",
     "gsim_db_histogram_queries", "gsim_db_histogram",
     "gsim_db_scores", "gsim_db_scores_queries", "gsim_db_scores_device",
+    "gsim_db_components", "gsim_components",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -236,6 +243,9 @@ def load():
                                             vp, C.c_uint64, C.POINTER(GsimScoresStats)]),
         "gsim_db_leader": (C.c_int, [vp, C.c_float, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, u32p, u32p, u32p,
                                      C.POINTER(C.c_float), C.POINTER(GsimLeaderStats)]),
+        "gsim_db_components": (C.c_int, [vp, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.c_float, C.c_float, u32p, u32p, u32p, u32p,
+                                         C.POINTER(GsimComponentsStats)]),
+        "gsim_components": (C.c_int, [u64p, u32p, C.c_uint64, u32p, u32p, u32p, u64p]),
         "gsim_last_error": (C.c_char_p, []),
         "gsim_version": (C.c_char_p, []),
     }
@@ -591,6 +601,23 @@ class Table:
                                      row_score.ctypes.data_as(C.POINTER(C.c_float)) if assign else None, C.byref(st)))
         return leaders[:nl.value].copy(), leader_of, row_score, {f: getattr(st, f) for f, _ in GsimLeaderStats._fields_}
 
+    def components(self, cutoffs, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, first_row=True, sizes=True):
+        """gsim_db_components: single-linkage clustering (connected components of "score >= cutoff") at an ascending list of cutoffs,
+        or one scalar cutoff -> (levels, stats dict); levels[l] = (component_of uint32 [N], first_row uint32 [ncomponents] (+ row
+        base), sizes uint32 [ncomponents]) for cutoffs[l]; first_row / sizes are None where not asked for."""
+        cut = np.ascontiguousarray(np.atleast_1d(cutoffs), dtype=np.float32).reshape(-1)
+        n, nl = self.count(), len(cut)
+        comp = np.empty((max(nl, 1), n), dtype=np.uint32)
+        ncomp = np.zeros(max(nl, 1), dtype=np.uint32)
+        first = np.empty((max(nl, 1), n), dtype=np.uint32) if first_row else None
+        size = np.empty((max(nl, 1), n), dtype=np.uint32) if sizes else None
+        st = GsimComponentsStats()
+        check(self._L.gsim_db_components(self._h, cut.ctypes.data_as(C.POINTER(C.c_float)), nl, metric, alpha, beta, _u32(comp), _u32(ncomp),
+                                         _u32(first) if first_row else None, _u32(size) if sizes else None, C.byref(st)))
+        levels = [(comp[l].copy(), first[l, :ncomp[l]].copy() if first_row else None, size[l, :ncomp[l]].copy() if sizes else None)
+                  for l in range(nl)]
+        return levels, {f: getattr(st, f) for f, _ in GsimComponentsStats._fields_}
+
     def rowset(self, rows=None, bitmap=None, exclude=False) -> RowSet:
         """gsim_rowset_from_rows / _from_bitmap: `rows` are row indices including the row base (gsim_hit.row values), any order,
         duplicates collapse; `bitmap` is (count + 31) // 32 uint32 words, bit r % 32 of word r // 32 selecting row r without the
@@ -736,6 +763,24 @@ def butina(indptr, indices):
     check(load().gsim_butina(indptr.ctypes.data_as(C.POINTER(C.c_uint64)), _u32(indices), n, _u32(cluster_of),
                              _u32(centroids), C.byref(nc)))
     return cluster_of, centroids[:nc.value].copy()
+
+
+def components(indptr, indices, nrows=None):
+    """gsim_components (host code): the connected components of a symmetric CSR graph -> (component_of uint32 [n],
+    first_row uint32 [ncomponents], sizes uint32 [ncomponents]); components are numbered in ascending order of their smallest row
+    (include/gpusim_hip.h states the rule)."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.uint64)
+    indices = np.ascontiguousarray(indices, dtype=np.uint32)
+    n = len(indptr) - 1 if nrows is None else int(nrows)
+    if n < 0 or len(indptr) < n + 1:
+        raise GsimError(-1, "indptr needs nrows + 1 entries")
+    component_of = np.empty(n, dtype=np.uint32)
+    first_row = np.empty(max(n, 1), dtype=np.uint32)
+    sizes = np.empty(max(n, 1), dtype=np.uint32)
+    nc = C.c_uint64(0)
+    check(load().gsim_components(indptr.ctypes.data_as(C.POINTER(C.c_uint64)), _u32(indices), n, _u32(component_of), _u32(first_row),
+                                 _u32(sizes), C.byref(nc)))
+    return component_of, first_row[:nc.value].copy(), sizes[:nc.value].copy()
 
 
 def litmus(test: int, workgroups: int = 256, iterations: int = 100000, device: int = 0) -> dict:

@@ -1,0 +1,220 @@
+// capi_components.cpp -- gsim_db_components (single-linkage clustering: the connected components of the threshold graph at up to
+// eight cutoffs, in one pass over the pairs) and gsim_components (the same rule on a symmetric CSR graph, host code).  The argument
+// checks and the launch sequence of a call; the device side is gsim_components.hip.  The rule is stated in include/gpusim_hip.h.
+#include "capi_pairs.h"
+
+#include <chrono>
+#include <cmath>
+
+namespace gsim_host
+{
+namespace
+{
+
+int components(gsim_db* db, Shard& s, const float* cutoffs, uint32_t nlevels, int metric, float alpha, float beta, uint32_t* component_of,
+               uint32_t* ncomponents, uint32_t* first_row, uint32_t* sizes, gsim_components_stats* st)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t N = s.nrows;
+    const uint32_t WP = gsim::nbr_padded_words(s.W);
+    GSIM_HIP(set_device(s.device));
+    const hipStream_t stream = s.stream;
+
+    const uint64_t nt = (N + gsim::kNbrTile - 1) / gsim::kNbrTile;
+    const std::vector<NbrLaunch> plan =
+        N < 2 ? std::vector<NbrLaunch>() : plan_launches(nt, nt, true, WP, static_cast<uint64_t>(db->knobs.components_launch_pairs));
+    size_t tmp_bytes = 0;
+    GSIM_HIP(gsim::comp_scan_bytes(N, &tmp_bytes));
+    DevBuf<uint32_t> pop, pad, parent, d_comp, d_first, d_sizes, d_ncomp, d_flag, d_num;
+    DevBuf<unsigned long long> ctl; // the counters, then 4 clock stamps per launch
+    DevBuf<> tmp;
+    const size_t stripe = static_cast<size_t>(N) * 4, all = stripe * nlevels;
+    GSIM_ALLOC(pop, stripe, "components (popcounts)");
+    if (WP != s.W) GSIM_ALLOC(pad, static_cast<size_t>(N) * WP * 4, "components (the padded rows)");
+    GSIM_ALLOC(parent, all, "components (the forests)");
+    GSIM_ALLOC(d_comp, all, "components (component_of)");
+    if (first_row) GSIM_ALLOC(d_first, all, "components (first_row)");
+    if (sizes) GSIM_ALLOC(d_sizes, all, "components (sizes)");
+    GSIM_ALLOC(d_ncomp, gsim::kCompMaxLevels * 4, "components (the counts)");
+    GSIM_ALLOC(d_flag, stripe, "components (label scratch)");
+    GSIM_ALLOC(d_num, stripe, "components (label scratch)");
+    GSIM_ALLOC(ctl, (gsim::kCompCounters + 4 * plan.size()) * 8, "components (control block)");
+    GSIM_ALLOC(tmp, tmp_bytes, "components (scan scratch)");
+    unsigned long long* d_clk = ctl + gsim::kCompCounters;
+
+    gsim::CompArgs a{};
+    a.rows = WP != s.W ? static_cast<const uint32_t*>(pad) : static_cast<const uint32_t*>(s.d_rows);
+    a.pop = pop;
+    a.nrows = N;
+    a.WP = WP;
+    a.nlevels = nlevels;
+    a.metric = metric;
+    a.alpha = alpha;
+    a.beta = beta;
+    for (uint32_t l = 0; l < gsim::kCompMaxLevels; l++) a.cutoffs[l] = cutoffs[l < nlevels ? l : nlevels - 1];
+    a.parent = parent;
+    a.counters = ctl;
+
+    EventPair ev_kernel, ev_label, ev_d2h;
+    GSIM_HIP(ev_kernel.create());
+    GSIM_HIP(ev_label.create());
+    GSIM_HIP(ev_d2h.create());
+    GSIM_HIP(hipMemsetAsync(ctl, 0, (gsim::kCompCounters + 4 * plan.size()) * 8, stream));
+    GSIM_HIP(gsim::launch_nbr_prepare(s.d_rows, N, s.W, WP, pad, pop, stream));
+    GSIM_HIP(gsim::launch_comp_init(parent, N, nlevels, stream));
+    // the pass: every launch is followed by the flatten (all path shortening is there; after the last launch it leaves
+    // parent[x] = the smallest row of x's component)
+    GSIM_HIP(hipEventRecord(ev_kernel.a, stream));
+    for (size_t l = 0; l < plan.size(); l++) {
+        gsim::CompArgs al = a;
+        al.clk = d_clk + 4 * l;
+        GSIM_HIP(gsim::launch_comp_tiles(al, plan[l].rt0, plan[l].nrt, plan[l].ct0, plan[l].nct, stream));
+        GSIM_HIP(gsim::launch_comp_flatten(parent, N, nlevels, stream));
+    }
+    GSIM_HIP(hipEventRecord(ev_kernel.b, stream));
+    // labels, on the device, a level at a time
+    GSIM_HIP(hipEventRecord(ev_label.a, stream));
+    if (sizes) GSIM_HIP(hipMemsetAsync(d_sizes, 0, all, stream));
+    for (uint32_t l = 0; l < nlevels; l++)
+        GSIM_HIP(gsim::launch_comp_label(tmp, tmp_bytes, parent + l * N, N, db->row_base, d_flag, d_num, d_comp + l * N,
+                                         first_row ? d_first + l * N : nullptr, sizes ? d_sizes + l * N : nullptr, d_ncomp + l, stream));
+    GSIM_HIP(hipEventRecord(ev_label.b, stream));
+    std::vector<unsigned long long> h_ctl(gsim::kCompCounters + 4 * plan.size());
+    uint32_t h_ncomp[gsim::kCompMaxLevels] = {};
+    GSIM_HIP(hipEventRecord(ev_d2h.a, stream));
+    GSIM_HIP(hipMemcpyAsync(h_ncomp, d_ncomp, nlevels * 4, hipMemcpyDeviceToHost, stream));
+    GSIM_HIP(hipMemcpyAsync(h_ctl.data(), ctl, h_ctl.size() * 8, hipMemcpyDeviceToHost, stream));
+    GSIM_HIP(hipMemcpyAsync(component_of, d_comp, all, hipMemcpyDeviceToHost, stream));
+    GSIM_HIP(hipStreamSynchronize(stream));
+    uint64_t unions = 0;
+    for (uint32_t l = 0; l < nlevels; l++) {
+        if (h_ncomp[l] < 1 || h_ncomp[l] > N) return fail(GSIM_ERR_STATE, "components: the device reported an impossible count");
+        unions += N - h_ncomp[l];
+        // (entries at and after ncomponents[l] of a stripe are left untouched)
+        if (first_row) GSIM_HIP(hipMemcpyAsync(first_row + l * N, d_first + l * N, static_cast<size_t>(h_ncomp[l]) * 4, hipMemcpyDeviceToHost, stream));
+        if (sizes) GSIM_HIP(hipMemcpyAsync(sizes + l * N, d_sizes + l * N, static_cast<size_t>(h_ncomp[l]) * 4, hipMemcpyDeviceToHost, stream));
+    }
+    GSIM_HIP(hipEventRecord(ev_d2h.b, stream));
+    GSIM_HIP(hipStreamSynchronize(stream));
+    if (h_ctl[gsim::kCompUnions] != unions) return fail(GSIM_ERR_STATE, "components: the hooks and the component counts do not add up");
+    for (uint32_t l = 0; l < nlevels; l++) ncomponents[l] = h_ncomp[l];
+    if (st) {
+        st->rows = N;
+        st->levels = nlevels;
+        st->launches = plan.size();
+        st->pairs = N * (N - 1) / 2;
+        st->kept = h_ctl[gsim::kCompKept];
+        st->unions = unions;
+        st->cas_failed = h_ctl[gsim::kCompCasFailed];
+        st->kernel_ms = ev_kernel.ms();
+        st->label_ms = ev_label.ms();
+        st->d2h_ms = ev_d2h.ms();
+        double cyc = 0.0, ticks = 0.0;
+        for (size_t l = 0; l < plan.size(); l++) {
+            const unsigned long long* c = h_ctl.data() + gsim::kCompCounters + 4 * l;
+            cyc += static_cast<double>(c[2] - c[0]);
+            ticks += static_cast<double>(c[3] - c[1]);
+        }
+        st->clock_mhz = ticks > 0.0 ? cyc / ticks * 100.0 : 0.0; // wall clock: 100 MHz
+        st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return GSIM_OK;
+}
+
+// the forest of gsim_components: the smaller index wins every hook, so a tree's root is its smallest row
+uint32_t host_root(std::vector<uint32_t>& parent, uint32_t x)
+{
+    uint32_t r = x;
+    while (parent[r] != r) r = parent[r];
+    while (parent[x] != r) {
+        const uint32_t p = parent[x];
+        parent[x] = r;
+        x = p;
+    }
+    return r;
+}
+
+} // namespace
+} // namespace gsim_host
+
+using namespace gsim_host;
+
+extern "C" {
+
+int gsim_db_components(gsim_db* db, const float* cutoffs, uint32_t nlevels, int metric, float alpha, float beta, uint32_t* component_of,
+                       uint32_t* ncomponents, uint32_t* first_row, uint32_t* sizes, gsim_components_stats* stats)
+{
+    if (stats) *stats = gsim_components_stats{};
+    if (!db || !cutoffs || !component_of || !ncomponents) return fail(GSIM_ERR_INVALID, "NULL argument");
+    if (nlevels < 1 || nlevels > GSIM_COMPONENTS_MAX_LEVELS) return fail(GSIM_ERR_INVALID, "components: between 1 and 8 cutoff levels");
+    for (uint32_t l = 0; l < nlevels; l++) {
+        if (!(cutoffs[l] > 0.0f && cutoffs[l] <= 1.0f)) return fail(GSIM_ERR_INVALID, "components: every cutoff must be in (0, 1]");
+        if (l && !(cutoffs[l - 1] < cutoffs[l])) return fail(GSIM_ERR_INVALID, "components: the cutoffs must be strictly ascending");
+    }
+    if (metric != GSIM_METRIC_TANIMOTO && metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
+    if (metric == GSIM_METRIC_TVERSKY && !(alpha == beta))
+        return fail(GSIM_ERR_INVALID, "components need a symmetric metric (Tversky with alpha == beta)");
+    if (metric == GSIM_METRIC_TVERSKY && !(std::isfinite(alpha) && alpha >= 0.0f))
+        return fail(GSIM_ERR_INVALID, "components: Tversky alpha = beta must be finite and >= 0");
+    if (db->fp_bits > 4096 || gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, "components: rows wider than 4096 bits");
+    const uint64_t N = db->nrows;
+    if (N > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "components: tables of 2^32 rows or more");
+    for (uint32_t l = 0; l < nlevels; l++) ncomponents[l] = 0;
+    if (N == 0) return GSIM_OK;
+    if (!db->finalized) return fail(GSIM_ERR_STATE, "table not finalized (no rows on a GPU)");
+    if (db->fold > 1) return fail(GSIM_ERR_STATE, "components do not support folded tables");
+    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, "components need a single-shard handle");
+    std::lock_guard<std::mutex> guard(db->search_mutex);
+    Shard& s = db->shards[0];
+    int rc;
+    try {
+        rc = components(db, s, cutoffs, nlevels, metric, alpha, beta, component_of, ncomponents, first_row, sizes, stats);
+    } catch (const std::bad_alloc&) {
+        rc = fail(GSIM_ERR_NOMEM, "host memory for components");
+    }
+    if (rc != GSIM_OK) s.state_dirty = true; // (launches of the call may have failed mid-stream: the next enqueue re-zeroes the search state)
+    return rc;
+}
+
+int gsim_components(const uint64_t* indptr, const uint32_t* indices, uint64_t nrows, uint32_t* component_of, uint32_t* first_row,
+                    uint32_t* sizes, uint64_t* ncomponents)
+{
+    if (!indptr || !ncomponents || (nrows && !component_of)) return fail(GSIM_ERR_INVALID, "NULL argument");
+    if (nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "more than 2^32-1 rows");
+    if (indptr[0] != 0) return fail(GSIM_ERR_INVALID, "indptr[0] must be 0");
+    for (uint64_t r = 0; r < nrows; r++)
+        if (indptr[r + 1] < indptr[r]) return fail(GSIM_ERR_INVALID, "indptr must not decrease");
+    const uint64_t nnz = indptr[nrows];
+    if (nnz && !indices) return fail(GSIM_ERR_INVALID, "NULL indices");
+    for (uint64_t e = 0; e < nnz; e++)
+        if (indices[e] >= nrows) return fail(GSIM_ERR_INVALID, "column index outside the graph");
+    try {
+        std::vector<uint32_t> parent(nrows);
+        for (uint64_t r = 0; r < nrows; r++) parent[r] = static_cast<uint32_t>(r);
+        for (uint64_t r = 0; r < nrows; r++)
+            for (uint64_t e = indptr[r]; e < indptr[r + 1]; e++) {
+                const uint32_t x = host_root(parent, static_cast<uint32_t>(r)), y = host_root(parent, indices[e]);
+                if (x != y) parent[std::max(x, y)] = std::min(x, y);
+            }
+        // rows ascending: a root comes before every other row of its component and takes the next number
+        uint32_t nc = 0;
+        for (uint64_t r = 0; r < nrows; r++) {
+            const uint32_t root = host_root(parent, static_cast<uint32_t>(r));
+            if (root == r) {
+                component_of[r] = nc;
+                if (first_row) first_row[nc] = static_cast<uint32_t>(r);
+                if (sizes) sizes[nc] = 1;
+                nc++;
+            } else {
+                component_of[r] = component_of[root];
+                if (sizes) sizes[component_of[root]]++;
+            }
+        }
+        *ncomponents = nc;
+    } catch (const std::bad_alloc&) {
+        return fail(GSIM_ERR_NOMEM, "components");
+    }
+    return GSIM_OK;
+}
+
+} // extern "C"

@@ -26,7 +26,13 @@ uint64_t launch_tile_budget(uint32_t WP)
 
 std::vector<NbrLaunch> plan_launches(uint64_t nlt, uint64_t nct, bool tri, uint32_t WP)
 {
-    const uint64_t max_tiles = launch_tile_budget(WP);
+    return plan_launches(nlt, nct, tri, WP, 0);
+}
+
+std::vector<NbrLaunch> plan_launches(uint64_t nlt, uint64_t nct, bool tri, uint32_t WP, uint64_t pair_budget)
+{
+    const uint64_t tile_pairs = static_cast<uint64_t>(gsim::kNbrTile) * gsim::kNbrTile;
+    const uint64_t max_tiles = pair_budget ? std::max<uint64_t>(1, pair_budget / tile_pairs) : launch_tile_budget(WP);
     std::vector<NbrLaunch> out;
     uint64_t rt = 0;
     while (rt < nlt) {

@@ -28,6 +28,8 @@ struct NbrLaunch {
 uint64_t launch_tile_budget(uint32_t WP);
 // Tile launches of a call over nlt tile rows x nct tile columns (rows of WP words), each within the work budget.
 std::vector<NbrLaunch> plan_launches(uint64_t nlt, uint64_t nct, bool tri, uint32_t WP);
+// ... each of at most pair_budget pairs instead (at least one tile; 0: the work budget) -- gsim_db_components' knob
+std::vector<NbrLaunch> plan_launches(uint64_t nlt, uint64_t nct, bool tri, uint32_t WP, uint64_t pair_budget);
 
 // Where a launch appends: the shard's pair buffer as it is now
 struct PairSink {

@@ -221,6 +221,9 @@ struct Knobs {
     long long scores_stage_bytes = 256ll << 20; // GSIM_SCORES_STAGE_BYTES  device staging of the host-output calls: a slab of whole left rows of
                                      // at most this many bytes (at least one row) is computed, then copied out.  The result does not
                                      // depend on it
+    long long components_launch_pairs = 0; // GSIM_COMPONENTS_LAUNCH_PAIRS  a launch of gsim_db_components' tile kernel scores at most this
+                                     // many pairs (at least one 256 x 256 tile); 0: the neighbour lists' launch plan (capi_pairs.cpp;
+                                     // DESIGN.md section 18).  The result does not depend on it
 };
 
 ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll, bool ragged = true);
@@ -386,6 +389,33 @@ hipError_t nbr_sort_bytes(uint64_t n, uint32_t end_bit, size_t* bytes);
 hipError_t launch_nbr_csr(void* tmp, size_t tmp_bytes, const unsigned long long* keys, const float* vals, unsigned long long* keys_sorted,
                           float* vals_sorted, uint64_t n, uint32_t end_bit, uint64_t nrows_out, uint32_t row_base, uint64_t* indptr,
                           uint32_t* indices, hipStream_t s);
+
+// ---- single-linkage clustering: connected components of the threshold graph (gsim_components.hip, gsim_db_components) -----
+constexpr uint32_t kCompMaxLevels = 8; // GSIM_COMPONENTS_MAX_LEVELS
+constexpr uint32_t kCompKept = 0, kCompUnions = 1, kCompCasFailed = 2, kCompCounters = 3; // CompArgs::counters
+struct CompArgs {
+    const uint32_t* rows;        // nrows x WP words, 16-byte aligned (the table itself when W == WP, else a zero-padded copy)
+    const uint32_t* pop;         // popc of every row
+    uint64_t nrows;
+    uint32_t WP;                 // words per row as the kernel reads them (4, 8, ... 128)
+    uint32_t nlevels;            // 1 ... kCompMaxLevels
+    int metric;
+    float alpha, beta;
+    float cutoffs[kCompMaxLevels]; // ascending; [0 .. nlevels)
+    uint32_t* parent;            // nlevels forests of nrows words (the protocol: gsim_components.hip)
+    unsigned long long* counters; // kCompCounters words, added to
+    unsigned long long* clk;     // as NbrArgs::clk
+};
+hipError_t launch_comp_init(uint32_t* parent, uint64_t nrows, uint32_t nlevels, hipStream_t s);
+// tiles (rt0 .. rt0+nrt-1) x (ct0 .. ct0+nct-1) of the upper triangle, as launch_nbr_tiles with tri = 1
+hipError_t launch_comp_tiles(const CompArgs& a, uint32_t rt0, uint32_t nrt, uint32_t ct0, uint32_t nct, hipStream_t s);
+hipError_t launch_comp_flatten(uint32_t* parent, uint64_t nrows, uint32_t nlevels, hipStream_t s);
+hipError_t comp_scan_bytes(uint64_t nrows, size_t* bytes);
+// one flattened forest -> component_of[nrows], *ncomponents, first_row / sizes (or nullptr; sizes zeroed before) -- flag, num: nrows
+// words of scratch each
+hipError_t launch_comp_label(void* tmp, size_t tmp_bytes, const uint32_t* parent, uint64_t nrows, uint32_t row_base, uint32_t* flag,
+                             uint32_t* num, uint32_t* component_of, uint32_t* first_row, uint32_t* sizes, uint32_t* ncomponents,
+                             hipStream_t s);
 
 // ---- exact k-nearest-neighbour lists of the table's own rows (gsim_knn.hip, gsim_db_knn) ----------------------------------
 constexpr int kKnnTile = 256;   // owner rows of one workgroup

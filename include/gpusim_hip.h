@@ -758,6 +758,61 @@ int gsim_db_scores_device(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint6
                           uint64_t rrow_begin, uint64_t rrow_end, int metric, float alpha, float beta,
                           void* d_out /* memory of the table's device */, uint64_t ld, gsim_scores_stats* stats);
 
+/* ---- single-linkage clustering: the connected components of the threshold graph -------------------------------------------------- */
+/* gsim_db_components clusters a single-shard, unfolded handle with N rows by single linkage: the connected components of the graph
+ * "score >= cutoff", at up to GSIM_COMPONENTS_MAX_LEVELS cutoffs in ONE pass over the pairs (a single-linkage dendrogram cut at those
+ * levels; leakage-free train / test splits, analog series, de-duplication at 1.0; no counterpart in the reference).  None of the graph
+ * is stored: every kept pair feeds a union-find forest in device memory, and the answer is N labels per level.
+ * THE RULE:
+ *   - pair score: score(i, j) is bit for bit the `score` gsim_db_search returns for query = row i against row j; NaN (0 / 0) is never
+ *     >= a cutoff: an all-zero row is a singleton at every level, non-zero duplicates join at 1.0.  Metrics: GSIM_METRIC_TANIMOTO, and
+ *     GSIM_METRIC_TVERSKY with alpha == beta, finite and >= 0 (gsim_db_neighbors' metrics: symmetric bit for bit, for the reason given
+ *     there);
+ *   - cutoffs: cutoffs[0] < cutoffs[1] < ..., each in (0, 1], 1 <= nlevels <= GSIM_COMPONENTS_MAX_LEVELS; level 0 is the loosest;
+ *   - the partition at level l: the connected components of the graph on the N rows whose edges are the pairs i != j with
+ *     score(i, j) >= cutoffs[l];
+ *   - numbering: the components of a level are numbered 0, 1, ... in ascending order of their smallest row;
+ *   - outputs: component_of[l * N + i] is the number of row i's component at level l; ncomponents[l] their count; first_row[l * N + c]
+ *     (or NULL) component c's smallest row plus the handle's row base; sizes[l * N + c] (or NULL) its member count.  The entries at and
+ *     after ncomponents[l] of a first_row / sizes stripe are left untouched.
+ * Consequences: level l + 1 refines level l; a single-level call and the matching stripe of a multi-level call are byte-identical; the
+ * output is byte-identical from run to run and does not depend on how the pass is cut into launches (GSIM_COMPONENTS_LAUNCH_PAIRS,
+ * read once per handle); the partition at level l equals gsim_components applied to gsim_db_neighbors(cutoffs[l])'s
+ * CSR.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / cutoffs / component_of / ncomponents, nlevels outside [1, 8], a cutoff
+ * outside (0, 1] or NaN, cutoffs not strictly ascending, an unknown metric, asymmetric weights or weights that are negative or not
+ * finite, rows wider than 4096 bits, N >= 2^32.  N == 0: GSIM_OK, every ncomponents[l] = 0.  GSIM_ERR_STATE: a table not on a GPU, a
+ * multi-shard handle, a folded table.  GSIM_ERR_NOMEM as elsewhere, nothing leaked.
+ * Execution: on the handle's stream under the one-call-at-a-time rule; the search state is left as it was found.  Device memory of the
+ * call, allocated and freed by it: 4 B x N x nlevels for the forests, as much for each of component_of / first_row / sizes asked for,
+ * 4 B x N for popcounts, the zero-padded copy of the rows where their width is not 128, 256, ... 4096 bits (as the neighbour lists),
+ * and 8 B x N of label scratch plus the scan's. */
+#define GSIM_COMPONENTS_MAX_LEVELS 8u
+typedef struct {
+    uint64_t rows;       /* N                                                                                                  */
+    uint64_t levels;     /* nlevels                                                                                            */
+    uint64_t launches;   /* launches of the tile kernel (each followed by one of the flatten kernel)                           */
+    uint64_t pairs;      /* pairs scored: N (N - 1) / 2                                                                        */
+    uint64_t kept;       /* pairs with score >= cutoffs[0]                                                                     */
+    uint64_t unions;     /* successful hooks = sum over levels of (N - ncomponents[l])                                         */
+    uint64_t cas_failed; /* diagnostic, NOT reproducible: compare-and-swaps that lost a race                                   */
+    double kernel_ms;    /* HIP events on the handle's stream: all tile and flatten launches                                   */
+    double label_ms;     /* numbering, component_of, first_row and sizes, on the device                                        */
+    double d2h_ms;       /* outputs to the host                                                                                */
+    double wall_ms;      /* the whole call, host clock                                                                         */
+    double clock_mhz;    /* as gsim_graph_stats.clock_mhz                                                                      */
+} gsim_components_stats;
+int gsim_db_components(gsim_db* db, const float* cutoffs, uint32_t nlevels, int metric, float alpha, float beta,
+                       uint32_t* component_of /* nlevels x N */, uint32_t* ncomponents /* nlevels */,
+                       uint32_t* first_row /* nlevels x N, or NULL */, uint32_t* sizes /* nlevels x N, or NULL */,
+                       gsim_components_stats* stats /* or NULL */);
+/* The same rule on a symmetric CSR graph (host code, no device; gsim_butina's companion): the connected components of the graph,
+ * numbered in ascending order of their smallest row.  component_of[nrows]; first_row / sizes (or NULL): capacity nrows, the first
+ * *ncomponents entries written, rows without any row base.  Self edges and repeated edges are harmless.  GSIM_ERR_INVALID for a
+ * malformed graph (gsim_butina's checks); nrows == 0 is legal. */
+int gsim_components(const uint64_t* indptr, const uint32_t* indices, uint64_t nrows,
+                    uint32_t* component_of, uint32_t* first_row /* or NULL */, uint32_t* sizes /* or NULL */, uint64_t* ncomponents);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
