@@ -106,6 +106,18 @@ class GsimComponentsStats(C.Structure):
                 ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
 
 
+MST_MAX_ROUNDS = 33
+MST_EDGE_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("score", np.float32)])
+MST_MERGE_DTYPE = np.dtype([("left", np.uint32), ("right", np.uint32), ("score", np.float32), ("size", np.uint32)])
+
+
+class GsimMstStats(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("rounds", C.c_uint64), ("scans", C.c_uint64), ("launches", C.c_uint64), ("pairs", C.c_uint64),
+                ("owner_rows", C.c_uint64), ("edges", C.c_uint64), ("kernel_ms", C.c_double), ("round_ms", C.c_double),
+                ("sort_ms", C.c_double), ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double),
+                ("scan_owners", C.c_uint64 * MST_MAX_ROUNDS), ("scan_kernel_ms", C.c_double * MST_MAX_ROUNDS)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -134,6 +146,7 @@ EXPORTS = [
     "gsim_db_histogram_queries", "gsim_db_histogram",
     "gsim_db_scores", "gsim_db_scores_queries", "gsim_db_scores_device",
     "gsim_db_components", "gsim_components",
+    "gsim_db_mst", "gsim_mst", "gsim_mst_linkage", "gsim_mst_cut",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -246,6 +259,10 @@ def load():
         "gsim_db_components": (C.c_int, [vp, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.c_float, C.c_float, u32p, u32p, u32p, u32p,
                                          C.POINTER(GsimComponentsStats)]),
         "gsim_components": (C.c_int, [u64p, u32p, C.c_uint64, u32p, u32p, u32p, u64p]),
+        "gsim_db_mst": (C.c_int, [vp, C.c_float, C.c_int, C.c_float, C.c_float, vp, u64p, C.POINTER(GsimMstStats)]),
+        "gsim_mst": (C.c_int, [u64p, u32p, C.POINTER(C.c_float), C.c_uint64, vp, u64p]),
+        "gsim_mst_linkage": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp]),
+        "gsim_mst_cut": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_float, u32p, u32p, u32p, u64p]),
         "gsim_last_error": (C.c_char_p, []),
         "gsim_version": (C.c_char_p, []),
     }
@@ -618,6 +635,20 @@ class Table:
                   for l in range(nl)]
         return levels, {f: getattr(st, f) for f, _ in GsimComponentsStats._fields_}
 
+    def mst(self, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0):
+        """gsim_db_mst: the single-linkage dendrogram as its maximum-similarity spanning forest -> (edges, stats dict); edges is a
+        structured array (MST_EDGE_DTYPE: a < b with the row base added, score) in order E = (score descending, a, b); the per-scan
+        arrays of the stats are cut to the scans made."""
+        n = self.count()
+        edges = np.empty(max(n - 1, 1), dtype=MST_EDGE_DTYPE)
+        ne = C.c_uint64(0)
+        st = GsimMstStats()
+        check(self._L.gsim_db_mst(self._h, cutoff, metric, alpha, beta, edges.ctypes.data, C.byref(ne), C.byref(st)))
+        stats = {f: getattr(st, f) for f, _ in GsimMstStats._fields_[:-2]}
+        stats["scan_owners"] = list(st.scan_owners)[:st.scans]
+        stats["scan_kernel_ms"] = list(st.scan_kernel_ms)[:st.scans]
+        return edges[:ne.value].copy(), stats
+
     def rowset(self, rows=None, bitmap=None, exclude=False) -> RowSet:
         """gsim_rowset_from_rows / _from_bitmap: `rows` are row indices including the row base (gsim_hit.row values), any order,
         duplicates collapse; `bitmap` is (count + 31) // 32 uint32 words, bit r % 32 of word r // 32 selecting row r without the
@@ -780,6 +811,49 @@ def components(indptr, indices, nrows=None):
     nc = C.c_uint64(0)
     check(load().gsim_components(indptr.ctypes.data_as(C.POINTER(C.c_uint64)), _u32(indices), n, _u32(component_of), _u32(first_row),
                                  _u32(sizes), C.byref(nc)))
+    return component_of, first_row[:nc.value].copy(), sizes[:nc.value].copy()
+
+
+def _mst_edges(edges):
+    edges = np.ascontiguousarray(edges, dtype=MST_EDGE_DTYPE).reshape(-1)
+    return edges, (edges.ctypes.data if len(edges) else None)
+
+
+def mst(indptr, indices, scores, nrows=None):
+    """gsim_mst (host code): the rule of gsim_db_mst on a symmetric scored CSR graph (Table.neighbors' output) -> edges
+    (MST_EDGE_DTYPE, rows without any row base) in order E."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.uint64)
+    indices = np.ascontiguousarray(indices, dtype=np.uint32)
+    scores = np.ascontiguousarray(scores, dtype=np.float32)
+    n = len(indptr) - 1 if nrows is None else int(nrows)
+    if n < 0 or len(indptr) < n + 1 or len(scores) != len(indices):
+        raise GsimError(-1, "indptr needs nrows + 1 entries, scores one per index")
+    edges = np.empty(max(n - 1, 1), dtype=MST_EDGE_DTYPE)
+    ne = C.c_uint64(0)
+    check(load().gsim_mst(indptr.ctypes.data_as(C.POINTER(C.c_uint64)), _u32(indices), scores.ctypes.data_as(C.POINTER(C.c_float)), n,
+                          edges.ctypes.data, C.byref(ne)))
+    return edges[:ne.value].copy()
+
+
+def mst_linkage(edges, nrows):
+    """gsim_mst_linkage (host code): the dendrogram of a forest in order E (rows without any row base) -> merges (MST_MERGE_DTYPE), one
+    per edge; a row is cluster `row`, merge m creates cluster nrows + m, `left` holds the smaller smallest row."""
+    edges, ptr = _mst_edges(edges)
+    merges = np.empty(max(len(edges), 1), dtype=MST_MERGE_DTYPE)
+    check(load().gsim_mst_linkage(ptr, len(edges), int(nrows), merges.ctypes.data))
+    return merges[:len(edges)].copy()
+
+
+def mst_cut(edges, nrows, t):
+    """gsim_mst_cut (host code): the components of the edges with score >= t -> (component_of uint32 [n], first_row uint32
+    [ncomponents], sizes uint32 [ncomponents]), as `components`."""
+    edges, ptr = _mst_edges(edges)
+    n = int(nrows)
+    component_of = np.empty(n, dtype=np.uint32)
+    first_row = np.empty(max(n, 1), dtype=np.uint32)
+    sizes = np.empty(max(n, 1), dtype=np.uint32)
+    nc = C.c_uint64(0)
+    check(load().gsim_mst_cut(ptr, len(edges), n, t, _u32(component_of), _u32(first_row), _u32(sizes), C.byref(nc)))
     return component_of, first_row[:nc.value].copy(), sizes[:nc.value].copy()
 
 

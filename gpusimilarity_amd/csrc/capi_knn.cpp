@@ -7,13 +7,6 @@
 
 namespace gsim_host
 {
-namespace
-{
-
-struct KnnLaunch {
-    uint32_t ot0, not_; // owner tiles
-    uint64_t c0, c1;    // candidate rows
-};
 
 // The fold launches of a call over `not_total` owner tiles and N candidate rows of WP words.  The fold kernel's unit of
 // parallelism is the owner tile alone (a workgroup walks every candidate of its launch), so a launch takes as many owner tiles as
@@ -44,6 +37,9 @@ std::vector<KnnLaunch> plan_knn(uint64_t nout, uint64_t N, uint32_t WP, long lon
     }
     return out;
 }
+
+namespace
+{
 
 int knn(gsim_db* db, Shard& s, uint32_t k, float cutoff, int metric, float alpha, float beta, uint64_t rb, uint64_t re, gsim_graph* g)
 {

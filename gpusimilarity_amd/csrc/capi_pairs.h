@@ -31,6 +31,13 @@ std::vector<NbrLaunch> plan_launches(uint64_t nlt, uint64_t nct, bool tri, uint3
 // ... each of at most pair_budget pairs instead (at least one tile; 0: the work budget) -- gsim_db_components' knob
 std::vector<NbrLaunch> plan_launches(uint64_t nlt, uint64_t nct, bool tri, uint32_t WP, uint64_t pair_budget);
 
+// The fold launches of gsim_db_knn and gsim_db_mst over nout owner rows x N candidate rows (capi_knn.cpp has the rule)
+struct KnnLaunch {
+    uint32_t ot0, not_; // owner tiles
+    uint64_t c0, c1;    // candidate rows
+};
+std::vector<KnnLaunch> plan_knn(uint64_t nout, uint64_t N, uint32_t WP, long long pairs);
+
 // Where a launch appends: the shard's pair buffer as it is now
 struct PairSink {
     unsigned long long* keys;

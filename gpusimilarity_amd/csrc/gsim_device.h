@@ -224,6 +224,9 @@ struct Knobs {
     long long components_launch_pairs = 0; // GSIM_COMPONENTS_LAUNCH_PAIRS  a launch of gsim_db_components' tile kernel scores at most this
                                      // many pairs (at least one 256 x 256 tile); 0: the neighbour lists' launch plan (capi_pairs.cpp;
                                      // DESIGN.md section 18).  The result does not depend on it
+    long long mst_launch_pairs = 0;  // GSIM_MST_LAUNCH_PAIRS    a launch of gsim_db_mst's fold kernel scores at most this many owner x candidate
+                                     // pairs (at least one column tile of 256 candidates); 0: as knn_launch_pairs (capi_mst.cpp;
+                                     // DESIGN.md section 19).  The result does not depend on it
 };
 
 ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll, bool ragged = true);
@@ -448,6 +451,52 @@ hipError_t launch_knn_offsets(void* tmp, size_t tmp_bytes, const uint32_t* len, 
 // every held entry to its place: indices (+ row_base) and scores
 hipError_t launch_knn_compact(const KnnEntry* lists, const uint32_t* len, const uint64_t* indptr, uint64_t nown, uint32_t k, uint32_t row_base,
                               uint32_t* indices, float* scores, hipStream_t s);
+
+// ---- exact single-linkage dendrograms: the maximum-similarity spanning forest (gsim_mst.hip, gsim_db_mst) -------------------
+// Boruvka rounds.  The fold kernel is knn_fold_kernel's scheme (kKnnTile owners to a workgroup, kKnnBlock threads) with the list
+// replaced by one 64-bit word per row; the owners of a round come through an index list.
+constexpr unsigned long long kMstNone = 0ull; // best[i]: (score bits << 32) | ~partner -- larger is earlier in order E; 0: none held
+constexpr uint32_t kMstCtlEdges = 0, kMstCtlOwners = 1, kMstCtlRoots = 2, kMstCtlWords = 3; // MstState::ctl
+struct MstArgs {
+    const uint32_t* rows;        // nrows x WP words, 16-byte aligned (the table itself when W == WP, else a zero-padded copy)
+    const uint32_t* pop;         // popc of every row
+    const uint32_t* comp;        // component id of every row (a row of the component)
+    const uint32_t* own;         // the round's owners: nown table rows, ascending
+    uint64_t nrows;
+    uint32_t nown;
+    uint32_t WP;                 // words per row as the kernel reads them (4, 8, ... 128)
+    int metric;
+    float alpha, beta, cutoff;
+    unsigned long long* best;    // nrows words, kMstNone for every owner before the round's first launch
+    unsigned long long* clk;     // as KnnArgs.clk
+};
+// Owner tiles ot0 .. ot0 + not_ - 1 of the list (tile t = owners t * kKnnTile ..) fold the candidate rows [c0, c1), cut into
+// nchunk pieces that run side by side, into best[].  Launch order and the cut play no part in the result.
+hipError_t launch_mst_fold(const MstArgs& a, uint32_t ot0, uint32_t not_, uint64_t c0, uint64_t c1, uint32_t nchunk, hipStream_t s);
+struct MstState {
+    uint64_t nrows;
+    uint32_t* comp;              // nrows
+    uint32_t* parent;            // nrows, indexed by component id
+    uint32_t* own;               // nrows: the next round's owner list
+    uint32_t* flag;              // nrows
+    uint32_t* cscore;            // nrows, per component id: the best held score's bits
+    unsigned long long* best;    // nrows
+    unsigned long long* ckey;    // nrows, per component id: (a << 32) | b of its E-first edge
+    unsigned long long* ekey;    // cap: (~score bits << 32) | a of every edge taken so far
+    uint32_t* eb;                // cap: its b
+    uint64_t cap;                // nrows - 1
+    unsigned long long* ctl;     // kMstCtlWords: edges taken so far, owners of the next round, roots (mst_count_roots)
+};
+hipError_t launch_mst_init(const MstState& m, hipStream_t s); // comp = parent = own = identity, best = none, ctl = 0
+hipError_t mst_select_bytes(uint64_t nrows, size_t* bytes);
+// One round's bookkeeping after its fold launches: every component's E-first held edge, the edges appended (each once), the
+// components merged and flattened, and the next round's owner list (ctl[kMstCtlOwners] rows of own[], their best[] reset).
+hipError_t launch_mst_round(const MstState& m, void* tmp, size_t tmp_bytes, hipStream_t s);
+hipError_t launch_mst_count_roots(const MstState& m, hipStream_t s);
+hipError_t mst_sort_bytes(uint64_t n, size_t* bytes);
+// the n edges taken, in order E, as gsim_mst_edge (12 bytes: a + row_base, b + row_base, score); ekey2 / eb2: n words of scratch
+hipError_t launch_mst_sort(const MstState& m, uint64_t n, void* tmp, size_t tmp_bytes, unsigned long long* ekey2, uint32_t* eb2,
+                           uint32_t row_base, void* edges, hipStream_t s);
 
 // ---- similarity histograms (gsim_hist.hip, gsim_db_histogram / gsim_db_histogram_queries) ----------------------------------
 constexpr int kHistTile = 256;           // owner (left) rows of one workgroup of the owner-tile kernel

@@ -813,6 +813,80 @@ int gsim_db_components(gsim_db* db, const float* cutoffs, uint32_t nlevels, int 
 int gsim_components(const uint64_t* indptr, const uint32_t* indices, uint64_t nrows,
                     uint32_t* component_of, uint32_t* first_row /* or NULL */, uint32_t* sizes /* or NULL */, uint64_t* ncomponents);
 
+/* ---- exact single-linkage dendrograms: the maximum-similarity spanning forest ---------------------------------------------------- */
+/* gsim_db_mst returns the single-linkage dendrogram of a single-shard, unfolded handle with N rows as its maximum-similarity spanning
+ * forest: at most N - 1 edges, from which every cut (gsim_mst_cut), the merge tree (gsim_mst_linkage), HDBSCAN-style stability and
+ * "cut where the gap is largest" follow without another pass over the pairs (no counterpart in the reference).  Built by Boruvka
+ * rounds on the device; none of the graph is stored: memory is O(N).
+ * THE RULE:
+ *   - table and metrics: N < 2^32 rows of at most 4096 bits; gsim_db_components' metrics: GSIM_METRIC_TANIMOTO, and GSIM_METRIC_TVERSKY
+ *     with alpha == beta, finite and >= 0 (symmetric bit for bit).  cutoff in (0, 1]; the smallest positive float means "every pair
+ *     that shares a bit";
+ *   - score: score(i, j) is bit for bit the `score` gsim_db_search returns; NaN (0 / 0) is never >= cutoff: an all-zero row is isolated;
+ *   - edges: the pairs a < b with score(a, b) >= cutoff, in the strict total ORDER E: (score descending, a ascending, b ascending);
+ *   - result: the spanning forest Kruskal builds when it takes the edges in order E and keeps an edge iff its ends are not yet
+ *     connected.  E is total, so this forest is unique; it is also exactly what Boruvka finds when every component takes its E-first
+ *     outgoing edge;
+ *   - output: *nedges = N - (the number of components at `cutoff`); edges[0 .. *nedges) with a < b, the handle's row base added to
+ *     both, sorted in order E.  The output is byte-identical from run to run and does not depend on how the work is cut into launches
+ *     (GSIM_MST_LAUNCH_PAIRS, read once per handle).
+ * Consequence: for any t >= cutoff, the edges with score >= t connect exactly the components of gsim_db_components at t (gsim_mst_cut
+ * gives its labels byte for byte), and gsim_db_mst equals gsim_mst applied to gsim_db_neighbors(cutoff)'s CSR.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / nedges, NULL edges with N > 1, a cutoff outside (0, 1] or NaN, an unknown
+ * metric, asymmetric weights or weights that are negative or not finite, rows wider than 4096 bits, N >= 2^32.  N == 0: GSIM_OK,
+ * *nedges = 0.  GSIM_ERR_STATE: a table not on a GPU, a multi-shard handle, a folded table (N == 1 on a resident table: GSIM_OK, no
+ * edges); more than ceil(log2 N) + 1 rounds or an edge count that differs from N minus the final component count (neither can happen).
+ * GSIM_ERR_NOMEM as elsewhere, nothing leaked.
+ * Execution: on the handle's stream under the one-call-at-a-time rule; the search state is left as it was found.  The host waits for
+ * one small read per round.  Device memory of the call, allocated and freed by it: 60 B x N (component ids and links, the owner list and its flags, 8 B
+ * per row of held edge, the per-component picks, which the sort reuses, and the edges twice: as keys and as the 12-byte output), 4 B x N for popcounts, the zero-padded copy
+ * of the rows where their width is not 128, 256, ... 4096 bits, and the select's and the sort's scratch. */
+#define GSIM_MST_MAX_ROUNDS 33u /* ceil(log2 N) + 1 for N < 2^32 */
+typedef struct {
+    uint32_t a, b; /* a < b, row base added */
+    float score;
+} gsim_mst_edge;
+typedef struct {
+    uint64_t rows;       /* N                                                                                                     */
+    uint64_t rounds;     /* Boruvka rounds that added edges                                                                       */
+    uint64_t scans;      /* rounds whose owners were scanned: `rounds`, plus one when a last scan had to find that nothing is left */
+    uint64_t launches;   /* launches of the fold kernel                                                                           */
+    uint64_t pairs;      /* owner x candidate pairs handed to the fold kernel: N x the sum of scan_owners, the last scan included */
+    uint64_t owner_rows; /* the sum over the `rounds` of their owner list's length (round 1: N); without the list: rounds x N     */
+    uint64_t edges;      /* *nedges                                                                                               */
+    double kernel_ms;    /* HIP events on the handle's stream: all fold launches                                                  */
+    double round_ms;     /* ... the rounds' bookkeeping                                                                           */
+    double sort_ms;      /* ... the component count and the edges' sort                                                           */
+    double d2h_ms;       /* edges to the host                                                                                     */
+    double wall_ms;      /* the whole call, host clock                                                                            */
+    double clock_mhz;    /* as gsim_graph_stats.clock_mhz                                                                         */
+    uint64_t scan_owners[GSIM_MST_MAX_ROUNDS];  /* per scan: owner rows                                                           */
+    double scan_kernel_ms[GSIM_MST_MAX_ROUNDS]; /* per scan: its fold launches                                                    */
+} gsim_mst_stats;
+int gsim_db_mst(gsim_db* db, float cutoff, int metric, float alpha, float beta,
+                gsim_mst_edge* edges /* capacity N - 1 */, uint64_t* nedges, gsim_mst_stats* stats /* or NULL */);
+/* The same rule on a symmetric scored CSR graph (host code, no device; gsim_components' companion), e.g. gsim_db_neighbors' output: plain
+ * Kruskal in order E over the pairs the CSR lists (under either row or both; self edges and repeated pairs are harmless).  edges:
+ * capacity nrows - 1, rows without any row base.  GSIM_ERR_INVALID for a malformed graph (gsim_components' checks) or a NaN score;
+ * nrows == 0 is legal. */
+int gsim_mst(const uint64_t* indptr, const uint32_t* indices, const float* scores, uint64_t nrows,
+             gsim_mst_edge* edges, uint64_t* nedges);
+/* The dendrogram of a forest in order E (rows without any row base): merges[m] joins the clusters holding edges[m].a and edges[m].b at
+ * edges[m].score.  Cluster ids: a row is its own index, merge m creates id nrows + m (scipy's linkage numbering); `left` is the cluster
+ * holding the smaller smallest row, `size` the new cluster's row count.  GSIM_ERR_INVALID: NULL arguments, nedges >= nrows (nedges > 0),
+ * an edge with a >= b or b >= nrows or a NaN score, a score above its predecessor's, an edge whose ends are already connected. */
+typedef struct {
+    uint32_t left, right;
+    float score;
+    uint32_t size;
+} gsim_mst_merge;
+int gsim_mst_linkage(const gsim_mst_edge* edges, uint64_t nedges, uint64_t nrows, gsim_mst_merge* merges /* nedges */);
+/* The labels at any t: the connected components of the edges with score >= t, numbered in ascending order of their smallest row --
+ * gsim_components' output contract (component_of[nrows]; first_row / sizes or NULL: capacity nrows, *ncomponents entries written).  The
+ * edges may come in any order.  GSIM_ERR_INVALID: NULL arguments, an edge with b >= nrows or a >= b, a NaN t. */
+int gsim_mst_cut(const gsim_mst_edge* edges, uint64_t nedges, uint64_t nrows, float t,
+                 uint32_t* component_of, uint32_t* first_row /* or NULL */, uint32_t* sizes /* or NULL */, uint64_t* ncomponents);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
