@@ -118,6 +118,15 @@ class GsimMstStats(C.Structure):
                 ("scan_owners", C.c_uint64 * MST_MAX_ROUNDS), ("scan_kernel_ms", C.c_double * MST_MAX_ROUNDS)]
 
 
+PROFILE_STREAMED, PROFILE_GATHERED, PROFILE_MATRIX, PROFILE_VALU = 1, 2, 4, 8
+ISIM_TANIMOTO, ISIM_RUSSELL_RAO, ISIM_SIMPLE_MATCHING = 0, 1, 2
+
+
+class GsimProfileStats(C.Structure):
+    _fields_ = [("rows_read", C.c_uint64), ("rows_counted", C.c_uint64), ("launches", C.c_uint64), ("route", C.c_uint64),
+                ("kernel_ms", C.c_double), ("d2h_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -147,6 +156,7 @@ EXPORTS = [
     "gsim_db_scores", "gsim_db_scores_queries", "gsim_db_scores_device",
     "gsim_db_components", "gsim_components",
     "gsim_db_mst", "gsim_mst", "gsim_mst_linkage", "gsim_mst_cut",
+    "gsim_db_bit_counts", "gsim_db_overlap_sums", "gsim_isim", "gsim_isim_complement",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -263,6 +273,10 @@ def load():
         "gsim_mst": (C.c_int, [u64p, u32p, C.POINTER(C.c_float), C.c_uint64, vp, u64p]),
         "gsim_mst_linkage": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp]),
         "gsim_mst_cut": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_float, u32p, u32p, u32p, u64p]),
+        "gsim_db_bit_counts": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, u64p, u64p, C.POINTER(GsimProfileStats)]),
+        "gsim_db_overlap_sums": (C.c_int, [vp, u32p, C.c_uint64, C.c_uint64, u64p, u32p, C.POINTER(GsimProfileStats)]),
+        "gsim_isim": (C.c_int, [u64p, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
+        "gsim_isim_complement": (C.c_int, [u64p, C.c_uint32, C.c_uint64, C.c_int, u64p, u32p, C.c_uint64, C.POINTER(C.c_double)]),
         "gsim_last_error": (C.c_char_p, []),
         "gsim_version": (C.c_char_p, []),
     }
@@ -649,6 +663,38 @@ class Table:
         stats["scan_kernel_ms"] = list(st.scan_kernel_ms)[:st.scans]
         return edges[:ne.value].copy(), stats
 
+    def bit_counts(self, rowset=None, row_begin=0, row_end=None, stats=None):
+        """gsim_db_bit_counts: how many of the counted rows have each bit set -> (counts uint64 [fp_bits], counted int).  The counted
+        rows are the rows of [row_begin, row_end) (indices without the row base) that are in `rowset` (a :class:`RowSet` of this
+        table), or all of them.  Bit k is bit k % 32 of word k // 32.  `stats`: a dict that receives the call's gsim_profile_stats."""
+        if row_end is None:
+            row_end = self.count()
+        counts = np.zeros(self.fp_bits, dtype=np.uint64)
+        counted = C.c_uint64(0)
+        st = GsimProfileStats()
+        check(self._L.gsim_db_bit_counts(self._h, rowset._h if rowset is not None else None, row_begin, row_end,
+                                         counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(counted), C.byref(st)))
+        if stats is not None:
+            stats.update({f: getattr(st, f) for f, _ in GsimProfileStats._fields_})
+        return counts, counted.value
+
+    def overlap_sums(self, weights, row_begin=0, row_end=None, popc=False, stats=None):
+        """gsim_db_overlap_sums: for every row of [row_begin, row_end) the sum of weights[k] over its set bits k -> sums uint64
+        [row_end - row_begin], or (sums, popc uint32) with popc=True.  `weights`: fp_bits non-negative integers below 2^32 -- the
+        counts of :meth:`bit_counts` as they are; anything larger is refused.  `stats`: as :meth:`bit_counts`."""
+        if row_end is None:
+            row_end = self.count()
+        w = _weights32(weights, self.fp_bits)
+        n = max(row_end - row_begin, 0)
+        sums = np.zeros(max(n, 1), dtype=np.uint64)
+        pc = np.zeros(max(n, 1), dtype=np.uint32) if popc else None
+        st = GsimProfileStats()
+        check(self._L.gsim_db_overlap_sums(self._h, _u32(w), row_begin, row_end, sums.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                           _u32(pc) if popc else None, C.byref(st)))
+        if stats is not None:
+            stats.update({f: getattr(st, f) for f, _ in GsimProfileStats._fields_})
+        return (sums[:n], pc[:n]) if popc else sums[:n]
+
     def rowset(self, rows=None, bitmap=None, exclude=False) -> RowSet:
         """gsim_rowset_from_rows / _from_bitmap: `rows` are row indices including the row base (gsim_hit.row values), any order,
         duplicates collapse; `bitmap` is (count + 31) // 32 uint32 words, bit r % 32 of word r // 32 selecting row r without the
@@ -855,6 +901,41 @@ def mst_cut(edges, nrows, t):
     nc = C.c_uint64(0)
     check(load().gsim_mst_cut(ptr, len(edges), n, t, _u32(component_of), _u32(first_row), _u32(sizes), C.byref(nc)))
     return component_of, first_row[:nc.value].copy(), sizes[:nc.value].copy()
+
+
+def _weights32(weights, fp_bits):
+    w = np.asarray(weights).reshape(-1)
+    if len(w) != fp_bits:
+        raise GsimError(-1, "weights: %d entries for %d bits" % (len(w), fp_bits))
+    if w.dtype.kind not in "ui" or (len(w) and (int(w.min()) < 0 or int(w.max()) > 0xFFFFFFFF)):
+        raise GsimError(-1, "weights must be integers in [0, 2^32)")
+    return np.ascontiguousarray(w, dtype=np.uint32)
+
+
+def isim(counts, n, index=ISIM_TANIMOTO) -> float:
+    """gsim_isim (host code): the iSIM index of a set of n rows from its column counts (Table.bit_counts' output) -- a ratio of sums
+    over all pairs, not the mean of the pairwise scores."""
+    c = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    v = C.c_double(0.0)
+    check(load().gsim_isim(c.ctypes.data_as(C.POINTER(C.c_uint64)) if len(c) else None, len(c), int(n), index, C.byref(v)))
+    return v.value
+
+
+def isim_complement(counts, n, sums, popc, index=ISIM_TANIMOTO) -> np.ndarray:
+    """gsim_isim_complement (host code): for every row i given by sums[i] (Table.overlap_sums with weights = counts) and popc[i], a
+    member of the counted set, the index of the n - 1 rows left without it -> float64 array; its argmin is the medoid, its largest
+    values are the outliers."""
+    c = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    s = np.ascontiguousarray(sums, dtype=np.uint64).reshape(-1)
+    p = np.ascontiguousarray(popc, dtype=np.uint32).reshape(-1)
+    if len(s) != len(p):
+        raise GsimError(-1, "sums and popc differ in length")
+    out = np.zeros(len(s), dtype=np.float64)
+    u64p = C.POINTER(C.c_uint64)
+    check(load().gsim_isim_complement(c.ctypes.data_as(u64p) if len(c) else None, len(c), int(n), index,
+                                      s.ctypes.data_as(u64p) if len(s) else None, _u32(p) if len(p) else None, len(s),
+                                      out.ctypes.data_as(C.POINTER(C.c_double)) if len(s) else None))
+    return out
 
 
 def litmus(test: int, workgroups: int = 256, iterations: int = 100000, device: int = 0) -> dict:

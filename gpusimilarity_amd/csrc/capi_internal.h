@@ -314,6 +314,8 @@ int enqueue_scan_tail(gsim_db* db, Shard& s, const gsim::ScanArgs& a, const gsim
                       void* out);
 // capi_subset.cpp: the candidate scratch for a scan of geometry g behind which enqueue_scan_tail runs (row sets, group queries)
 int ensure_subset_scratch(Shard& s, const gsim::ScanGeometry& g);
+// ... and its route rule (GSIM_SUBSET_GATHER_MAX_PERMILLE): gather a set of `selected` rows through its list, or stream under its bitmap?
+bool subset_gather_applies(const gsim_db* db, const Shard& s, uint64_t selected);
 // capi_batch.cpp: multi-query passes
 int enqueue_batch(gsim_db* db, Shard& s, const uint32_t* queries, uint32_t nq, uint32_t k, float cutoff, int metric, float alpha,
                   float beta, uint32_t row_base, void* results, bool allow_mfma = true);

@@ -110,11 +110,8 @@ int ensure_subset_scratch(Shard& s, const gsim::ScanGeometry& g)
     return GSIM_OK;
 }
 
-namespace
-{
-
-// gather when selected x max(row bytes, 128) x 1000 <= permille x N x row bytes
-bool gather_applies(const gsim_db* db, const Shard& s, uint64_t selected)
+// gather when selected x max(row bytes, 128) x 1000 <= permille x N x row bytes (gsim_db_bit_counts decides by the same rule)
+bool subset_gather_applies(const gsim_db* db, const Shard& s, uint64_t selected)
 {
     const uint64_t permille = static_cast<uint64_t>(db->knobs.subset_gather_max_permille);
     if (permille == 0) return false;
@@ -122,6 +119,9 @@ bool gather_applies(const gsim_db* db, const Shard& s, uint64_t selected)
     const uint64_t row_bytes = static_cast<uint64_t>(s.W) * 4u;
     return selected * std::max<uint64_t>(row_bytes, 128u) * 1000u <= permille * s.nrows * row_bytes; // (< 2^32 x 2^12 x 2^10: no overflow)
 }
+
+namespace
+{
 
 int search_rows(gsim_db* db, Shard& s, const gsim_rowset* rs, const uint32_t* queries, uint32_t nq, uint32_t kout, float cutoff, int metric,
                 float alpha, float beta, gsim_hit* hits, uint32_t* counts, uint64_t* approx, gsim_rowset_stats* st)
@@ -140,7 +140,7 @@ int search_rows(gsim_db* db, Shard& s, const gsim_rowset* rs, const uint32_t* qu
     }
     GSIM_HIP(set_device(s.device));
     const hipStream_t stream = s.stream;
-    const bool gather = gather_applies(db, s, sel);
+    const bool gather = subset_gather_applies(db, s, sel);
     const gsim::ScanGeometry g = gather ? gsim::subset_gather_geometry(sel, s.W, s.num_cus) : gsim::subset_scan_geometry(s.nrows, s.W, s.num_cus);
     int rc = ensure_subset_scratch(s, g);
     if (rc == GSIM_OK) rc = ensure_result_capacity(s, k);

@@ -227,6 +227,9 @@ struct Knobs {
     long long mst_launch_pairs = 0;  // GSIM_MST_LAUNCH_PAIRS    a launch of gsim_db_mst's fold kernel scores at most this many owner x candidate
                                      // pairs (at least one column tile of 256 candidates); 0: as knn_launch_pairs (capi_mst.cpp;
                                      // DESIGN.md section 19).  The result does not depend on it
+    long long profile_launch_rows = 0; // GSIM_PROFILE_LAUNCH_ROWS  a launch of gsim_db_bit_counts / gsim_db_overlap_sums takes at most this many
+                                     // rows (list entries on the gather route); 0: 32 GiB of rows (capi_profile.cpp; DESIGN.md section
+                                     // 20).  The result does not depend on it
 };
 
 ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll, bool ragged = true);
@@ -497,6 +500,38 @@ hipError_t mst_sort_bytes(uint64_t n, size_t* bytes);
 // the n edges taken, in order E, as gsim_mst_edge (12 bytes: a + row_base, b + row_base, score); ekey2 / eb2: n words of scratch
 hipError_t launch_mst_sort(const MstState& m, uint64_t n, void* tmp, size_t tmp_bytes, unsigned long long* ekey2, uint32_t* eb2,
                            uint32_t row_base, void* edges, hipStream_t s);
+
+// ---- per-bit column counts and weighted popcounts (gsim_profile.hip, gsim_db_bit_counts / gsim_db_overlap_sums) -------------
+constexpr int kProfileBlock = 256;
+constexpr uint32_t kProfileMaxIters = 4088; // rows one thread can add into its 12 vertical counter planes: a multiple of 8 below 2^12
+constexpr uint32_t kProfileSliceIters = 1024; // ... and the most a slice gives it
+struct ProfileCountArgs {
+    const uint32_t* rows;        // the whole table, nrows x W words (16-byte aligned rows when W % 4 == 0)
+    uint32_t W;
+    const uint32_t* bits;        // a row set's bitmap: the launch streams its rows and counts those the bitmap selects; or nullptr
+    const uint32_t* list;        // a row set's ascending list: the launch gathers entries of it; or nullptr (never both)
+    unsigned long long* counts;  // W x 32 counters + one more: the rows counted
+    uint32_t* partial;           // scratch of a launch: profile_count_blocks(num_cus) x (W x 32 + 1) words
+};
+uint32_t profile_count_blocks(int num_cus); // the most workgroups a launch has
+// One launch (the counting kernel and the reduce kernel behind it): adds the rows [i0, i1) -- with `list`, the rows
+// list[i0 .. i1) -- into counts.  Any cut of a range into launches gives the same counters (integer adds).  Launches that share
+// counts and partial go on one stream.
+hipError_t launch_profile_count(const ProfileCountArgs& a, uint64_t i0, uint64_t i1, int num_cus, hipStream_t s);
+// range[0], range[1] = the first entries of the ascending list[0 .. n) that are >= r0, >= r1
+hipError_t launch_profile_list_range(const uint32_t* list, uint32_t n, uint64_t r0, uint64_t r1, uint32_t* range, hipStream_t s);
+struct ProfileOverlapArgs {
+    const uint32_t* rows;        // as ProfileCountArgs
+    uint32_t W;
+    const uint32_t* planes;      // 32 x W words: plane b = the fingerprint of the columns whose weight has bit b set (zero from nplanes on)
+    uint32_t nplanes;            // planes the largest weight needs (1 ... 32)
+    unsigned long long* sums;    // sums[row - out0]
+    uint32_t* popc;              // popc[row - out0], or nullptr
+    uint64_t out0;
+};
+bool profile_overlap_matrix(uint32_t W); // does the matrix-core kernel take rows of W words (whole 256-bit groups)?
+// One launch over the rows [r0, r1): on the matrix cores (`matrix`, only where profile_overlap_matrix(W)) or the VALU kernel (any W <= 128)
+hipError_t launch_profile_overlap(const ProfileOverlapArgs& a, uint64_t r0, uint64_t r1, bool matrix, int num_cus, hipStream_t s);
 
 // ---- similarity histograms (gsim_hist.hip, gsim_db_histogram / gsim_db_histogram_queries) ----------------------------------
 constexpr int kHistTile = 256;           // owner (left) rows of one workgroup of the owner-tile kernel

@@ -887,6 +887,80 @@ int gsim_mst_linkage(const gsim_mst_edge* edges, uint64_t nedges, uint64_t nrows
 int gsim_mst_cut(const gsim_mst_edge* edges, uint64_t nedges, uint64_t nrows, float t,
                  uint32_t* component_of, uint32_t* first_row /* or NULL */, uint32_t* sizes /* or NULL */, uint64_t* ncomponents);
 
+/* ---- per-bit column counts and iSIM library statistics ---------------------------------------------------------------------------- */
+/* The column-wise questions about a table, a row range or a cluster (a gsim_rowset): how often is each bit set, how tight is the set,
+ * which row is its medoid, which rows are outliers.  All of them are O(N) once the per-bit column counts c_k of the set's n rows are
+ * known (iSIM: Lopez-Perez, Kim, Miranda-Quintana, "iSIM: instant similarity", Digital Discovery 2024): the sum over all pairs i < j
+ * of |x_i AND x_j| is sum_k c_k (c_k - 1) / 2, that of |x_i XOR x_j| is sum_k c_k (n - c_k).  No counterpart in the reference.
+ * WHAT THE STATISTIC IS: a ratio of sums over all pairs.  It is not the mean of the pairwise Tanimoto scores; gsim_db_histogram
+ * remains the way to the true distribution of the scores.
+ *
+ * gsim_db_bit_counts, THE RESULT RULE:
+ *   - the counted rows are the rows of [row_begin, row_end) that are in `rs`, or all of them when rs is NULL; the indices carry no
+ *     row base, as in gsim_db_knn;
+ *   - counts[k], k < fp_bits, is the number of counted rows whose bit k is set; bit k is bit k % 32 of word k / 32 of the row (the
+ *     row-set bitmap's convention); *counted (or NULL) is the number of counted rows;
+ *   - an empty range or an empty set gives GSIM_OK with zeros;
+ *   - the output is integer: byte-identical from run to run, independent of the route a row set takes (streamed under its bitmap or
+ *     gathered through its list: gsim_db_search_rows' rule and its GSIM_SUBSET_GATHER_MAX_PERMILLE, applied to the set's size and the
+ *     table's) and of how the pass is cut into launches (GSIM_PROFILE_LAUNCH_ROWS, read once per handle, 0 = automatic;
+ *     INTEGRATION.md).  The counts of ranges that partition a range add up to its counts.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / counts, row_begin > row_end or row_end past the count, a row set made
+ * for another handle, a table of 2^32 rows or more, rows wider than 4096 bits.  GSIM_ERR_STATE: a table not on a GPU (N == 0: GSIM_OK
+ * with zeros), a multi-shard handle, a folded table, a table that changed after the row set was made.  GSIM_ERR_NOMEM: the call's
+ * device memory cannot be had; nothing leaked.
+ * Execution: on the handle's stream under the one-call-at-a-time rule; the search state is left as it was found (a gsim_db_search
+ * before and after returns identical bytes).  One streaming pass over the rows read; device memory of the call: fp_bits + 1 64-bit
+ * counters, freed by the call.  Tables from gsim_db_generate and gsim_db_attach_device_rows work; no host copy is needed.
+ *
+ * gsim_db_overlap_sums, THE RESULT RULE:
+ *   - sums[i], i < row_end - row_begin, is the sum of weights[k] over the bits k set in row row_begin + i, exact in uint64 (at most
+ *     4096 x (2^32 - 1)); popc[i] (or NULL) is that row's popcount.  weights has fp_bits entries, in host memory;
+ *   - with weights = the counts of a set (they fit in 32 bits: N < 2^32) sums[i] is S_i, the row's total overlap with the set,
+ *     sum over the set's rows j of |x_i AND x_j| -- row i itself included when it is a member.  The row need not belong to the set:
+ *     "how close is every row to this cluster's profile" is the same call;
+ *   - the output is integer: byte-identical from run to run, independent of the kernel that computes it (rows of whole 256-bit groups
+ *     go through the matrix cores, every other width through a VALU kernel) and of GSIM_PROFILE_LAUNCH_ROWS.  Ranges concatenate.
+ * GSIM_ERR_INVALID: NULL db / weights, NULL sums with a non-empty range, a bad range, N >= 2^32, rows wider than 4096 bits.
+ * GSIM_ERR_STATE, GSIM_ERR_NOMEM and execution as gsim_db_bit_counts; device memory of the call: 8 bytes per row of the range (12 with
+ * popc) and the weights' 32 bit planes (fp_bits x 4 bytes), freed by the call -- ranges are how a table too long for that is done. */
+#define GSIM_PROFILE_STREAMED 1u /* gsim_profile_stats.route: the rows were streamed (under the set's bitmap, if any)   */
+#define GSIM_PROFILE_GATHERED 2u /* ... gathered through the set's list                                                  */
+#define GSIM_PROFILE_MATRIX 4u   /* ... gsim_db_overlap_sums ran on the matrix cores                                     */
+#define GSIM_PROFILE_VALU 8u     /* ... on the VALU kernel                                                               */
+typedef struct {
+    uint64_t rows_read;    /* rows the kernels visited: the range, or the set's rows in it on the gather route         */
+    uint64_t rows_counted; /* bit counts: *counted; overlap sums: the rows of the range                                 */
+    uint64_t launches;     /* kernel launches of the pass                                                               */
+    uint64_t route;        /* GSIM_PROFILE_* bits; 0 when nothing ran                                                   */
+    double kernel_ms;      /* HIP events on the handle's stream around the pass                                         */
+    double d2h_ms;         /* outputs to the host                                                                       */
+    double wall_ms;        /* the whole call, host clock                                                                */
+} gsim_profile_stats;
+int gsim_db_bit_counts(gsim_db* db, const gsim_rowset* rs /* or NULL */, uint64_t row_begin, uint64_t row_end,
+                       uint64_t* counts /* fp_bits */, uint64_t* counted /* or NULL */, gsim_profile_stats* stats /* or NULL */);
+int gsim_db_overlap_sums(gsim_db* db, const uint32_t* weights /* fp_bits */, uint64_t row_begin, uint64_t row_end,
+                         uint64_t* sums /* row_end - row_begin */, uint32_t* popc /* or NULL, same length */,
+                         gsim_profile_stats* stats /* or NULL */);
+/* The iSIM index of a set of n rows from its column counts (host code, no device, no handle).  With a = sum c_k (c_k - 1) / 2 (pairs
+ * of ones), d = sum (n - c_k) (n - c_k - 1) / 2 (pairs of zeros) and dis = sum c_k (n - c_k) (mismatches), all exact integers (128-bit:
+ * they pass 2^64 at n near 2^32 and 4096 bits), the index is numerator / denominator as listed below: each converted to double with
+ * one round-to-nearest conversion, then one double divide.  A zero denominator gives 0.0 (n < 2; a Tanimoto index over all-zero rows),
+ * as "NaN counts as 0.0" elsewhere.  Once more: a ratio of sums over all pairs, not the mean of the pairwise scores.
+ * GSIM_ERR_INVALID: NULL counts / value, fp_bits == 0, a count above n, n >= 2^32, an unknown index. */
+#define GSIM_ISIM_TANIMOTO 0        /* a / (a + dis)           */
+#define GSIM_ISIM_RUSSELL_RAO 1     /* a / (a + d + dis)       */
+#define GSIM_ISIM_SIMPLE_MATCHING 2 /* (a + d) / (a + d + dis) */
+int gsim_isim(const uint64_t* counts, uint32_t fp_bits, uint64_t n, int index, double* value);
+/* Complementary similarity: out[i], i < m, is the same index of the n - 1 rows left when row i is removed from the set; the lowest
+ * value marks the medoid, the highest the outliers.  Row i is a MEMBER of the counted set, given by sums[i] (gsim_db_overlap_sums with
+ * weights = counts) and popc[i].  With C = sum c_k: a_i = a - sums[i] + popc[i], dis_i = dis - n popc[i] - C + 2 sums[i],
+ * d_i = d - (fp_bits - popc[i]) (n - 1) + (C - sums[i]); the same conversions and divide.  GSIM_ERR_INVALID: gsim_isim's, NULL sums /
+ * popc / out with m > 0, popc[i] > fp_bits, m > 0 with n == 0, and a row whose sums / popc no member of the set can have (one of the
+ * three terms would be negative). */
+int gsim_isim_complement(const uint64_t* counts, uint32_t fp_bits, uint64_t n, int index,
+                         const uint64_t* sums, const uint32_t* popc, uint64_t m, double* out /* m */);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
