@@ -127,6 +127,26 @@ class GsimProfileStats(C.Structure):
                 ("kernel_ms", C.c_double), ("d2h_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
+LABEL_NONE = 0xFFFFFFFF  # == LEADER_NONE: gsim_db_label_counts counts the row nowhere
+ASSIGN_MAX_CENTRES = 65536
+
+
+class GsimAssignStats(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("centres", C.c_uint64), ("launches", C.c_uint64), ("pairs", C.c_uint64),
+                ("prepare_ms", C.c_double), ("kernel_ms", C.c_double), ("d2h_ms", C.c_double), ("wall_ms", C.c_double),
+                ("clock_mhz", C.c_double)]
+
+
+class GsimLabelStats(C.Structure):
+    _fields_ = [("rows_read", C.c_uint64), ("rows_counted", C.c_uint64), ("labels", C.c_uint64), ("launches", C.c_uint64),
+                ("sort_ms", C.c_double), ("kernel_ms", C.c_double), ("d2h_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+class GsimKmeansStats(C.Structure):
+    _fields_ = [("iterations", C.c_uint64), ("converged", C.c_uint64), ("changed_last", C.c_uint64), ("assign_ms", C.c_double),
+                ("counts_ms", C.c_double), ("update_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -157,6 +177,7 @@ EXPORTS = [
     "gsim_db_components", "gsim_components",
     "gsim_db_mst", "gsim_mst", "gsim_mst_linkage", "gsim_mst_cut",
     "gsim_db_bit_counts", "gsim_db_overlap_sums", "gsim_isim", "gsim_isim_complement",
+    "gsim_db_assign", "gsim_db_label_counts", "gsim_label_centroids", "gsim_db_kmeans",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -277,6 +298,12 @@ def load():
         "gsim_db_overlap_sums": (C.c_int, [vp, u32p, C.c_uint64, C.c_uint64, u64p, u32p, C.POINTER(GsimProfileStats)]),
         "gsim_isim": (C.c_int, [u64p, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
         "gsim_isim_complement": (C.c_int, [u64p, C.c_uint32, C.c_uint64, C.c_int, u64p, u32p, C.c_uint64, C.POINTER(C.c_double)]),
+        "gsim_db_assign": (C.c_int, [vp, u32p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_float, C.c_float, u32p,
+                                     C.POINTER(C.c_float), C.POINTER(GsimAssignStats)]),
+        "gsim_db_label_counts": (C.c_int, [vp, u32p, C.c_uint32, C.c_uint64, C.c_uint64, u32p, u32p, C.POINTER(GsimLabelStats)]),
+        "gsim_label_centroids": (C.c_int, [u32p, u32p, C.c_uint32, C.c_uint32, u32p, u32p]),
+        "gsim_db_kmeans": (C.c_int, [vp, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, u32p, u32p,
+                                     C.POINTER(C.c_float), u32p, C.POINTER(GsimKmeansStats)]),
         "gsim_last_error": (C.c_char_p, []),
         "gsim_version": (C.c_char_p, []),
     }
@@ -695,6 +722,64 @@ class Table:
             stats.update({f: getattr(st, f) for f, _ in GsimProfileStats._fields_})
         return (sums[:n], pc[:n]) if popc else sums[:n]
 
+    def _centres(self, centres):
+        c = np.ascontiguousarray(centres, dtype=np.uint32).reshape(-1, self.fp_bits // 32)
+        return c, (_u32(c) if len(c) else None)
+
+    def assign(self, centres, row_begin=0, row_end=None, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, stats=None):
+        """gsim_db_assign: for every row of [row_begin, row_end) the nearest of the m `centres` (m x fp_bits / 32 uint32 words) ->
+        (label uint32, score float32), both of length row_end - row_begin.  label[i] is the centre of the greatest f32
+        score(query = centre, row i), the lowest index among equal scores; an all-zero row gets (0, 0.0).  `stats`: a dict that
+        receives the call's gsim_assign_stats."""
+        if row_end is None:
+            row_end = self.count()
+        c, cp = self._centres(centres)
+        n = max(row_end - row_begin, 0)
+        label = np.zeros(max(n, 1), dtype=np.uint32)
+        score = np.zeros(max(n, 1), dtype=np.float32)
+        st = GsimAssignStats()
+        check(self._L.gsim_db_assign(self._h, cp, len(c), row_begin, row_end, metric, alpha, beta, _u32(label),
+                                     score.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st)))
+        if stats is not None:
+            stats.update({f: getattr(st, f) for f, _ in GsimAssignStats._fields_})
+        return label[:n], score[:n]
+
+    def label_counts(self, labels, nlabels, row_begin=0, row_end=None, stats=None):
+        """gsim_db_label_counts: the column counts of every label in one pass -> (counts uint32 [nlabels, fp_bits], sizes uint32
+        [nlabels]).  labels[i] is the label of row row_begin + i: below `nlabels`, or LABEL_NONE for a row that is counted nowhere
+        (the outputs of :meth:`leader`, :meth:`maxmin` with assign=True and :func:`butina` go in as they are).  Row l of counts is
+        :meth:`bit_counts` over the rows with label l; widen it to uint64 for :func:`isim`.  `stats`: a dict that receives the
+        call's gsim_label_stats."""
+        if row_end is None:
+            row_end = self.count()
+        lab = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+        if len(lab) != max(row_end - row_begin, 0):
+            raise GsimError(-1, "labels: %d entries for %d rows" % (len(lab), row_end - row_begin))
+        counts = np.zeros((max(int(nlabels), 1), self.fp_bits), dtype=np.uint32)
+        sizes = np.zeros(max(int(nlabels), 1), dtype=np.uint32)
+        st = GsimLabelStats()
+        check(self._L.gsim_db_label_counts(self._h, _u32(lab) if len(lab) else None, nlabels, row_begin, row_end, _u32(counts), _u32(sizes),
+                                           C.byref(st)))
+        if stats is not None:
+            stats.update({f: getattr(st, f) for f, _ in GsimLabelStats._fields_})
+        return counts, sizes
+
+    def kmeans(self, init, max_iter=20, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0):
+        """gsim_db_kmeans: Lloyd's iteration from the m centres `init` over the whole table -- assign, count, majority-vote centroid,
+        until the labels repeat or `max_iter` assignments were made -> (centres uint32 [m, words], label uint32 [N], score float32
+        [N], sizes uint32 [m], stats dict).  The centres returned are the ones the labels were assigned to:
+        ``assign(centres)`` reproduces label and score; an empty cluster keeps its centre."""
+        c, cp = self._centres(init)
+        n = self.count()
+        centres = np.zeros_like(c)
+        label = np.zeros(max(n, 1), dtype=np.uint32)
+        score = np.zeros(max(n, 1), dtype=np.float32)
+        sizes = np.zeros(max(len(c), 1), dtype=np.uint32)
+        st = GsimKmeansStats()
+        check(self._L.gsim_db_kmeans(self._h, cp, len(c), max_iter, metric, alpha, beta, _u32(centres) if len(c) else None, _u32(label),
+                                     score.ctypes.data_as(C.POINTER(C.c_float)), _u32(sizes), C.byref(st)))
+        return centres, label[:n], score[:n], sizes[:len(c)], {f: getattr(st, f) for f, _ in GsimKmeansStats._fields_}
+
     def rowset(self, rows=None, bitmap=None, exclude=False) -> RowSet:
         """gsim_rowset_from_rows / _from_bitmap: `rows` are row indices including the row base (gsim_hit.row values), any order,
         duplicates collapse; `bitmap` is (count + 31) // 32 uint32 words, bit r % 32 of word r // 32 selecting row r without the
@@ -935,6 +1020,27 @@ def isim_complement(counts, n, sums, popc, index=ISIM_TANIMOTO) -> np.ndarray:
     check(load().gsim_isim_complement(c.ctypes.data_as(u64p) if len(c) else None, len(c), int(n), index,
                                       s.ctypes.data_as(u64p) if len(s) else None, _u32(p) if len(p) else None, len(s),
                                       out.ctypes.data_as(C.POINTER(C.c_double)) if len(s) else None))
+    return out
+
+
+def label_centroids(counts, sizes, previous=None) -> np.ndarray:
+    """gsim_label_centroids (host code): the majority-vote centroids of Table.label_counts' output -> uint32 [nlabels, fp_bits / 32];
+    bit k of centre l is set iff 2 * counts[l, k] >= sizes[l].  An empty label keeps its row of `previous`, or is all zeros."""
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    if c.ndim != 2:
+        raise GsimError(-1, "counts must be nlabels x fp_bits")
+    z = np.ascontiguousarray(sizes, dtype=np.uint32).reshape(-1)
+    nlabels, fp_bits = c.shape
+    if len(z) != nlabels:
+        raise GsimError(-1, "sizes: %d entries for %d labels" % (len(z), nlabels))
+    out = np.zeros((nlabels, fp_bits // 32), dtype=np.uint32)
+    prev = None
+    if previous is not None:
+        prev = np.ascontiguousarray(previous, dtype=np.uint32)
+        if prev.shape != out.shape:
+            raise GsimError(-1, "previous must be nlabels x fp_bits / 32")
+    check(load().gsim_label_centroids(_u32(c) if c.size else None, _u32(z) if nlabels else None, nlabels, fp_bits,
+                                      _u32(prev) if prev is not None and prev.size else None, _u32(out) if out.size else None))
     return out
 
 

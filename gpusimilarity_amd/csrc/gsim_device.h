@@ -230,6 +230,12 @@ struct Knobs {
     long long profile_launch_rows = 0; // GSIM_PROFILE_LAUNCH_ROWS  a launch of gsim_db_bit_counts / gsim_db_overlap_sums takes at most this many
                                      // rows (list entries on the gather route); 0: 32 GiB of rows (capi_profile.cpp; DESIGN.md section
                                      // 20).  The result does not depend on it
+    long long assign_launch_pairs = 0; // GSIM_ASSIGN_LAUNCH_PAIRS  a launch of gsim_db_assign's kernel scores at most this many centre x row
+                                     // pairs (at least one block of 128 table rows against every centre); 0: by the padded row width,
+                                     // as scores_launch_pairs (capi_labels.cpp).  The result does not depend on it
+    long long labels_launch_rows = 0; // GSIM_LABELS_LAUNCH_ROWS  a launch of gsim_db_label_counts' counting kernel takes at most this many
+                                     // entries of the sorted row list; 0: 32 GiB of rows, as profile_launch_rows.  The result does not
+                                     // depend on it
 };
 
 ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll, bool ragged = true);
@@ -601,6 +607,49 @@ uint32_t scores_padded_words(uint32_t W); // 0: wider than kNbrMaxWords
 // The block of left rows [l0, l1) x table rows [r0, r1) of the call's rectangle: l0 and r0 multiples of kScoresTile, l1 and r1
 // too unless they are nl / nr; at most 65 535 x kScoresTile left rows to a launch.
 hipError_t launch_scores(const ScoresArgs& a, uint64_t l0, uint64_t l1, uint64_t r0, uint64_t r1, hipStream_t s);
+
+// ---- nearest-centre assignment (gsim_assign.hip, gsim_db_assign / gsim_db_kmeans) ------------------------------------------
+struct AssignArgs {
+    const uint32_t* centres;     // m x WP words, 16-byte aligned (zero-padded copy unless W == WP)
+    const uint32_t* rows;        // the slab's table rows: nr x WP words, likewise
+    const uint32_t* cpop;        // popc of every centre
+    const uint32_t* rpop;        // popc of every row of the slab
+    uint32_t m;                  // 1 ... GSIM_ASSIGN_MAX_CENTRES
+    uint64_t nr;
+    uint32_t WP;                 // as ScoresArgs.WP
+    int metric;
+    float alpha, beta;           // the centre is the left side: alpha weighs its bits
+    uint32_t* label;             // label[j], j < nr: the centre of the greatest f32 score, the lowest index among equals
+    float* score;                // that score (never nullptr)
+    unsigned long long* clk;     // as KnnArgs.clk
+};
+// The rows [r0, r1) of the slab, every centre: r0 a multiple of kScoresTile, r1 too unless it is nr.  One workgroup per block of
+// kScoresTile rows; it loops over the centres itself.
+hipError_t launch_assign(const AssignArgs& a, uint64_t r0, uint64_t r1, hipStream_t s);
+
+// ---- column counts of every label (gsim_labels.hip, gsim_db_label_counts / gsim_db_kmeans) ---------------------------------
+constexpr int kLabelsBlock = 256;
+constexpr uint32_t kLabelsSlice = 4096; // entries of the sorted list one workgroup walks before it takes the next slice
+// keys[i] = min(labels[i], nlabels) (GSIM_LABEL_NONE sorts behind every label), vals[i] = row0 + i
+hipError_t launch_labels_keys(const uint32_t* labels, uint64_t n, uint32_t nlabels, uint32_t row0, uint32_t* keys, uint32_t* vals, hipStream_t s);
+hipError_t labels_sort_bytes(uint64_t n, uint32_t nlabels, size_t* bytes);
+// (keys, vals) -> (keys_sorted, vals_sorted), stable: the rows of a label ascend
+hipError_t launch_labels_sort(void* tmp, size_t tmp_bytes, const uint32_t* keys, uint32_t* keys_sorted, const uint32_t* vals, uint32_t* vals_sorted,
+                              uint64_t n, uint32_t nlabels, hipStream_t s);
+// first[l], l <= nlabels: the first entry of the sorted keys that is >= l (first[nlabels]: the rows counted)
+hipError_t launch_labels_bounds(const uint32_t* keys_sorted, uint64_t n, uint32_t nlabels, uint32_t* first, hipStream_t s);
+struct LabelCountArgs {
+    const uint32_t* rows;        // the whole table, nrows x W words
+    uint32_t W;
+    const uint32_t* keys;        // the sorted labels
+    const uint32_t* list;        // ... and their rows
+    uint32_t* counts;            // nlabels x (W x 32) counters
+    uint32_t nlabels;
+};
+// Adds the rows list[i0 .. i1) into their labels' counters.  Any cut of the list into launches gives the same counters.
+hipError_t launch_labels_count(const LabelCountArgs& a, uint64_t i0, uint64_t i1, int num_cus, hipStream_t s);
+// *changed (zeroed by the caller) += the number of i < n with a[i] != b[i]
+hipError_t launch_labels_changed(const uint32_t* a, const uint32_t* b, uint64_t n, unsigned long long* changed, hipStream_t s);
 
 // ---- MaxMin diversity picking (gsim_maxmin.hip, gsim_db_maxmin) ----------------------------------------------------------
 // ctl words of a call (zeroed by the host before the first pass; the ticket on its own 128-byte line)

@@ -961,6 +961,106 @@ int gsim_isim(const uint64_t* counts, uint32_t fp_bits, uint64_t n, int index, d
 int gsim_isim_complement(const uint64_t* counts, uint32_t fp_bits, uint64_t n, int index,
                          const uint64_t* sums, const uint32_t* popc, uint64_t m, double* out /* m */);
 
+/* ---- centroid clustering: nearest-centre assignment, per-label column counts, k-means --------------------------------------------- */
+/* "Give me K clusters of this library": the two passes of Lloyd's iteration on fingerprints and the loop over them.  The centroid of
+ * a cluster is its majority vote per bit (BitBIRCH's floor(sum / n + 0.5)).  No counterpart in the reference.  The labels that
+ * gsim_db_leader, gsim_db_maxmin (`nearest`) and gsim_butina return are valid inputs of gsim_db_label_counts as they are.
+ *
+ * gsim_db_assign, THE RESULT RULE:
+ *   - S[c, i] is what gsim_db_scores_queries(db, centres, m, row_begin, row_end, ...) returns: the centre is the left side (alpha
+ *     weighs the centre's own bits), the reference's one f32 divide, 0 / 0 is 0.0f;
+ *   - label[i], i < row_end - row_begin, is the centre c with the greatest f32 S[c, i]; among centres whose f32 scores are equal the
+ *     LOWEST index wins.  The rule is stated on the rounded f32 scores, not on the exact fractions: two different c / den that round
+ *     to the same float tie, and the lower index wins whatever a cross-multiplied comparison would say;
+ *   - score[i] (or NULL) is that S[label[i], i], bit for bit;
+ *   - an all-zero row (every score 0.0) gets label 0 and score 0.0;
+ *   - metrics: GSIM_METRIC_TANIMOTO, and GSIM_METRIC_TVERSKY with any finite alpha >= 0, beta >= 0, asymmetric included;
+ *   - ranges concatenate; the row base plays no part (indices as in gsim_db_bit_counts); the output is byte-identical from run to run
+ *     and does not depend on how the call is cut into launches (GSIM_ASSIGN_LAUNCH_PAIRS, read once per handle).
+ * GSIM_ERR_INVALID, checked before any device state: NULL db, m == 0 or m > GSIM_ASSIGN_MAX_CENTRES, NULL centres / label with a
+ * non-empty range, row_begin > row_end or row_end past the count, an unknown metric, Tversky alpha / beta negative or not finite, a
+ * table of 2^32 rows or more, rows wider than 4096 bits.  GSIM_ERR_STATE: a multi-shard handle, a folded table, a table not on a GPU.
+ * GSIM_ERR_NOMEM: the call's device memory cannot be had; nothing leaked.  An empty range: GSIM_OK, outputs untouched.
+ * Execution: as gsim_db_scores -- on the handle's stream under the one-call-at-a-time rule, every temporary freed, the search state
+ * left as it was found.  Device memory of a call: the centres (zero-padded to whole 256-bit groups) and their popcounts, 8 bytes per
+ * row of the range (labels and scores), and per SLAB of at most 2^20 rows 4 bytes a row (popcounts) plus, for rows that are not whole
+ * 256-bit groups, the slab's zero-padded copy: never a padded copy of the table. */
+#define GSIM_ASSIGN_MAX_CENTRES 65536u
+typedef struct {
+    uint64_t rows, centres;          /* row_end - row_begin, m                                               */
+    uint64_t launches;               /* launches of the assign kernel                                        */
+    uint64_t pairs;                  /* m * rows                                                             */
+    double prepare_ms;               /* popcounts and zero-padded copies (centres and slabs)                 */
+    double kernel_ms;                /* HIP events on the handle's stream: all assign launches               */
+    double d2h_ms;                   /* labels and scores to the host                                        */
+    double wall_ms;
+    double clock_mhz;                /* as gsim_scores_stats.clock_mhz                                       */
+} gsim_assign_stats;
+int gsim_db_assign(gsim_db* db, const uint32_t* centres /* host, m x fp_bits/32 words */, uint32_t m,
+                   uint64_t row_begin, uint64_t row_end, int metric, float alpha, float beta,
+                   uint32_t* label /* row_end - row_begin */, float* score /* or NULL, same length */,
+                   gsim_assign_stats* stats /* or NULL */);
+
+/* gsim_db_label_counts, THE RESULT RULE (labels[i] is the label of row row_begin + i; host memory):
+ *   - counts[l * fp_bits + k], l < nlabels, is the number of rows of the range with label l whose bit k is set (bit k: as
+ *     gsim_db_bit_counts); sizes[l] (or NULL) is the number of rows with label l.  A row labelled GSIM_LABEL_NONE is counted nowhere;
+ *   - the counters are uint32 (a table has fewer than 2^32 rows; 10^5 labels x 1024 bits are 400 MB, not 800): gsim_isim and
+ *     gsim_isim_complement take uint64 counts -- widen a label's row before it goes there;
+ *   - row l of counts equals gsim_db_bit_counts over the row set {i : labels[i] == l}; the counts of ranges that partition a range add
+ *     up; an empty range gives GSIM_OK with zeros;
+ *   - the output is integer: byte-identical from run to run, independent of the way a row's bits are added
+ *     and of how the pass is cut into launches (GSIM_LABELS_LAUNCH_ROWS, read once per handle, 0 = automatic).
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / counts, nlabels == 0, NULL labels with a non-empty range, a label
+ * >= nlabels other than GSIM_LABEL_NONE, row_begin > row_end or row_end past the count, a table of 2^32 rows or more, rows wider than
+ * 4096 bits.  GSIM_ERR_STATE and GSIM_ERR_NOMEM: as gsim_db_bit_counts.  Execution: as gsim_db_bit_counts.  Device memory of the
+ * call: nlabels x fp_bits 32-bit counters, nlabels + 1 segment starts, 20 bytes per row of the range (labels, sort keys and row
+ * numbers before and behind the sort) and the sort's scratch, freed by the call. */
+#define GSIM_LABEL_NONE 0xFFFFFFFFu /* == GSIM_LEADER_NONE: the row is counted nowhere */
+typedef struct {
+    uint64_t rows_read;    /* rows of the range                                                                         */
+    uint64_t rows_counted; /* ... whose label is not GSIM_LABEL_NONE                                                    */
+    uint64_t labels;       /* nlabels                                                                                   */
+    uint64_t launches;     /* launches of the counting kernel                                                           */
+    double sort_ms;        /* HIP events: labels to the device, keys, the sort, the segment starts                      */
+    double kernel_ms;      /* ... the counting launches                                                                 */
+    double d2h_ms;         /* counts to the host                                                                        */
+    double wall_ms;        /* the whole call, host clock                                                                */
+} gsim_label_stats;
+int gsim_db_label_counts(gsim_db* db, const uint32_t* labels /* host, row_end - row_begin */, uint32_t nlabels,
+                         uint64_t row_begin, uint64_t row_end,
+                         uint32_t* counts /* nlabels x fp_bits */, uint32_t* sizes /* nlabels, or NULL */,
+                         gsim_label_stats* stats /* or NULL */);
+
+/* The majority-vote centroids of labelled rows from gsim_db_label_counts' output (host code, no device, no handle): bit k of centre l
+ * is set iff 2 * counts[l * fp_bits + k] >= sizes[l] (a tie sets the bit).  A label with sizes[l] == 0 keeps previous[l * words ..],
+ * or is all zeros when previous is NULL; words = fp_bits / 32.  GSIM_ERR_INVALID: NULL counts / sizes / centres, nlabels == 0,
+ * fp_bits 0 or not a multiple of 32, a count above its label's size. */
+int gsim_label_centroids(const uint32_t* counts, const uint32_t* sizes, uint32_t nlabels, uint32_t fp_bits,
+                         const uint32_t* previous /* nlabels x words, or NULL */, uint32_t* centres /* nlabels x words */);
+
+/* gsim_db_kmeans, THE RESULT RULE (Lloyd's iteration over the whole table of N rows, m centres):
+ *   - C_0 = init.  Iteration t = 0, 1, ...: labels_t = gsim_db_assign(C_t) over [0, N).  Stop if t > 0 and labels_t == labels_(t-1)
+ *     (converged), or once t + 1 == max_iter.  Otherwise C_(t+1) = gsim_label_centroids(gsim_db_label_counts(labels_t), previous =
+ *     C_t): an empty cluster keeps its centre;
+ *   - centres (m x words) are the C_t that the returned label[N] / score[N] (or NULL) were assigned to, so gsim_db_assign(centres)
+ *     reproduces them exactly; sizes[m] (or NULL) are the sizes of the returned labels.
+ * GSIM_ERR_INVALID: max_iter == 0, NULL init / centres, NULL label with N > 0, and what gsim_db_assign refuses; GSIM_ERR_STATE: as
+ * the two calls, and a table without rows; GSIM_ERR_NOMEM: as the two calls.  Execution: as gsim_db_assign; the labels stay on the device between iterations, per iteration
+ * only the counts and sizes come down and the centres go up. */
+typedef struct {
+    uint64_t iterations;   /* assignments made: t + 1 at the stop                                                       */
+    uint64_t converged;    /* 1: the last two assignments were equal                                                    */
+    uint64_t changed_last; /* rows whose label differed between the last two assignments (N after a single one)        */
+    double assign_ms;      /* kernel time of the assignments (prepare + kernel of gsim_assign_stats)                    */
+    double counts_ms;      /* ... of the label counts (sort + kernel + d2h of gsim_label_stats)                         */
+    double update_ms;      /* host clock: the majority votes and the centres' way up                                    */
+    double wall_ms;
+} gsim_kmeans_stats;
+int gsim_db_kmeans(gsim_db* db, const uint32_t* init /* m x words */, uint32_t m, uint32_t max_iter,
+                   int metric, float alpha, float beta,
+                   uint32_t* centres /* m x words */, uint32_t* label /* N */, float* score /* or NULL */,
+                   uint32_t* sizes /* m, or NULL */, gsim_kmeans_stats* stats /* or NULL */);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
