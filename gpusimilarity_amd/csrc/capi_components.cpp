@@ -25,12 +25,12 @@ int components(gsim_db* db, Shard& s, const float* cutoffs, uint32_t nlevels, in
         N < 2 ? std::vector<NbrLaunch>() : plan_launches(nt, nt, true, WP, static_cast<uint64_t>(db->knobs.components_launch_pairs));
     size_t tmp_bytes = 0;
     GSIM_HIP(gsim::comp_scan_bytes(N, &tmp_bytes));
-    DevBuf<uint32_t> pop, pad, parent, d_comp, d_first, d_sizes, d_ncomp, d_flag, d_num;
+    PaddedRows table;
+    DevBuf<uint32_t> parent, d_comp, d_first, d_sizes, d_ncomp, d_flag, d_num;
     DevBuf<unsigned long long> ctl; // the counters, then 4 clock stamps per launch
     DevBuf<> tmp;
     const size_t stripe = static_cast<size_t>(N) * 4, all = stripe * nlevels;
-    GSIM_ALLOC(pop, stripe, "components (popcounts)");
-    if (WP != s.W) GSIM_ALLOC(pad, static_cast<size_t>(N) * WP * 4, "components (the padded rows)");
+    if (const int rc = table.alloc(N, s.W, WP, "components (popcounts)", "components (the padded rows)")) return rc;
     GSIM_ALLOC(parent, all, "components (the forests)");
     GSIM_ALLOC(d_comp, all, "components (component_of)");
     if (first_row) GSIM_ALLOC(d_first, all, "components (first_row)");
@@ -40,11 +40,10 @@ int components(gsim_db* db, Shard& s, const float* cutoffs, uint32_t nlevels, in
     GSIM_ALLOC(d_num, stripe, "components (label scratch)");
     GSIM_ALLOC(ctl, (gsim::kCompCounters + 4 * plan.size()) * 8, "components (control block)");
     GSIM_ALLOC(tmp, tmp_bytes, "components (scan scratch)");
-    unsigned long long* d_clk = ctl + gsim::kCompCounters;
+    LaunchClocks clocks;
+    clocks.view(ctl + gsim::kCompCounters);
 
     gsim::CompArgs a{};
-    a.rows = WP != s.W ? static_cast<const uint32_t*>(pad) : static_cast<const uint32_t*>(s.d_rows);
-    a.pop = pop;
     a.nrows = N;
     a.WP = WP;
     a.nlevels = nlevels;
@@ -60,14 +59,16 @@ int components(gsim_db* db, Shard& s, const float* cutoffs, uint32_t nlevels, in
     GSIM_HIP(ev_label.create());
     GSIM_HIP(ev_d2h.create());
     GSIM_HIP(hipMemsetAsync(ctl, 0, (gsim::kCompCounters + 4 * plan.size()) * 8, stream));
-    GSIM_HIP(gsim::launch_nbr_prepare(s.d_rows, N, s.W, WP, pad, pop, stream));
+    if (const int rc = table.prepare(s.d_rows, N, stream)) return rc;
+    a.rows = table.rows();
+    a.pop = table.pop();
     GSIM_HIP(gsim::launch_comp_init(parent, N, nlevels, stream));
     // the pass: every launch is followed by the flatten (all path shortening is there; after the last launch it leaves
     // parent[x] = the smallest row of x's component)
     GSIM_HIP(hipEventRecord(ev_kernel.a, stream));
     for (size_t l = 0; l < plan.size(); l++) {
         gsim::CompArgs al = a;
-        al.clk = d_clk + 4 * l;
+        al.clk = clocks.at(l);
         GSIM_HIP(gsim::launch_comp_tiles(al, plan[l].rt0, plan[l].nrt, plan[l].ct0, plan[l].nct, stream));
         GSIM_HIP(gsim::launch_comp_flatten(parent, N, nlevels, stream));
     }
@@ -109,13 +110,8 @@ int components(gsim_db* db, Shard& s, const float* cutoffs, uint32_t nlevels, in
         st->kernel_ms = ev_kernel.ms();
         st->label_ms = ev_label.ms();
         st->d2h_ms = ev_d2h.ms();
-        double cyc = 0.0, ticks = 0.0;
-        for (size_t l = 0; l < plan.size(); l++) {
-            const unsigned long long* c = h_ctl.data() + gsim::kCompCounters + 4 * l;
-            cyc += static_cast<double>(c[2] - c[0]);
-            ticks += static_cast<double>(c[3] - c[1]);
-        }
-        st->clock_mhz = ticks > 0.0 ? cyc / ticks * 100.0 : 0.0; // wall clock: 100 MHz
+        clocks.add(h_ctl.data() + gsim::kCompCounters, plan.size()); // (read with the counters, in one copy)
+        st->clock_mhz = clocks.mhz();
         st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     return GSIM_OK;

@@ -102,7 +102,9 @@ int histogram(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, bool l
             coarse[t] = static_cast<uint8_t>(n);
         }
         DevBuf<unsigned long long> d_hist, d_total;
-        DevBuf<> d_bins, pop, pad, lpop, lpad, ctl;
+        DevBuf<> d_bins;
+        PaddedRows table, left;
+        LaunchClocks clocks;
         GSIM_ALLOC(d_hist, nl * nb * 8, "the histogram's counters");
         GSIM_ALLOC(d_total, static_cast<size_t>(nb) * 8, "the histogram's totals");
         GSIM_ALLOC(d_bins, GSIM_HIST_MAX_EDGES * 4 + gsim::kHistCoarse, "the histogram's edges");
@@ -120,7 +122,6 @@ int histogram(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, bool l
         GSIM_HIP(ev_reduce.create());
         GSIM_HIP(ev_d2h.create());
         const bool stream = db->knobs.hist_stream_max_rows > 0 && nl <= static_cast<uint64_t>(db->knobs.hist_stream_max_rows);
-        std::vector<unsigned long long> clk;
         if (N == 0) {
             GSIM_HIP(hipEventRecord(ev_run.a, st));
             GSIM_HIP(hipEventRecord(ev_run.b, st));
@@ -146,26 +147,25 @@ int histogram(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, bool l
         } else {
             // popc of every table row, and the rows of either side zero-padded to WP words unless they already are WP words
             const uint32_t WP = gsim::nbr_padded_words(s.W);
-            GSIM_ALLOC(pop, N * 4, "the histogram (popcounts)");
-            if (WP != s.W) GSIM_ALLOC(pad, N * WP * 4, "the histogram (padded rows)");
-            GSIM_HIP(gsim::launch_nbr_prepare(s.d_rows, N, s.W, WP, pad.as<uint32_t>(), pop.as<uint32_t>(), st));
+            if (const int rc = table.alloc(N, s.W, WP, "the histogram (popcounts)", "the histogram (padded rows)")) return rc;
+            if (const int rc = table.prepare(s.d_rows, N, st)) return rc;
+            // (the kernel counts the left rows' bits itself: only their padded copy is wanted, where the table's does not hold them)
             const uint32_t* lrows = d_left;
             if (WP != s.W) {
                 if (left_in_table) {
-                    lrows = pad.as<uint32_t>() + left_row0 * WP;
+                    lrows = table.rows() + left_row0 * WP;
                 } else {
-                    GSIM_ALLOC(lpop, nl * 4, "the histogram (popcounts of the left rows)");
-                    GSIM_ALLOC(lpad, nl * WP * 4, "the histogram (padded left rows)");
-                    GSIM_HIP(gsim::launch_nbr_prepare(d_left, nl, s.W, WP, lpad.as<uint32_t>(), lpop.as<uint32_t>(), st));
-                    lrows = lpad.as<uint32_t>();
+                    if (const int rc = left.alloc(nl, s.W, WP, "the histogram (popcounts of the left rows)", "the histogram (padded left rows)")) return rc;
+                    if (const int rc = left.prepare(d_left, nl, st)) return rc;
+                    lrows = left.rows();
                 }
             }
             const std::vector<HistLaunch> plan = plan_tiles(nl, N, WP, db->knobs.hist_launch_pairs, s.num_cus);
-            GSIM_ALLOC(ctl, 4 * plan.size() * 8, "the histogram (clock stamps)");
-            GSIM_HIP(hipMemsetAsync(ctl, 0, 4 * plan.size() * 8, st));
+            if (const int rc = clocks.own(plan.size(), "the histogram (clock stamps)")) return rc;
+            GSIM_HIP(clocks.zero(plan.size(), st));
             gsim::HistTileArgs a{};
-            a.rows = WP != s.W ? pad.as<uint32_t>() : static_cast<const uint32_t*>(s.d_rows);
-            a.pop = pop.as<uint32_t>();
+            a.rows = table.rows();
+            a.pop = table.pop();
             a.lrows = lrows;
             a.nrows = N;
             a.nl = nl;
@@ -178,12 +178,11 @@ int histogram(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, bool l
             a.hist = d_hist;
             GSIM_HIP(hipEventRecord(ev_run.a, st));
             for (size_t l = 0; l < plan.size(); l++) {
-                a.clk = ctl.as<unsigned long long>() + 4 * l;
+                a.clk = clocks.at(l);
                 GSIM_HIP(gsim::launch_hist_tiles(a, plan[l].ot0, plan[l].not_, plan[l].c0, plan[l].c1, plan[l].chunk, st));
             }
             GSIM_HIP(hipEventRecord(ev_run.b, st));
-            clk.resize(4 * plan.size());
-            GSIM_HIP(hipMemcpyAsync(clk.data(), ctl, clk.size() * 8, hipMemcpyDeviceToHost, st));
+            GSIM_HIP(clocks.fetch(plan.size(), st));
             hs.rows_tiled = nl;
             hs.tile_launches = plan.size();
         }
@@ -196,12 +195,8 @@ int histogram(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, bool l
         GSIM_HIP(hipMemcpyAsync(h_total.data(), d_total, static_cast<size_t>(nb) * 8, hipMemcpyDeviceToHost, st));
         GSIM_HIP(hipEventRecord(ev_d2h.b, st));
         GSIM_HIP(hipStreamSynchronize(st));
-        double cyc = 0.0, ticks = 0.0;
-        for (size_t l = 0; 4 * l < clk.size(); l++) {
-            cyc += static_cast<double>(clk[4 * l + 2] - clk[4 * l]);
-            ticks += static_cast<double>(clk[4 * l + 3] - clk[4 * l + 1]);
-        }
-        hs.clock_mhz = ticks > 0.0 ? cyc / ticks * 100.0 : 0.0; // wall clock: 100 MHz
+        clocks.add(); // (nothing on the streaming route)
+        hs.clock_mhz = clocks.mhz();
         (stream ? hs.stream_ms : hs.tile_ms) = ev_run.ms();
         hs.reduce_ms = ev_reduce.ms();
         hs.d2h_ms = ev_d2h.ms();

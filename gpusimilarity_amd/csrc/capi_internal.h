@@ -283,6 +283,84 @@ inline uint32_t popcount_words(const uint32_t* q, uint32_t W)
     return a;
 }
 
+// ---- the host side of a tile call: what the callers of the tile and fold kernels (neighbours, joins, k-NN, histograms,
+// components, the spanning forest) and of the matrix kernels (scores, assign) do before and after their launches ----
+
+// One side's rows as those kernels read them: popc of every row and, where the rows are not WP words already, their zero-padded
+// copy (nbr_prepare_kernel).
+class PaddedRows
+{
+    DevBuf<uint32_t> pop_, pad_;
+    uint32_t W_ = 0, WP_ = 0;
+    const uint32_t* rows_ = nullptr;
+
+public:
+    // Room for n rows of W words.  A shortage is GSIM_ERR_NOMEM, "device memory for <what>", as GSIM_ALLOC; without labels it is
+    // reported the way GSIM_HIP reports a failed call.
+    int alloc(uint64_t n, uint32_t W, uint32_t WP, const char* what_pop = nullptr, const char* what_pad = nullptr)
+    {
+        W_ = W;
+        WP_ = WP;
+        if (!what_pop) {
+            GSIM_HIP(pop_.grow(n * 4));
+            if (WP != W) GSIM_HIP(pad_.grow(n * WP * 4));
+            return GSIM_OK;
+        }
+        if (pop_.grow(n * 4) != hipSuccess) return fail(GSIM_ERR_NOMEM, std::string("device memory for ") + what_pop);
+        if (WP != W && pad_.grow(n * WP * 4) != hipSuccess) return fail(GSIM_ERR_NOMEM, std::string("device memory for ") + what_pad);
+        return GSIM_OK;
+    }
+    // Enqueues the preparation of d_rows[0 .. n), n at most alloc's; rows() and pop() are those rows' from here on.
+    int prepare(const void* d_rows, uint64_t n, hipStream_t st)
+    {
+        GSIM_HIP(gsim::launch_nbr_prepare(d_rows, n, W_, WP_, pad_, pop_, st));
+        rows_ = WP_ != W_ ? static_cast<const uint32_t*>(pad_) : static_cast<const uint32_t*>(d_rows);
+        return GSIM_OK;
+    }
+    const uint32_t* rows() const { return rows_; } // WP words each
+    const uint32_t* pop() const { return pop_; }
+};
+
+// The clock a call's launches ran at: the kernels' stamps (stamp_begin / stamp_end of gsim_device_common.h, four device words per launch: shader cycles
+// and the 100 MHz wall clock at either end) and their sum over the launches, the rounds of a call included.
+class LaunchClocks
+{
+    DevBuf<unsigned long long> own_;
+    unsigned long long* d_ = nullptr;
+    std::vector<unsigned long long> h_;
+    double cyc_ = 0.0, ticks_ = 0.0;
+
+public:
+    static constexpr size_t kWords = 4; // per launch
+    // the device words: inside the caller's control block, which the caller zeroes and may read back itself ...
+    void view(unsigned long long* d_words) { d_ = d_words; }
+    // ... or a buffer of their own for n launches
+    int own(size_t n, const char* what)
+    {
+        if (own_.grow(kWords * n * 8) != hipSuccess) return fail(GSIM_ERR_NOMEM, std::string("device memory for ") + what);
+        d_ = own_;
+        return GSIM_OK;
+    }
+    unsigned long long* at(size_t l) const { return d_ + kWords * l; } // launch l's (the kernel argument `clk`)
+    hipError_t zero(size_t n, hipStream_t st) { return hipMemsetAsync(d_, 0, kWords * n * 8, st); }
+    // enqueues the copy of n launches' words to the host; add() them once the stream has been waited for
+    hipError_t fetch(size_t n, hipStream_t st)
+    {
+        h_.assign(kWords * n, 0);
+        return n ? hipMemcpyAsync(h_.data(), d_, h_.size() * 8, hipMemcpyDeviceToHost, st) : hipSuccess;
+    }
+    void add() { add(h_.data(), h_.size() / kWords); }
+    // n launches' words the caller read back with its control block
+    void add(const unsigned long long* h, size_t n)
+    {
+        for (size_t l = 0; l < n; l++) {
+            cyc_ += static_cast<double>(h[kWords * l + 2] - h[kWords * l]);
+            ticks_ += static_cast<double>(h[kWords * l + 3] - h[kWords * l + 1]);
+        }
+    }
+    double mhz() const { return ticks_ > 0.0 ? cyc_ / ticks_ * 100.0 : 0.0; } // wall clock: 100 MHz
+};
+
 enum QueryMode { kAuto = 0, kClassic = 1 };
 // Per-query record of the synchronous routes (Shard::PipeSlot::why -> gsim_db::query_flags -> gsim_debug_query_flags)
 constexpr uint8_t kQHandedBack = 1;   // the single launch ran the query and handed it back itself (gsim_timing.handed_back counts these)

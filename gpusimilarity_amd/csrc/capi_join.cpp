@@ -88,26 +88,23 @@ int join(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, float cutof
     } else {
         // popc of every row of either side, and the rows zero-padded to WP words unless they already are WP words
         const uint32_t WP = gsim::nbr_padded_words(s.W);
-        DevBuf<> pop, pad, lpop, lpad;
-        GSIM_HIP(pop.grow(N * 4));
-        GSIM_HIP(lpop.grow(nl * 4));
-        if (WP != s.W) {
-            GSIM_HIP(pad.grow(N * WP * 4));
-            GSIM_HIP(lpad.grow(nl * WP * 4));
-        }
-        GSIM_HIP(gsim::launch_nbr_prepare(s.d_rows, N, s.W, WP, pad.as<uint32_t>(), pop.as<uint32_t>(), st));
-        GSIM_HIP(gsim::launch_nbr_prepare(d_left, nl, s.W, WP, lpad.as<uint32_t>(), lpop.as<uint32_t>(), st));
+        PaddedRows table, left;
+        if (const int rc = table.alloc(N, s.W, WP)) return rc;
+        if (const int rc = left.alloc(nl, s.W, WP)) return rc;
+        if (const int rc = table.prepare(s.d_rows, N, st)) return rc;
+        if (const int rc = left.prepare(d_left, nl, st)) return rc;
         const uint64_t nlt = (nl + gsim::kNbrTile - 1) / gsim::kNbrTile;
         const uint64_t nct = (N + gsim::kNbrTile - 1) / gsim::kNbrTile;
         const std::vector<NbrLaunch> plan = plan_launches(nlt, nct, false, WP);
         DevBuf<> ctl; // [0] the cursor, [1 + l] the cursor after launch l, then 4 clock stamps per launch
         GSIM_HIP(ctl.grow((1 + 5 * plan.size()) * 8));
-        unsigned long long* d_clk = ctl.as<unsigned long long>() + 1 + plan.size();
+        LaunchClocks clocks;
+        clocks.view(ctl.as<unsigned long long>() + 1 + plan.size());
         gsim::JoinTileArgs a{};
-        a.rows = WP != s.W ? pad.as<uint32_t>() : static_cast<const uint32_t*>(s.d_rows);
-        a.pop = pop.as<uint32_t>();
-        a.lrows = WP != s.W ? lpad.as<uint32_t>() : d_left;
-        a.lpop = lpop.as<uint32_t>();
+        a.rows = table.rows();
+        a.pop = table.pop();
+        a.lrows = left.rows();
+        a.lpop = left.pop();
         a.nrows = N;
         a.row_begin = 0;
         a.row_end = nl;
@@ -123,21 +120,16 @@ int join(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, float cutof
                                              al.vals = sink.vals;
                                              al.cursor = sink.cursor;
                                              al.cap = sink.cap;
-                                             al.clk = d_clk + 4 * l;
+                                             al.clk = clocks.at(l);
                                              GSIM_HIP(gsim::launch_join_tiles(al, plan[l].rt0, plan[l].nrt, plan[l].ct0, plan[l].nct, st));
                                              return static_cast<int>(GSIM_OK);
                                          },
                                          &run);
         if (rc != GSIM_OK) return rc;
-        std::vector<unsigned long long> clk(4 * plan.size());
-        GSIM_HIP(hipMemcpyAsync(clk.data(), d_clk, clk.size() * 8, hipMemcpyDeviceToHost, st));
+        GSIM_HIP(clocks.fetch(plan.size(), st));
         GSIM_HIP(hipStreamSynchronize(st));
-        double cyc = 0.0, ticks = 0.0;
-        for (size_t l = 0; l < plan.size(); l++) {
-            cyc += static_cast<double>(clk[4 * l + 2] - clk[4 * l]);
-            ticks += static_cast<double>(clk[4 * l + 3] - clk[4 * l + 1]);
-        }
-        g->join.clock_mhz = g->stats.clock_mhz = ticks > 0.0 ? cyc / ticks * 100.0 : 0.0; // wall clock: 100 MHz
+        clocks.add();
+        g->join.clock_mhz = g->stats.clock_mhz = clocks.mhz();
         g->join.rows_tiled = nl;
         g->join.tile_launches = plan.size();
         g->join.tile_ms = run.ms;

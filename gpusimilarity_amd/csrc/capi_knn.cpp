@@ -61,29 +61,30 @@ int knn(gsim_db* db, Shard& s, uint32_t k, float cutoff, int metric, float alpha
 
     // popc of every row, and the rows zero-padded to WP words unless they already are WP words; the lists and their lengths
     // (one more length, zero: the scan's last output is the total); [0] the insert counter, then 4 clock stamps per launch
-    DevBuf<> pop, pad, ctl, tmp;
+    PaddedRows table;
+    DevBuf<> ctl, tmp;
     DevBuf<gsim::KnnEntry> lists;
     DevBuf<uint32_t> len, d_indices;
     DevBuf<float> d_scores;
     DevBuf<uint64_t> d_indptr;
     size_t tmp_bytes = 0;
     GSIM_HIP(gsim::knn_scan_bytes(nout + 1, &tmp_bytes));
-    GSIM_ALLOC(pop, N * 4, "the k-nearest-neighbour lists (popcounts)");
-    if (WP != s.W) GSIM_ALLOC(pad, N * WP * 4, "the k-nearest-neighbour lists (padded rows)");
+    if (const int rc = table.alloc(N, s.W, WP, "the k-nearest-neighbour lists (popcounts)", "the k-nearest-neighbour lists (padded rows)")) return rc;
     GSIM_ALLOC(lists, nout * k * sizeof(gsim::KnnEntry), "the k-nearest-neighbour lists");
     GSIM_ALLOC(len, (nout + 1) * 4, "the k-nearest-neighbour lists (lengths)");
     GSIM_ALLOC(d_indptr, (nout + 1) * 8, "the k-nearest-neighbour lists (row offsets)");
     GSIM_ALLOC(ctl, (1 + 4 * plan.size()) * 8, "the k-nearest-neighbour lists (control block)");
     GSIM_ALLOC(tmp, tmp_bytes, "the k-nearest-neighbour lists (scan scratch)");
     unsigned long long* d_inserts = ctl.as<unsigned long long>();
-    unsigned long long* d_clk = d_inserts + 1;
+    LaunchClocks clocks;
+    clocks.view(d_inserts + 1);
     GSIM_HIP(hipMemsetAsync(len, 0, (nout + 1) * 4, st));
     GSIM_HIP(hipMemsetAsync(ctl, 0, (1 + 4 * plan.size()) * 8, st));
-    GSIM_HIP(gsim::launch_nbr_prepare(s.d_rows, N, s.W, WP, pad.as<uint32_t>(), pop.as<uint32_t>(), st));
+    if (const int rc = table.prepare(s.d_rows, N, st)) return rc;
 
     gsim::KnnArgs a{};
-    a.rows = WP != s.W ? pad.as<uint32_t>() : static_cast<const uint32_t*>(s.d_rows);
-    a.pop = pop.as<uint32_t>();
+    a.rows = table.rows();
+    a.pop = table.pop();
     a.nrows = N;
     a.row_begin = rb;
     a.row_end = re;
@@ -103,7 +104,7 @@ int knn(gsim_db* db, Shard& s, uint32_t k, float cutoff, int metric, float alpha
     GSIM_HIP(ev_d2h.create());
     GSIM_HIP(hipEventRecord(ev_fold.a, st));
     for (size_t l = 0; l < plan.size(); l++) {
-        a.clk = d_clk + 4 * l;
+        a.clk = clocks.at(l);
         GSIM_HIP(gsim::launch_knn_fold(a, plan[l].ot0, plan[l].not_, plan[l].c0, plan[l].c1, st));
     }
     GSIM_HIP(hipEventRecord(ev_fold.b, st));
@@ -131,12 +132,7 @@ int knn(gsim_db* db, Shard& s, uint32_t k, float cutoff, int metric, float alpha
     GSIM_HIP(hipEventRecord(ev_d2h.b, st));
     GSIM_HIP(hipStreamSynchronize(st));
 
-    double cyc = 0.0, ticks = 0.0;
-    for (size_t l = 0; l < plan.size(); l++) {
-        const unsigned long long* clk = h_ctl.data() + 1 + 4 * l;
-        cyc += static_cast<double>(clk[2] - clk[0]);
-        ticks += static_cast<double>(clk[3] - clk[1]);
-    }
+    clocks.add(h_ctl.data() + 1, plan.size()); // (read with the insert counter, in one copy)
     gsim_knn_stats& ks = g->knn;
     ks.launches = plan.size();
     ks.pairs = nout * N;
@@ -146,7 +142,7 @@ int knn(gsim_db* db, Shard& s, uint32_t k, float cutoff, int metric, float alpha
     // (the events of the CSR build span the host's look at the total: offsets, one small read, compaction)
     ks.csr_ms = ev_csr.ms();
     ks.d2h_ms = ev_d2h.ms();
-    ks.clock_mhz = ticks > 0.0 ? cyc / ticks * 100.0 : 0.0; // wall clock: 100 MHz
+    ks.clock_mhz = clocks.mhz();
     ks.wall_ms = wall();
     g->stats.launches = ks.launches;
     g->stats.pairs = total;

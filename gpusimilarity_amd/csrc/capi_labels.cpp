@@ -50,25 +50,19 @@ int assign_device(gsim_db* db, Shard& s, const uint32_t* d_centres, uint32_t m, 
     const hipStream_t st = s.stream;
     const uint32_t W = s.W, WP = gsim::scores_padded_words(W);
     const uint64_t slab = std::min(kAssignSlabRows, c.nr), per = assign_launch_rows(db, m, WP);
-    DevBuf<> cpop, cpad, rpop, rpad, ctl;
-    GSIM_ALLOC(cpop, static_cast<size_t>(m) * 4, "the assignment (popcounts of the centres)");
-    GSIM_ALLOC(rpop, slab * 4, "the assignment (popcounts of a slab of rows)");
-    if (WP != W) {
-        GSIM_ALLOC(cpad, static_cast<size_t>(m) * WP * 4, "the assignment (padded centres)");
-        GSIM_ALLOC(rpad, slab * WP * 4, "the assignment (a slab of padded rows)");
-    }
+    PaddedRows centres, rows_of_slab;
+    LaunchClocks clocks;
+    if (const int rc = centres.alloc(m, W, WP, "the assignment (popcounts of the centres)", "the assignment (padded centres)")) return rc;
+    if (const int rc = rows_of_slab.alloc(slab, W, WP, "the assignment (popcounts of a slab of rows)", "the assignment (a slab of padded rows)")) return rc;
     size_t nlaunch = 0;
     for (uint64_t f = 0; f < c.nr; f += slab) nlaunch += (std::min(slab, c.nr - f) + per - 1) / per;
-    GSIM_ALLOC(ctl, 4 * nlaunch * 8, "the assignment (clock stamps)");
-    GSIM_HIP(hipMemsetAsync(ctl, 0, 4 * nlaunch * 8, st));
+    if (const int rc = clocks.own(nlaunch, "the assignment (clock stamps)")) return rc;
+    GSIM_HIP(clocks.zero(nlaunch, st));
     EventPair ev_prep, ev_run;
     GSIM_HIP(ev_prep.create());
     GSIM_HIP(ev_run.create());
 
     gsim::AssignArgs a{};
-    a.centres = WP != W ? cpad.as<uint32_t>() : d_centres;
-    a.cpop = cpop.as<uint32_t>();
-    a.rpop = rpop.as<uint32_t>();
     a.m = m;
     a.WP = WP;
     a.metric = c.metric;
@@ -79,16 +73,21 @@ int assign_device(gsim_db* db, Shard& s, const uint32_t* d_centres, uint32_t m, 
         const uint64_t rows = std::min(slab, c.nr - f);
         const uint32_t* d_rows = static_cast<const uint32_t*>(s.d_rows) + (c.r0 + f) * W;
         GSIM_HIP(hipEventRecord(ev_prep.a, st));
-        if (f == 0) GSIM_HIP(gsim::launch_nbr_prepare(d_centres, m, W, WP, cpad.as<uint32_t>(), cpop.as<uint32_t>(), st));
-        GSIM_HIP(gsim::launch_nbr_prepare(d_rows, rows, W, WP, rpad.as<uint32_t>(), rpop.as<uint32_t>(), st));
+        if (f == 0) { // the centres: once, with the first slab
+            if (const int rc = centres.prepare(d_centres, m, st)) return rc;
+            a.centres = centres.rows();
+            a.cpop = centres.pop();
+        }
+        if (const int rc = rows_of_slab.prepare(d_rows, rows, st)) return rc;
         GSIM_HIP(hipEventRecord(ev_prep.b, st));
-        a.rows = WP != W ? rpad.as<uint32_t>() : d_rows;
+        a.rows = rows_of_slab.rows();
+        a.rpop = rows_of_slab.pop();
         a.nr = rows;
         a.label = d_label + f;
         a.score = d_score + f;
         GSIM_HIP(hipEventRecord(ev_run.a, st));
         for (uint64_t r = 0; r < rows; r += per) {
-            a.clk = ctl.as<unsigned long long>() + 4 * launched++;
+            a.clk = clocks.at(launched++);
             GSIM_HIP(gsim::launch_assign(a, r, std::min(r + per, rows), st));
         }
         GSIM_HIP(hipEventRecord(ev_run.b, st));
@@ -98,15 +97,10 @@ int assign_device(gsim_db* db, Shard& s, const uint32_t* d_centres, uint32_t m, 
         ss.kernel_ms += ev_run.ms();
     }
     ss.launches += nlaunch;
-    std::vector<unsigned long long> clk(4 * nlaunch);
-    GSIM_HIP(hipMemcpyAsync(clk.data(), ctl, clk.size() * 8, hipMemcpyDeviceToHost, st));
+    GSIM_HIP(clocks.fetch(nlaunch, st));
     GSIM_HIP(hipStreamSynchronize(st));
-    double cyc = 0.0, ticks = 0.0;
-    for (size_t l = 0; l < nlaunch; l++) {
-        cyc += static_cast<double>(clk[4 * l + 2] - clk[4 * l]);
-        ticks += static_cast<double>(clk[4 * l + 3] - clk[4 * l + 1]);
-    }
-    ss.clock_mhz = ticks > 0.0 ? cyc / ticks * 100.0 : 0.0; // wall clock: 100 MHz
+    clocks.add();
+    ss.clock_mhz = clocks.mhz();
     return GSIM_OK;
 }
 

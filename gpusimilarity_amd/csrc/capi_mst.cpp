@@ -46,12 +46,13 @@ int mst(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, float beta
     size_t select_bytes = 0, sort_bytes = 0;
     GSIM_HIP(gsim::mst_select_bytes(N, &select_bytes));
     GSIM_HIP(gsim::mst_sort_bytes(N - 1, &sort_bytes));
-    DevBuf<uint32_t> pop, pad, comp, parent, own, flag, cscore, eb;
-    DevBuf<unsigned long long> best, ckey, ekey, ctl, clk;
+    PaddedRows table;
+    LaunchClocks clocks;
+    DevBuf<uint32_t> comp, parent, own, flag, cscore, eb;
+    DevBuf<unsigned long long> best, ckey, ekey, ctl;
     DevBuf<gsim_mst_edge> d_edges;
     DevBuf<> tmp;
-    GSIM_ALLOC(pop, N * 4, "the spanning forest (popcounts)");
-    if (WP != s.W) GSIM_ALLOC(pad, N * WP * 4, "the spanning forest (the padded rows)");
+    if (const int rc = table.alloc(N, s.W, WP, "the spanning forest (popcounts)", "the spanning forest (the padded rows)")) return rc;
     GSIM_ALLOC(comp, N * 4, "the spanning forest (component ids)");
     GSIM_ALLOC(parent, N * 4, "the spanning forest (component links)");
     GSIM_ALLOC(own, N * 4, "the spanning forest (the owner list)");
@@ -63,7 +64,7 @@ int mst(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, float beta
     GSIM_ALLOC(eb, (N - 1) * 4, "the spanning forest (edges)");
     GSIM_ALLOC(d_edges, (N - 1) * sizeof(gsim_mst_edge), "the spanning forest (edges)");
     GSIM_ALLOC(ctl, gsim::kMstCtlWords * 8, "the spanning forest (control block)");
-    GSIM_ALLOC(clk, 4 * max_launches * 8, "the spanning forest (clock stamps)");
+    if (const int rc = clocks.own(max_launches, "the spanning forest (clock stamps)")) return rc;
     GSIM_ALLOC(tmp, std::max(select_bytes, sort_bytes), "the spanning forest (select and sort scratch)");
 
     gsim::MstState m{};
@@ -80,8 +81,6 @@ int mst(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, float beta
     m.cap = N - 1;
     m.ctl = ctl;
     gsim::MstArgs a{};
-    a.rows = WP != s.W ? static_cast<const uint32_t*>(pad) : static_cast<const uint32_t*>(s.d_rows);
-    a.pop = pop;
     a.comp = comp;
     a.own = own;
     a.nrows = N;
@@ -97,24 +96,24 @@ int mst(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, float beta
     GSIM_HIP(ev_round.create());
     GSIM_HIP(ev_sort.create());
     GSIM_HIP(ev_d2h.create());
-    GSIM_HIP(gsim::launch_nbr_prepare(s.d_rows, N, s.W, WP, pad, pop, stream));
+    if (const int rc = table.prepare(s.d_rows, N, stream)) return rc;
+    a.rows = table.rows();
+    a.pop = table.pop();
     GSIM_HIP(gsim::launch_mst_init(m, stream));
 
     gsim_mst_stats ms{};
     ms.rows = N;
     uint64_t total = 0, nown = N;
-    double cyc = 0.0, ticks = 0.0;
-    std::vector<unsigned long long> h_clk;
     for (;;) {
         if (ms.scans >= max_scans) return fail(GSIM_ERR_STATE, "mst: more rounds than a forest of this many rows can take");
         // this round's owners against every row: the fold launches, then the bookkeeping and the next round's owner list
         const std::vector<KnnLaunch> plan = nown ? plan_knn(nown, N, WP, knob) : std::vector<KnnLaunch>();
         if (plan.size() > max_launches) return fail(GSIM_ERR_STATE, "mst: a launch plan larger than the first round's");
         a.nown = static_cast<uint32_t>(nown);
-        if (!plan.empty()) GSIM_HIP(hipMemsetAsync(clk, 0, 4 * plan.size() * 8, stream));
+        if (!plan.empty()) GSIM_HIP(clocks.zero(plan.size(), stream));
         GSIM_HIP(hipEventRecord(ev_fold.a, stream));
         for (size_t l = 0; l < plan.size(); l++) {
-            a.clk = clk + 4 * l;
+            a.clk = clocks.at(l);
             GSIM_HIP(gsim::launch_mst_fold(a, plan[l].ot0, plan[l].not_, plan[l].c0, plan[l].c1, mst_chunks(plan[l]), stream));
         }
         GSIM_HIP(hipEventRecord(ev_fold.b, stream));
@@ -123,14 +122,10 @@ int mst(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, float beta
         GSIM_HIP(hipEventRecord(ev_round.b, stream));
         // the one read of the round: edges so far, owners of the next round
         unsigned long long h_ctl[gsim::kMstCtlWords] = {};
-        h_clk.assign(4 * plan.size(), 0);
         GSIM_HIP(hipMemcpyAsync(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, stream));
-        if (!plan.empty()) GSIM_HIP(hipMemcpyAsync(h_clk.data(), clk, h_clk.size() * 8, hipMemcpyDeviceToHost, stream));
+        GSIM_HIP(clocks.fetch(plan.size(), stream));
         GSIM_HIP(hipStreamSynchronize(stream));
-        for (size_t l = 0; l < plan.size(); l++) {
-            cyc += static_cast<double>(h_clk[4 * l + 2] - h_clk[4 * l]);
-            ticks += static_cast<double>(h_clk[4 * l + 3] - h_clk[4 * l + 1]);
-        }
+        clocks.add(); // (summed over the rounds)
         const double fold_ms = ev_fold.ms();
         ms.scan_owners[ms.scans] = nown;
         ms.scan_kernel_ms[ms.scans] = fold_ms;
@@ -167,7 +162,7 @@ int mst(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, float beta
         ms.edges = total;
         ms.sort_ms = ev_sort.ms();
         ms.d2h_ms = ev_d2h.ms();
-        ms.clock_mhz = ticks > 0.0 ? cyc / ticks * 100.0 : 0.0; // wall clock: 100 MHz
+        ms.clock_mhz = clocks.mhz();
         ms.wall_ms = wall();
         *st = ms;
     }

@@ -25,10 +25,9 @@ int neighbors(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, floa
     GSIM_HIP(set_device(s.device));
     const hipStream_t st = s.stream;
     // popc of every row, and the rows zero-padded to WP words unless they already are WP words
-    DevBuf<> pop, pad;
-    GSIM_HIP(pop.grow(N * 4));
-    if (WP != s.W) GSIM_HIP(pad.grow(N * WP * 4));
-    GSIM_HIP(gsim::launch_nbr_prepare(s.d_rows, N, s.W, WP, pad.as<uint32_t>(), pop.as<uint32_t>(), st));
+    PaddedRows table;
+    if (const int rc = table.alloc(N, s.W, WP)) return rc;
+    if (const int rc = table.prepare(s.d_rows, N, st)) return rc;
 
     const uint64_t nlt = (nout + gsim::kNbrTile - 1) / gsim::kNbrTile;
     const uint64_t nct = (N + gsim::kNbrTile - 1) / gsim::kNbrTile;
@@ -37,10 +36,11 @@ int neighbors(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, floa
     GSIM_HIP(ctl.grow((1 + 5 * plan.size()) * 8));
     unsigned long long* d_cursor = ctl.as<unsigned long long>();
     unsigned long long* d_snap = d_cursor + 1;
-    unsigned long long* d_clk = d_snap + plan.size();
+    LaunchClocks clocks;
+    clocks.view(d_snap + plan.size());
     gsim::NbrArgs a{};
-    a.rows = WP != s.W ? pad.as<uint32_t>() : static_cast<const uint32_t*>(s.d_rows);
-    a.pop = pop.as<uint32_t>();
+    a.rows = table.rows();
+    a.pop = table.pop();
     a.nrows = N;
     a.row_begin = rb;
     a.row_end = re;
@@ -58,7 +58,7 @@ int neighbors(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, floa
         al.vals = sink.vals;
         al.cursor = sink.cursor;
         al.cap = sink.cap;
-        al.clk = d_clk + 4 * l; // 4 words per launch (gsim::NbrArgs::clk)
+        al.clk = clocks.at(l);
         GSIM_HIP(gsim::launch_nbr_tiles(al, plan[l].rt0, plan[l].nrt, plan[l].ct0, plan[l].nct, st));
         return static_cast<int>(GSIM_OK);
     }, &run);
@@ -68,17 +68,10 @@ int neighbors(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, floa
     g->stats.launches_rerun = run.rerun;
     g->stats.tile_ms = run.ms;
     g->stats.pairs = tri ? total / 2 : total;
-    {
-        std::vector<unsigned long long> clk(4 * plan.size());
-        GSIM_HIP(hipMemcpyAsync(clk.data(), d_clk, clk.size() * 8, hipMemcpyDeviceToHost, st));
-        GSIM_HIP(hipStreamSynchronize(st));
-        double cyc = 0.0, ticks = 0.0;
-        for (size_t l = 0; l < plan.size(); l++) {
-            cyc += static_cast<double>(clk[4 * l + 2] - clk[4 * l]);
-            ticks += static_cast<double>(clk[4 * l + 3] - clk[4 * l + 1]);
-        }
-        g->stats.clock_mhz = ticks > 0.0 ? cyc / ticks * 100.0 : 0.0; // wall clock: 100 MHz
-    }
+    GSIM_HIP(clocks.fetch(plan.size(), st));
+    GSIM_HIP(hipStreamSynchronize(st));
+    clocks.add();
+    g->stats.clock_mhz = clocks.mhz();
     const int rc2 = build_pair_csr(db, s, total, nout, GSIM_JOIN_BY_ROW, g);
     if (rc2 != GSIM_OK) return rc2;
     g->stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -68,13 +68,11 @@ int scores(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, const Sco
         const uint32_t* d_right = static_cast<const uint32_t*>(s.d_rows) + c.r0 * W;
 
         // popc of every row of either side, and the rows zero-padded to WP words unless they already are WP words
-        DevBuf<> lpop, rpop, lpad, rpad, stage, ctl;
-        GSIM_ALLOC(lpop, nl * 4, "the score matrix (popcounts of the left rows)");
-        GSIM_ALLOC(rpop, nr * 4, "the score matrix (popcounts of the table rows)");
-        if (WP != W) {
-            GSIM_ALLOC(lpad, nl * WP * 4, "the score matrix (padded left rows)");
-            GSIM_ALLOC(rpad, nr * WP * 4, "the score matrix (padded table rows)");
-        }
+        PaddedRows left, right;
+        LaunchClocks clocks;
+        DevBuf<> stage;
+        if (const int rc = left.alloc(nl, W, WP, "the score matrix (popcounts of the left rows)", "the score matrix (padded left rows)")) return rc;
+        if (const int rc = right.alloc(nr, W, WP, "the score matrix (popcounts of the table rows)", "the score matrix (padded table rows)")) return rc;
         // host output: slabs of whole left rows through device memory
         const bool host_out = c.out != nullptr;
         uint64_t slab_rows = nl;
@@ -87,21 +85,21 @@ int scores(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, const Sco
         const uint64_t last_rows = nl - (nslabs - 1) * slab_rows;
         const std::vector<ScoresLaunch> plan_last = last_rows == slab_rows ? plan : plan_scores(last_rows, nr, WP, db->knobs.scores_launch_pairs);
         const size_t nlaunch = plan.size() * (nslabs - 1) + plan_last.size();
-        GSIM_ALLOC(ctl, 4 * nlaunch * 8, "the score matrix (clock stamps)");
-        GSIM_HIP(hipMemsetAsync(ctl, 0, 4 * nlaunch * 8, st));
+        if (const int rc = clocks.own(nlaunch, "the score matrix (clock stamps)")) return rc;
+        GSIM_HIP(clocks.zero(nlaunch, st));
 
         EventPair ev_prep, ev_run, ev_d2h;
         GSIM_HIP(ev_prep.create());
         GSIM_HIP(ev_run.create());
         GSIM_HIP(ev_d2h.create());
         GSIM_HIP(hipEventRecord(ev_prep.a, st));
-        GSIM_HIP(gsim::launch_nbr_prepare(d_left, nl, W, WP, lpad.as<uint32_t>(), lpop.as<uint32_t>(), st));
-        GSIM_HIP(gsim::launch_nbr_prepare(d_right, nr, W, WP, rpad.as<uint32_t>(), rpop.as<uint32_t>(), st));
+        if (const int rc = left.prepare(d_left, nl, st)) return rc;
+        if (const int rc = right.prepare(d_right, nr, st)) return rc;
         GSIM_HIP(hipEventRecord(ev_prep.b, st));
 
         gsim::ScoresArgs a{};
-        a.rrows = WP != W ? rpad.as<uint32_t>() : d_right;
-        a.rpop = rpop.as<uint32_t>();
+        a.rrows = right.rows();
+        a.rpop = right.pop();
         a.nr = nr;
         a.WP = WP;
         a.metric = c.metric;
@@ -110,14 +108,14 @@ int scores(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, const Sco
         size_t launched = 0;
         for (uint64_t sl = 0; sl < nslabs; sl++) {
             const uint64_t first = sl * slab_rows, rows = std::min(slab_rows, nl - first);
-            a.lrows = (WP != W ? lpad.as<uint32_t>() : d_left) + first * WP;
-            a.lpop = lpop.as<uint32_t>() + first;
+            a.lrows = left.rows() + first * WP;
+            a.lpop = left.pop() + first;
             a.nl = rows;
             a.out = host_out ? stage.as<float>() : c.d_out + first * c.ld;
             a.ld = host_out ? nr : c.ld;
             GSIM_HIP(hipEventRecord(ev_run.a, st));
             for (const ScoresLaunch& l : sl + 1 == nslabs ? plan_last : plan) {
-                a.clk = ctl.as<unsigned long long>() + 4 * launched++;
+                a.clk = clocks.at(launched++);
                 GSIM_HIP(gsim::launch_scores(a, l.l0, l.l1, l.r0, l.r1, st));
             }
             GSIM_HIP(hipEventRecord(ev_run.b, st));
@@ -136,15 +134,10 @@ int scores(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, const Sco
         ss.launches = nlaunch;
         ss.slabs = host_out ? nslabs : 0;
         ss.prepare_ms = ev_prep.ms();
-        std::vector<unsigned long long> clk(4 * nlaunch);
-        GSIM_HIP(hipMemcpyAsync(clk.data(), ctl, clk.size() * 8, hipMemcpyDeviceToHost, st));
+        GSIM_HIP(clocks.fetch(nlaunch, st));
         GSIM_HIP(hipStreamSynchronize(st));
-        double cyc = 0.0, ticks = 0.0;
-        for (size_t l = 0; l < nlaunch; l++) {
-            cyc += static_cast<double>(clk[4 * l + 2] - clk[4 * l]);
-            ticks += static_cast<double>(clk[4 * l + 3] - clk[4 * l + 1]);
-        }
-        ss.clock_mhz = ticks > 0.0 ? cyc / ticks * 100.0 : 0.0; // wall clock: 100 MHz
+        clocks.add();
+        ss.clock_mhz = clocks.mhz();
     }
     ss.wall_ms = wall();
     if (c.stats) *c.stats = ss;

@@ -59,10 +59,7 @@ __global__ __launch_bounds__(kScoresBlock) __attribute__((amdgpu_waves_per_eu(2,
     const int wr = wq >> 1, wc = wq & 1; // this wave's quarter: centres wr * 64 .. of a block, table rows wc * 64 ..
     const u64 rb = r0 + static_cast<u64>(blockIdx.x) * kScoresTile; // this workgroup's first table row (it exists)
     const bool stamp = a.clk && blockIdx.x == 0 && tid == 0;
-    if (stamp) {
-        a.clk[0] = clock64();
-        a.clk[1] = wall_clock64();
-    }
+    if (stamp) stamp_begin(a.clk);
 
     // ---- staging: thread t loads chunk t % 8 of line t / 8 + 32 p, p = 0 .. 7 (lines 0..127: centres, 128..255: table rows) ----
     const int chunk = tid & (kAssignStageChunks - 1);
@@ -208,10 +205,7 @@ __global__ __launch_bounds__(kScoresBlock) __attribute__((amdgpu_waves_per_eu(2,
             a.score[row] = __uint_as_float(static_cast<uint32_t>(k >> 32));
         }
     }
-    if (stamp) {
-        a.clk[2] = clock64();
-        a.clk[3] = wall_clock64();
-    }
+    if (stamp) stamp_end(a.clk);
 }
 
 } // namespace

@@ -2,9 +2,9 @@
 // gsim_db_components: the pair scoring of gsim_neighbors.hip's tile kernel, every kept pair fed to a union-find forest in device
 // memory instead of being stored, one forest per cutoff level.  Nothing of the graph is ever written.
 //
-// Tile kernel (comp_tile_kernel<WP, L>): nbr_tile_kernel's upper-triangle scheme -- a workgroup owns kNbrTile x kNbrTile rows,
-// each lane of its four waves holds one right row in VGPRs, the left row's words come through the scalar path, the division-free
-// band of gsim_prefilter.h runs against cutoffs[0] (the loosest level) and the divide only where a lane may be kept.  ONE pass per
+// Tile kernel (comp_tile_kernel<WP, L>): the held-row pair count of gsim_held_row.h in nbr_tile_kernel's upper-triangle layout -- a
+// workgroup owns kNbrTile x kNbrTile rows, each lane of its four waves holds one right row, the left rows are the uniform side, the
+// division-free band of gsim_prefilter.h runs against cutoffs[0] (the loosest level) and the divide only where a lane may be kept.  ONE pass per
 // tile: no counting pass, no cursor, no pair stores.  A kept pair (i, j), j > i, with score s unites i and j in forest l for every
 // level l with s >= cutoffs[l].
 //
@@ -45,14 +45,13 @@
 
 #include "../../include/gpusim_hip.h"
 #include "gsim_device_common.h"
+#include "gsim_held_row.h"
 #include "gsim_prefilter.h"
 
 namespace gsim
 {
 namespace
 {
-
-typedef const __attribute__((address_space(4))) u32x4* const_u32x4p;
 
 __device__ __forceinline__ uint32_t parent_load(const uint32_t* p)
 {
@@ -119,21 +118,12 @@ template <int WP, int L> __global__ __launch_bounds__(kNbrBlock) void comp_tile_
     const u64 iend = i0 + kNbrTile < a.nrows ? i0 + kNbrTile : a.nrows;
     // the clock this launch ran at: shader cycles (s_memtime) against the 100 MHz wall clock over one full tile
     const bool stamp = a.clk && blockIdx.x == gridDim.x - 1 && blockIdx.y == 0 && threadIdx.x == 0;
-    if (stamp) {
-        a.clk[0] = clock64();
-        a.clk[1] = wall_clock64();
-    }
+    if (stamp) stamp_begin(a.clk);
     const u64 j = static_cast<u64>(ct) * kNbrTile + wib * 64u + static_cast<uint32_t>(lane);
     const bool jin = j < a.nrows;
 
-    // this lane's right row, whole, in VGPRs (zero words beyond the row: nothing to count there)
-    u32x4 r4[WP / 4];
-    const u32x4* rp = reinterpret_cast<const u32x4*>(a.rows) + (jin ? j : 0) * (WP / 4);
-#pragma unroll
-    for (int k = 0; k < WP / 4; k++) r4[k] = jin ? rp[k] : u32x4{0, 0, 0, 0};
-    uint32_t b = 0;
-#pragma unroll
-    for (int k = 0; k < WP / 4; k++) b += __popc(r4[k].x) + __popc(r4[k].y) + __popc(r4[k].z) + __popc(r4[k].w);
+    HeldRow<WP> right; // this lane's right row
+    const uint32_t b = right.load(a.rows, jin ? j : 0, jin);
 
     uint32_t nl = static_cast<uint32_t>(iend - i0);
     // diagonal tile: left row i0 + t pairs with some right row of this wave only if t < 64 wib + 63
@@ -151,28 +141,20 @@ template <int WP, int L> __global__ __launch_bounds__(kNbrBlock) void comp_tile_
     const float cut0 = a.cutoffs[0];
     const float cut_lo = valu_cutoff_lo(cut0);
     const const_u32x4p lrows = (const_u32x4p) (a.rows) + i0 * (WP / 4);
-    uint32_t vpop = 0, kept = 0, hooks = 0, lost = 0;
+    Handout64 vpop; // popc of the left rows
+    uint32_t kept = 0, hooks = 0, lost = 0;
     for (uint32_t t = 0; t < nl; t++) {
-        if ((t & 63u) == 0) { // popc and the cached roots of the next 64 left rows, one per lane (read back with v_readlane)
+        if (Handout64::due(t)) { // ... and their cached roots, one per lane too
+            vpop.fetch(a.pop, i0 + t, static_cast<uint32_t>(lane), iend);
             const u64 il = i0 + t + static_cast<uint32_t>(lane);
-            vpop = il < iend ? a.pop[il] : 0u;
 #pragma unroll
             for (int l = 0; l < L; l++)
                 if (l < static_cast<int>(a.nlevels)) vroot[l] = il < iend ? parent_load(a.parent + static_cast<u64>(l) * a.nrows + il) : 0u;
         }
-        const uint32_t av = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(vpop), static_cast<int>(t & 63u)));
+        const uint32_t av = vpop.get(t);
         // left row t against this lane's right row: keep == (score_of(...) >= cutoffs[0]), s = that score
         const const_u32x4p qw = lrows + static_cast<u64>(t) * (WP / 4);
-        uint32_t acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
-#pragma unroll
-        for (int k = 0; k < WP / 4; k++) {
-            const u32x4 q = qw[k]; // s_load: the left row is wave-uniform
-            acc0 = bcnt_acc(r4[k].x & q.x, acc0);
-            acc1 = bcnt_acc(r4[k].y & q.y, acc1);
-            acc2 = bcnt_acc(r4[k].z & q.z, acc2);
-            acc3 = bcnt_acc(r4[k].w & q.w, acc3);
-        }
-        const uint32_t c = (acc0 + acc1) + (acc2 + acc3);
+        const uint32_t c = right.common(qw);
         const u64 i = i0 + t;
         const bool valid = jin && j > i;
         const float den = score_den(a.metric, a.alpha, a.beta, av, b, c);
@@ -224,10 +206,7 @@ template <int WP, int L> __global__ __launch_bounds__(kNbrBlock) void comp_tile_
             if (lost) atomicAdd(a.counters + 2, static_cast<u64>(lost));
         }
     }
-    if (stamp) {
-        a.clk[2] = clock64();
-        a.clk[3] = wall_clock64();
-    }
+    if (stamp) stamp_end(a.clk);
 }
 
 // parent_l[x] = root(x), one thread per (level, row): every thread climbs to its root (other threads' stores only ever put an
@@ -294,15 +273,7 @@ hipError_t launch_comp_init(uint32_t* parent, uint64_t nrows, uint32_t nlevels, 
 hipError_t launch_comp_tiles(const CompArgs& a, uint32_t rt0, uint32_t nrt, uint32_t ct0, uint32_t nct, hipStream_t s)
 {
     if (a.nlevels < 1 || a.nlevels > kCompMaxLevels) return hipErrorInvalidValue;
-    switch (a.WP) {
-    case 4: return launch_tiles_wp<4>(a, rt0, nrt, ct0, nct, s);
-    case 8: return launch_tiles_wp<8>(a, rt0, nrt, ct0, nct, s);
-    case 16: return launch_tiles_wp<16>(a, rt0, nrt, ct0, nct, s);
-    case 32: return launch_tiles_wp<32>(a, rt0, nrt, ct0, nct, s);
-    case 64: return launch_tiles_wp<64>(a, rt0, nrt, ct0, nct, s);
-    case 128: return launch_tiles_wp<128>(a, rt0, nrt, ct0, nct, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_wp(a.WP, [&](auto wp) { return launch_tiles_wp<decltype(wp)::value>(a, rt0, nrt, ct0, nct, s); });
 }
 
 hipError_t launch_comp_flatten(uint32_t* parent, uint64_t nrows, uint32_t nlevels, hipStream_t s)

@@ -108,6 +108,20 @@ __device__ __forceinline__ float apply_cutoff(float s, float cutoff)
     return s >= cutoff ? s : 0.0f;
 }
 
+// The clock a launch ran at: shader cycles (s_memtime) against the 100 MHz wall clock, four words per launch.  Which thread
+// stamps is the kernel's own condition; the host's half is LaunchClocks (capi_internal.h).  Used by
+// nbr_tile_kernel, comp_tile_kernel, knn_fold_kernel, mst_fold_kernel, hist_tile_kernel, scores_kernel and assign_kernel.
+__device__ __forceinline__ void stamp_begin(unsigned long long* clk)
+{
+    clk[0] = clock64();
+    clk[1] = wall_clock64();
+}
+__device__ __forceinline__ void stamp_end(unsigned long long* clk)
+{
+    clk[2] = clock64();
+    clk[3] = wall_clock64();
+}
+
 // ---------------------------------------------------------------------------
 // cross-lane helpers (wave64)
 // ---------------------------------------------------------------------------

@@ -42,6 +42,7 @@
 
 #include "../../include/gpusim_hip.h"
 #include "gsim_device_common.h"
+#include "gsim_held_row.h"
 #include "gsim_prefilter.h"
 #include "gsim_scan_inl.h"
 
@@ -49,13 +50,6 @@ namespace gsim
 {
 namespace
 {
-
-typedef const __attribute__((address_space(4))) u32x4* const_u32x4p;
-
-__device__ __forceinline__ uint32_t readlane_u32(uint32_t v, uint32_t l)
-{
-    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), static_cast<int>(l)));
-}
 
 // bin(s); edges / coarse in LDS
 __device__ __forceinline__ uint32_t hist_bin(float s, const float* edges, const uint8_t* coarse, uint32_t nedges)
@@ -209,10 +203,7 @@ __global__ __launch_bounds__(kHistBlock) void hist_tile_kernel(HistTileArgs a, u
     const u64 o0 = (static_cast<u64>(ot0) + blockIdx.x) * kHistTile + wib * 64u;
     if (o0 >= a.nl) return; // (wave-uniform; no barrier behind this point)
     const bool stamp = a.clk && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;
-    if (stamp) {
-        a.clk[0] = clock64();
-        a.clk[1] = wall_clock64();
-    }
+    if (stamp) stamp_begin(a.clk);
     const u64 o = o0 + lane;
     const bool oin = o < a.nl; // a lane past the last owner is idle, but takes part in the ballots
     const u64 self = a.self0 != ~0ull && oin ? a.self0 + o : ~0ull;
@@ -277,10 +268,7 @@ __global__ __launch_bounds__(kHistBlock) void hist_tile_kernel(HistTileArgs a, u
         const uint32_t v = (wcnt[ow * stride + (bin >> 1)] >> ((bin & 1u) * 16u)) & 0xFFFFu;
         if (v) atomicAdd(&out[i], static_cast<u64>(v));
     }
-    if (stamp) {
-        a.clk[2] = clock64();
-        a.clk[3] = wall_clock64();
-    }
+    if (stamp) stamp_end(a.clk);
 }
 
 template <int WP>
@@ -338,15 +326,8 @@ hipError_t launch_hist_tiles(const HistTileArgs& a, uint32_t ot0, uint32_t not_,
     if (a.bins.nedges < 1 || a.bins.nedges > GSIM_HIST_MAX_EDGES || c1 > a.nrows || chunk == 0 || chunk > kHistMaxChunk || chunk % kHistColTile ||
         (static_cast<u64>(ot0) + not_ - 1) * kHistTile >= a.nl)
         return hipErrorInvalidValue;
-    switch (a.WP) {
-    case 4: return launch_tiles_t<4>(a, ot0, not_, c0, c1, chunk, s);
-    case 8: return launch_tiles_t<8>(a, ot0, not_, c0, c1, chunk, s);
-    case 16: return launch_tiles_t<16>(a, ot0, not_, c0, c1, chunk, s);
-    case 32: return launch_tiles_t<32>(a, ot0, not_, c0, c1, chunk, s);
-    case 64: return launch_tiles_t<64>(a, ot0, not_, c0, c1, chunk, s);
-    case 128: return launch_tiles_t<128>(a, ot0, not_, c0, c1, chunk, s);
-    default: return hipErrorInvalidValue;
-    }
+    // (launch_tiles_t<WP> keeps its own DynLdsOnce: the dynamic-LDS attribute is set once per instantiation)
+    return dispatch_wp(a.WP, [&](auto wp) { return launch_tiles_t<decltype(wp)::value>(a, ot0, not_, c0, c1, chunk, s); });
 }
 
 hipError_t launch_hist_pass(const HistStreamArgs& m, const ScanGeometry& g, uint64_t r0, uint64_t nrows, uint32_t p, hipStream_t s)

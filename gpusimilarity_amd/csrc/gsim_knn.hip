@@ -35,19 +35,13 @@
 
 #include "../../include/gpusim_hip.h"
 #include "gsim_device_common.h"
+#include "gsim_held_row.h"
 #include "gsim_prefilter.h"
 
 namespace gsim
 {
 namespace
 {
-
-typedef const __attribute__((address_space(4))) u32x4* const_u32x4p;
-
-__device__ __forceinline__ uint32_t readlane_u32(uint32_t v, uint32_t l)
-{
-    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), static_cast<int>(l)));
-}
 
 template <int WP> __global__ __launch_bounds__(kKnnBlock) void knn_fold_kernel(KnnArgs a, uint32_t ot0, u64 c0, u64 c1)
 {
@@ -58,10 +52,7 @@ template <int WP> __global__ __launch_bounds__(kKnnBlock) void knn_fold_kernel(K
     const u64 nown = a.row_end - a.row_begin;
     if (o0 >= nown) return; // (wave-uniform; the kernel has no barrier)
     const bool stamp = a.clk && blockIdx.x == 0 && threadIdx.x == 0;
-    if (stamp) {
-        a.clk[0] = clock64();
-        a.clk[1] = wall_clock64();
-    }
+    if (stamp) stamp_begin(a.clk);
     const u64 o = o0 + lane;
     const bool oin = o < nown; // a lane past the last owner is idle, but takes part in the ballots
     const uint32_t i = static_cast<uint32_t>(a.row_begin + (oin ? o : 0));
@@ -145,10 +136,7 @@ template <int WP> __global__ __launch_bounds__(kKnnBlock) void knn_fold_kernel(K
     }
     if (oin) a.len[o] = len;
     if (inserts && lane == 0) atomicAdd(a.inserts, static_cast<u64>(inserts));
-    if (stamp) {
-        a.clk[2] = clock64();
-        a.clk[3] = wall_clock64();
-    }
+    if (stamp) stamp_end(a.clk);
 }
 
 // entry (owner, slot) of the lists -> position indptr[owner] + slot of indices (+ row_base) and scores
@@ -172,16 +160,10 @@ hipError_t launch_knn_fold(const KnnArgs& a, uint32_t ot0, uint32_t not_, uint64
     if (not_ == 0 || c0 >= c1) return hipSuccess;
     if (a.k < 1 || a.k > GSIM_KNN_MAX_K || c1 > a.nrows || a.row_end > a.nrows) return hipErrorInvalidValue;
     const dim3 grid(not_), block(kKnnBlock);
-    switch (a.WP) {
-    case 4: hipLaunchKernelGGL(knn_fold_kernel<4>, grid, block, 0, s, a, ot0, static_cast<u64>(c0), static_cast<u64>(c1)); break;
-    case 8: hipLaunchKernelGGL(knn_fold_kernel<8>, grid, block, 0, s, a, ot0, static_cast<u64>(c0), static_cast<u64>(c1)); break;
-    case 16: hipLaunchKernelGGL(knn_fold_kernel<16>, grid, block, 0, s, a, ot0, static_cast<u64>(c0), static_cast<u64>(c1)); break;
-    case 32: hipLaunchKernelGGL(knn_fold_kernel<32>, grid, block, 0, s, a, ot0, static_cast<u64>(c0), static_cast<u64>(c1)); break;
-    case 64: hipLaunchKernelGGL(knn_fold_kernel<64>, grid, block, 0, s, a, ot0, static_cast<u64>(c0), static_cast<u64>(c1)); break;
-    case 128: hipLaunchKernelGGL(knn_fold_kernel<128>, grid, block, 0, s, a, ot0, static_cast<u64>(c0), static_cast<u64>(c1)); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_wp(a.WP, [&](auto wp) {
+        hipLaunchKernelGGL(knn_fold_kernel<decltype(wp)::value>, grid, block, 0, s, a, ot0, static_cast<u64>(c0), static_cast<u64>(c1));
+        return hipGetLastError();
+    });
 }
 
 hipError_t knn_scan_bytes(uint64_t n, size_t* bytes)

@@ -57,19 +57,13 @@
 
 #include "../../include/gpusim_hip.h"
 #include "gsim_device_common.h"
+#include "gsim_held_row.h"
 #include "gsim_prefilter.h"
 
 namespace gsim
 {
 namespace
 {
-
-typedef const __attribute__((address_space(4))) u32x4* const_u32x4p;
-
-__device__ __forceinline__ uint32_t readlane_u32(uint32_t v, uint32_t l)
-{
-    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), static_cast<int>(l)));
-}
 
 template <int WP> __global__ __launch_bounds__(kKnnBlock) void mst_fold_kernel(MstArgs a, uint32_t ot0, u64 c0, u64 c1, u64 per)
 {
@@ -82,10 +76,7 @@ template <int WP> __global__ __launch_bounds__(kKnnBlock) void mst_fold_kernel(M
     if (p0 >= c1) return;
     const u64 p1 = p0 + per < c1 ? p0 + per : c1;
     const bool stamp = a.clk && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;
-    if (stamp) {
-        a.clk[0] = clock64();
-        a.clk[1] = wall_clock64();
-    }
+    if (stamp) stamp_begin(a.clk);
     const u64 o = o0 + lane;
     const bool oin = o < a.nown; // a lane past the last owner is idle, but takes part in the ballots
     const uint32_t i = oin ? a.own[o] : 0u;
@@ -141,10 +132,7 @@ template <int WP> __global__ __launch_bounds__(kKnnBlock) void mst_fold_kernel(M
         }
     }
     if (held != found) atomicMax(a.best + i, held);
-    if (stamp) {
-        a.clk[2] = clock64();
-        a.clk[3] = wall_clock64();
-    }
+    if (stamp) stamp_end(a.clk);
 }
 
 __global__ __launch_bounds__(256) void mst_init_kernel(MstState m)
@@ -270,16 +258,10 @@ hipError_t launch_mst_fold(const MstArgs& a, uint32_t ot0, uint32_t not_, uint64
     const u64 per = ((c1 - c0 + nchunk - 1) / nchunk + 63u) / 64u * 64u;
     const dim3 grid(not_, nchunk), block(kKnnBlock);
     const u64 b0 = c0, b1 = c1;
-    switch (a.WP) {
-    case 4: hipLaunchKernelGGL(mst_fold_kernel<4>, grid, block, 0, s, a, ot0, b0, b1, per); break;
-    case 8: hipLaunchKernelGGL(mst_fold_kernel<8>, grid, block, 0, s, a, ot0, b0, b1, per); break;
-    case 16: hipLaunchKernelGGL(mst_fold_kernel<16>, grid, block, 0, s, a, ot0, b0, b1, per); break;
-    case 32: hipLaunchKernelGGL(mst_fold_kernel<32>, grid, block, 0, s, a, ot0, b0, b1, per); break;
-    case 64: hipLaunchKernelGGL(mst_fold_kernel<64>, grid, block, 0, s, a, ot0, b0, b1, per); break;
-    case 128: hipLaunchKernelGGL(mst_fold_kernel<128>, grid, block, 0, s, a, ot0, b0, b1, per); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_wp(a.WP, [&](auto wp) {
+        hipLaunchKernelGGL(mst_fold_kernel<decltype(wp)::value>, grid, block, 0, s, a, ot0, b0, b1, per);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_mst_init(const MstState& m, hipStream_t s)

@@ -1,13 +1,13 @@
 // gsim_neighbors.hip -- all-pairs neighbour lists above a cutoff (the similarity self-join behind gsim_db_neighbors)
 // and the device half of their CSR.
 //
-// Tile kernel: the scalar-operand VALU scheme of batch_scan_kernel (gsim_batch.hip) with the table on both sides.
+// Tile kernel: the held-row pair count of gsim_held_row.h (the scalar-operand VALU scheme of batch_scan_kernel, gsim_batch.hip,
+// with the table on both sides).
 //   * a workgroup owns a tile of kNbrTile left rows x kNbrTile right rows; each of its four waves holds 64 right rows,
-//     one whole (zero-padded) fingerprint per lane in VGPRs, and walks the tile's left rows one by one;
-//   * the left row's words are wave-uniform: read through the scalar path and used as the SGPR operand of v_and_b32,
-//     so a (left, right) word-pair costs v_and + the accumulating v_bcnt_u32_b32;
-//   * popc(left row) comes from a side array made once per call (nbr_prepare_kernel), popc(right row) from the lane's
-//     own registers;
+//     one whole (zero-padded) fingerprint per lane in VGPRs (HeldRow), and walks the tile's left rows one by one;
+//   * the left row's words are wave-uniform: a (left, right) word-pair costs v_and + the accumulating v_bcnt_u32_b32;
+//   * popc(left row) comes from a side array made once per call (nbr_prepare_kernel) through Handout64, popc(right row)
+//     from the lane's own registers;
 //   * the keep decision is exactly score_of(...) >= cutoff: the division-free band of gsim_prefilter.h
 //     (valu_surely_not_kept, proven on the host by tests/cpp/prefilter_check.cpp) drops almost every pair with one
 //     multiply and a compare, and every pair it lets through is scored with the reference's divide;
@@ -26,14 +26,13 @@
 
 #include "../../include/gpusim_hip.h"
 #include "gsim_device_common.h"
+#include "gsim_held_row.h"
 #include "gsim_prefilter.h"
 
 namespace gsim
 {
 namespace
 {
-
-typedef const __attribute__((address_space(4))) u32x4* const_u32x4p;
 
 // popc of every row, and (pad != nullptr) the rows copied to WP words with zero words after the first W
 __global__ __launch_bounds__(256) void nbr_prepare_kernel(const uint32_t* __restrict__ rows, u64 nrows, uint32_t W, uint32_t WP,
@@ -84,21 +83,12 @@ __global__ __launch_bounds__(kNbrBlock) void nbr_tile_kernel(Args a, uint32_t rt
     const u64 iend = i0 + kNbrTile < a.row_end ? i0 + kNbrTile : a.row_end;
     // the clock this launch ran at: shader cycles (s_memtime) against the 100 MHz wall clock over one full tile
     const bool stamp = a.clk && blockIdx.x == gridDim.x - 1 && blockIdx.y == 0 && threadIdx.x == 0;
-    if (stamp) {
-        a.clk[0] = clock64();
-        a.clk[1] = wall_clock64();
-    }
+    if (stamp) stamp_begin(a.clk);
     const u64 j = static_cast<u64>(ct) * kNbrTile + wib * 64u + static_cast<uint32_t>(lane);
     const bool jin = j < a.nrows;
 
-    // this lane's right row, whole, in VGPRs (zero words beyond the row: nothing to count there)
-    u32x4 r4[WP / 4];
-    const u32x4* rp = reinterpret_cast<const u32x4*>(a.rows) + (jin ? j : 0) * (WP / 4);
-#pragma unroll
-    for (int k = 0; k < WP / 4; k++) r4[k] = jin ? rp[k] : u32x4{0, 0, 0, 0};
-    uint32_t b = 0;
-#pragma unroll
-    for (int k = 0; k < WP / 4; k++) b += __popc(r4[k].x) + __popc(r4[k].y) + __popc(r4[k].z) + __popc(r4[k].w);
+    HeldRow<WP> right; // this lane's right row
+    const uint32_t b = right.load(a.rows, jin ? j : 0, jin);
 
     uint32_t nl = static_cast<uint32_t>(iend - i0);
     // diagonal tile (i0 == first right row of the tile): left row i0 + t pairs with some right row of this wave only if
@@ -111,16 +101,7 @@ __global__ __launch_bounds__(kNbrBlock) void nbr_tile_kernel(Args a, uint32_t rt
     // left row t against this lane's right row: keep == (score_of(...) >= cutoff), s = that score
     auto pair = [&](uint32_t t, uint32_t av, float& s) __attribute__((always_inline)) -> bool {
         const const_u32x4p qw = lrows + static_cast<u64>(t) * (WP / 4);
-        uint32_t acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
-#pragma unroll
-        for (int k = 0; k < WP / 4; k++) {
-            const u32x4 q = qw[k]; // s_load: the left row is wave-uniform
-            acc0 = bcnt_acc(r4[k].x & q.x, acc0);
-            acc1 = bcnt_acc(r4[k].y & q.y, acc1);
-            acc2 = bcnt_acc(r4[k].z & q.z, acc2);
-            acc3 = bcnt_acc(r4[k].w & q.w, acc3);
-        }
-        const uint32_t c = (acc0 + acc1) + (acc2 + acc3);
+        const uint32_t c = right.common(qw);
         const u64 i = i0 + t;
         const bool valid = JOIN ? jin : jin && (tile_tri<JOIN>(a) ? j > i : j != i);
         const float den = score_den(a.metric, a.alpha, a.beta, av, b, c);
@@ -136,13 +117,11 @@ __global__ __launch_bounds__(kNbrBlock) void nbr_tile_kernel(Args a, uint32_t rt
     // whose every pair is kept costs twice the arithmetic but 1 atomic instead of 256.
     __shared__ uint32_t s_rows[kNbrBlock / 64][kNbrTile / 32];
     if (lane < kNbrTile / 32) s_rows[wib][lane] = 0u;
-    uint32_t vpop = 0, cnt = 0;
+    Handout64 vpop; // popc of the left rows
+    uint32_t cnt = 0;
     for (uint32_t t = 0; t < nl; t++) {
-        if ((t & 63u) == 0) { // popc of the next 64 left rows, one per lane (read back with v_readlane)
-            const u64 il = i0 + t + static_cast<uint32_t>(lane);
-            vpop = il < iend ? tile_left_pop<JOIN>(a)[il] : 0u;
-        }
-        const uint32_t av = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(vpop), static_cast<int>(t & 63u)));
+        if (Handout64::due(t)) vpop.fetch(tile_left_pop<JOIN>(a), i0 + t, static_cast<uint32_t>(lane), iend);
+        const uint32_t av = vpop.get(t);
         float s;
         const u64 m = __ballot(pair(t, av, s));
         if (m == 0) continue;
@@ -179,10 +158,7 @@ __global__ __launch_bounds__(kNbrBlock) void nbr_tile_kernel(Args a, uint32_t rt
             }
         }
     }
-    if (stamp) {
-        a.clk[2] = clock64();
-        a.clk[3] = wall_clock64();
-    }
+    if (stamp) stamp_end(a.clk);
 }
 
 __global__ void nbr_snap_kernel(const u64* cursor, u64* snap)
@@ -230,31 +206,19 @@ hipError_t launch_nbr_prepare(const void* rows, uint64_t nrows, uint32_t W, uint
 hipError_t launch_nbr_tiles(const NbrArgs& a, uint32_t rt0, uint32_t nrt, uint32_t ct0, uint32_t nct, hipStream_t s)
 {
     const dim3 grid(nct, nrt), block(kNbrBlock);
-    switch (a.WP) {
-    case 4: hipLaunchKernelGGL(nbr_tile_kernel<4>, grid, block, 0, s, a, rt0, ct0); break;
-    case 8: hipLaunchKernelGGL(nbr_tile_kernel<8>, grid, block, 0, s, a, rt0, ct0); break;
-    case 16: hipLaunchKernelGGL(nbr_tile_kernel<16>, grid, block, 0, s, a, rt0, ct0); break;
-    case 32: hipLaunchKernelGGL(nbr_tile_kernel<32>, grid, block, 0, s, a, rt0, ct0); break;
-    case 64: hipLaunchKernelGGL(nbr_tile_kernel<64>, grid, block, 0, s, a, rt0, ct0); break;
-    case 128: hipLaunchKernelGGL(nbr_tile_kernel<128>, grid, block, 0, s, a, rt0, ct0); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_wp(a.WP, [&](auto wp) {
+        hipLaunchKernelGGL(nbr_tile_kernel<decltype(wp)::value>, grid, block, 0, s, a, rt0, ct0);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_join_tiles(const JoinTileArgs& a, uint32_t rt0, uint32_t nrt, uint32_t ct0, uint32_t nct, hipStream_t s)
 {
     const dim3 grid(nct, nrt), block(kNbrBlock);
-    switch (a.WP) {
-    case 4: hipLaunchKernelGGL((nbr_tile_kernel<4, true, JoinTileArgs>), grid, block, 0, s, a, rt0, ct0); break;
-    case 8: hipLaunchKernelGGL((nbr_tile_kernel<8, true, JoinTileArgs>), grid, block, 0, s, a, rt0, ct0); break;
-    case 16: hipLaunchKernelGGL((nbr_tile_kernel<16, true, JoinTileArgs>), grid, block, 0, s, a, rt0, ct0); break;
-    case 32: hipLaunchKernelGGL((nbr_tile_kernel<32, true, JoinTileArgs>), grid, block, 0, s, a, rt0, ct0); break;
-    case 64: hipLaunchKernelGGL((nbr_tile_kernel<64, true, JoinTileArgs>), grid, block, 0, s, a, rt0, ct0); break;
-    case 128: hipLaunchKernelGGL((nbr_tile_kernel<128, true, JoinTileArgs>), grid, block, 0, s, a, rt0, ct0); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_wp(a.WP, [&](auto wp) {
+        hipLaunchKernelGGL((nbr_tile_kernel<decltype(wp)::value, true, JoinTileArgs>), grid, block, 0, s, a, rt0, ct0);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_nbr_snap(const unsigned long long* cursor, unsigned long long* snap, hipStream_t s)

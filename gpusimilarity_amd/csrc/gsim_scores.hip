@@ -61,10 +61,7 @@ __global__ __launch_bounds__(kScoresBlock) void scores_kernel(ScoresArgs a, u64 
     const u64 lb = l0 + static_cast<u64>(blockIdx.y) * kScoresTile;
     const u64 rb = r0 + static_cast<u64>(blockIdx.x) * kScoresTile;
     const bool stamp = a.clk && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0;
-    if (stamp) {
-        a.clk[0] = clock64();
-        a.clk[1] = wall_clock64();
-    }
+    if (stamp) stamp_begin(a.clk);
 
     // ---- staging: thread t loads chunk t % 8 of line t / 8 + 32 p, p = 0 .. 7 (lines 0..127: left rows, 128..255: table rows) ----
     const int chunk = tid & (kScoresStageChunks - 1);
@@ -185,10 +182,7 @@ __global__ __launch_bounds__(kScoresBlock) void scores_kernel(ScoresArgs a, u64 
             }
         }
     }
-    if (stamp) {
-        a.clk[2] = clock64();
-        a.clk[3] = wall_clock64();
-    }
+    if (stamp) stamp_end(a.clk);
 }
 
 } // namespace

@@ -157,9 +157,10 @@ def as_bytes(level):
     return b"".join(x.tobytes() for x in level)
 
 
-@pytest.mark.parametrize("bits", [128, 160, 1024, 2048])
+@pytest.mark.parametrize("bits", [128, 160, 512, 1024, 2048, 4096])
 def test_parity_with_the_oracle(bits):
-    """1000 rows: three full tiles and a partial one, diagonal and off-diagonal; 160 bits takes the zero-padded copy"""
+    """1000 rows: three full tiles and a partial one, diagonal and off-diagonal; 160 bits takes the zero-padded copy; the six widths
+    are the six instantiations of the tile kernel (4, 8, 16, 32, 64 and 128 words a row)"""
     n = 1000
     db, links, S = planted_table(bits)
     t = table(db)
