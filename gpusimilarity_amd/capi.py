@@ -31,6 +31,7 @@ GROUP_MEAN = 2
 GROUP_MAX_QUERIES = 1024
 LEADER_NONE = 0xFFFFFFFF
 KNN_MAX_K = 128
+KNN_EXCLUDE_SELF = 1
 HIST_MAX_EDGES = 128
 HIST_EXCLUDE_SELF = 1
 
@@ -86,6 +87,13 @@ class GsimKnnStats(C.Structure):
     _fields_ = [("rows", C.c_uint64), ("launches", C.c_uint64), ("pairs", C.c_uint64), ("inserts", C.c_uint64),
                 ("entries", C.c_uint64), ("kernel_ms", C.c_double), ("csr_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
+
+
+class GsimKnnJoinStats(C.Structure):
+    _fields_ = [("left_rows", C.c_uint64), ("table_rows", C.c_uint64), ("segments", C.c_uint64), ("fold_launches", C.c_uint64),
+                ("merge_launches", C.c_uint64), ("pairs", C.c_uint64), ("inserts", C.c_uint64), ("partial_entries", C.c_uint64),
+                ("entries", C.c_uint64), ("kernel_ms", C.c_double), ("merge_ms", C.c_double), ("csr_ms", C.c_double),
+                ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
 
 
 class GsimHistStats(C.Structure):
@@ -172,6 +180,7 @@ EXPORTS = [
     "gsim_db_search_group",
     "gsim_db_leader",
     "gsim_db_knn", "gsim_graph_get_knn_stats",
+    "gsim_db_knn_join", "gsim_db_knn_queries", "gsim_graph_get_knn_join_stats",
     "gsim_db_histogram_queries", "gsim_db_histogram",
     "gsim_db_scores", "gsim_db_scores_queries", "gsim_db_scores_device",
     "gsim_db_components", "gsim_components",
@@ -275,6 +284,10 @@ def load():
                                            C.POINTER(GsimGroupStats)]),
         "gsim_db_knn": (C.c_int, [vp, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
         "gsim_graph_get_knn_stats": (C.c_int, [vp, C.POINTER(GsimKnnStats)]),
+        "gsim_db_knn_join": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, C.c_uint32,
+                                       C.POINTER(vp)]),
+        "gsim_db_knn_queries": (C.c_int, [vp, u32p, C.c_uint64, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, C.POINTER(vp)]),
+        "gsim_graph_get_knn_join_stats": (C.c_int, [vp, C.POINTER(GsimKnnJoinStats)]),
         "gsim_db_histogram_queries": (C.c_int, [vp, u32p, C.c_uint64, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.c_float, C.c_float, u64p, u64p,
                                                 C.POINTER(GsimHistStats)]),
         "gsim_db_histogram": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_float), C.c_uint32, C.c_int, C.c_float, C.c_float,
@@ -498,6 +511,31 @@ class Table:
         g = C.c_void_p()
         check(self._L.gsim_db_knn(self._h, k, cutoff, metric, alpha, beta, row_begin, row_end, C.byref(g)))
         return self._take_graph(g, stats, GsimKnnStats, self._L.gsim_graph_get_knn_stats)
+
+    def knn_join(self, left, k, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, row_begin=0, row_end=None, exclude_self=False,
+                 stats=None):
+        """gsim_db_knn_join / gsim_db_knn_queries: for every left row, the k most similar rows j of THIS table with
+        score(query = left row, row j) >= cutoff -- gsim_db_search(left row, k, cutoff) on this table
+        -> CSR (indptr uint64 [nl + 1], indices uint32 (+ this table's row base), scores float32), each list by (score descending,
+        row ascending).
+        `left`: a Table on the same device (its rows [row_begin, row_end)) or a (nq, W) / (W,) uint32 array.
+        `exclude_self` (only with left = this table): the pair (left row i, table row i) is not listed -- knn's lists.
+        `stats`: a dict that receives the call's gsim_knn_join_stats."""
+        g = C.c_void_p()
+        if isinstance(left, Table):
+            if row_end is None:
+                row_end = left.count()
+            check(self._L.gsim_db_knn_join(self._h, left._h, row_begin, row_end, k, cutoff, metric, alpha, beta,
+                                           KNN_EXCLUDE_SELF if exclude_self else 0, C.byref(g)))
+        else:
+            if exclude_self:
+                raise ValueError("exclude_self needs left to be this table")
+            q = np.ascontiguousarray(left, dtype=np.uint32).reshape(-1, self.W)
+            if row_end is None:
+                row_end = q.shape[0]
+            q = np.ascontiguousarray(q[row_begin:row_end])
+            check(self._L.gsim_db_knn_queries(self._h, _u32(q) if len(q) else None, len(q), k, cutoff, metric, alpha, beta, C.byref(g)))
+        return self._take_graph(g, stats, GsimKnnJoinStats, self._L.gsim_graph_get_knn_join_stats)
 
     def _take_graph(self, g, stats, stats_type, get_stats):
         """A gsim_graph -> (indptr, indices, scores) (+ its stats into the dict `stats`); the graph is destroyed."""

@@ -74,6 +74,8 @@ gsim::Knobs read_knobs()
     k.leader_round = std::min(std::max(env_value("GSIM_LEADER_ROUND", k.leader_round), 1), static_cast<int>(gsim::kLeaderMaxRound));
     if (const char* v = std::getenv("GSIM_LEADER_LAUNCH_PAIRS")) k.leader_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
     if (const char* v = std::getenv("GSIM_KNN_LAUNCH_PAIRS")) k.knn_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
+    k.knn_join_segments = std::max(env_value("GSIM_KNN_JOIN_SEGMENTS", k.knn_join_segments), 0); // (0: by the owner tiles and the CUs)
+    if (const char* v = std::getenv("GSIM_KNN_JOIN_LAUNCH_PAIRS")) k.knn_join_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
     k.hist_stream_max_rows = env_value("GSIM_HIST_STREAM_MAX_ROWS", k.hist_stream_max_rows);
     if (const char* v = std::getenv("GSIM_HIST_LAUNCH_PAIRS")) k.hist_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
     k.hist_naive_add = env_value("GSIM_HIST_NAIVE_ADD", k.hist_naive_add) ? 1 : 0;

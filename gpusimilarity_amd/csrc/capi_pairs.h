@@ -12,10 +12,11 @@ struct gsim_graph {
     std::vector<uint32_t> indices;
     std::vector<float> scores;
     gsim_graph_stats stats{};
-    enum class Kind : uint8_t { kNeighbors, kJoin, kKnn }; // who made it: which of the *_get_*_stats accessors answers for it
+    enum class Kind : uint8_t { kNeighbors, kJoin, kKnn, kKnnJoin }; // who made it: which of the *_get_*_stats accessors answers for it
     Kind kind = Kind::kNeighbors;
     gsim_join_stats join{}; // kJoin (gsim_db_join / gsim_db_join_queries)
     gsim_knn_stats knn{};   // kKnn (gsim_db_knn, capi_knn.cpp)
+    gsim_knn_join_stats knn_join{}; // kKnnJoin (gsim_db_knn_join / gsim_db_knn_queries, capi_knn_join.cpp)
 };
 
 namespace gsim_host
@@ -37,6 +38,19 @@ struct KnnLaunch {
     uint64_t c0, c1;    // candidate rows
 };
 std::vector<KnnLaunch> plan_knn(uint64_t nout, uint64_t N, uint32_t WP, long long pairs);
+
+// The column segments and fold launches of gsim_db_knn_join* over nl owner rows x N table rows on num_cus compute units
+// (capi_knn_join.cpp has the rule; `segments`, `pairs`: GSIM_KNN_JOIN_SEGMENTS, GSIM_KNN_JOIN_LAUNCH_PAIRS).  Pure.  With
+// segments == 0 the partial lists, nl x S x k x 8 bytes, stay below 2 x (2 x num_cus) x 256 x k x 8: 256 MiB at k = 128, 256 CUs.
+struct KnnJoinLaunch {
+    uint32_t ot0, not_; // owner tiles
+    uint64_t r0, r1;    // rows of every segment, counted from the segment's first row (gsim::knn_join_seg_begin)
+};
+struct KnnJoinPlan {
+    uint32_t segments = 1;
+    std::vector<KnnJoinLaunch> launches;
+};
+KnnJoinPlan plan_knn_join(uint64_t nl, uint64_t N, uint32_t WP, int num_cus, int segments, long long pairs);
 
 // Where a launch appends: the shard's pair buffer as it is now
 struct PairSink {

@@ -207,6 +207,13 @@ struct Knobs {
     long long knn_launch_pairs = 0;  // GSIM_KNN_LAUNCH_PAIRS    a launch of gsim_db_knn's fold kernel scores at most this many owner x candidate
                                      // pairs (at least one column tile of 256 candidates); 0: by the row width, with the tile
                                      // kernel's pricing and budget (capi_knn.cpp).  The result does not depend on it
+    int knn_join_segments = 0;       // GSIM_KNN_JOIN_SEGMENTS   column segments of a gsim_db_knn_join* call, each folded by workgroups of its
+                                     // own and merged afterwards; 0: 1 when the owner tiles alone give two workgroups per CU, else as
+                                     // many as make up for it; n: n, at most the table's column tiles and kKnnJoinMaxSegments
+                                     // (capi_knn_join.cpp plan_knn_join).  The result does not depend on it
+    long long knn_join_launch_pairs = 0; // GSIM_KNN_JOIN_LAUNCH_PAIRS  a launch of gsim_db_knn_join*'s fold kernel scores at most this many
+                                     // owner x candidate pairs (at least one column tile of 256 candidates per segment); 0: by the row
+                                     // width, as knn_launch_pairs.  The result does not depend on it
     int hist_stream_max_rows = 32;   // GSIM_HIST_STREAM_MAX_ROWS  histogram calls of at most this many left rows stream the table once per left
                                      // row, larger ones take the owner-tile kernel (0: always tiles; DESIGN.md section 16 has the crossover:
                                      // between 32 and 64 left rows at 1 M and at 100 M x 1024-bit rows)
@@ -460,6 +467,46 @@ hipError_t launch_knn_offsets(void* tmp, size_t tmp_bytes, const uint32_t* len, 
 // every held entry to its place: indices (+ row_base) and scores
 hipError_t launch_knn_compact(const KnnEntry* lists, const uint32_t* len, const uint64_t* indptr, uint64_t nown, uint32_t k, uint32_t row_base,
                               uint32_t* indices, float* scores, hipStream_t s);
+
+// ---- exact k-nearest-neighbour joins: the k nearest TABLE rows of another table's rows (gsim_knn_join.hip, gsim_db_knn_join*) ----
+// knn_fold_kernel's scheme with the owners read from a second array and the table's columns cut into nseg segments, each folded
+// by workgroups of its own into a partial list per (owner, segment); a merge kernel then ranks the partial lists' entries.
+constexpr uint32_t kKnnJoinMaxSegments = 65535; // (a launch's second grid dimension)
+// Segment s of nseg over N table rows: whole column tiles [first_tile(s), first_tile(s + 1)), clipped to N.  Segment 0 is never
+// shorter than another.
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline uint64_t knn_join_seg_begin(uint64_t s, uint64_t nseg, uint64_t N)
+{
+    const uint64_t nct = (N + kKnnColTile - 1) / kKnnColTile;
+    const uint64_t r = (s * nct + nseg - 1) / nseg * kKnnColTile;
+    return r < N ? r : N;
+}
+struct KnnJoinArgs {
+    const uint32_t* rows;        // the table: nrows x WP words, 16-byte aligned (itself when W == WP, else a zero-padded copy)
+    const uint32_t* pop;         // popc of every table row
+    uint64_t nrows;
+    const uint32_t* lrows;       // the owners: nl x WP words, 16-byte aligned
+    uint64_t nl;
+    uint64_t self0;              // GSIM_KNN_EXCLUDE_SELF: owner o is table row self0 + o and that pair is left out; ~0: no pair is
+    uint32_t WP;                 // words per row as the kernel reads them (4, 8, ... 128)
+    uint32_t k;                  // 1 ... GSIM_KNN_MAX_K
+    uint32_t nseg;               // 1 ... kKnnJoinMaxSegments, at most the table's column tiles
+    int metric;
+    float alpha, beta, cutoff;
+    KnnEntry* lists;             // nl x nseg x k entries: list (o, s) at (o * nseg + s) * k, in (score descending, row ascending) order
+    uint32_t* len;               // entries held per list (zero before the first launch)
+    unsigned long long* inserts; // list insertions made so far
+    unsigned long long* clk;     // as KnnArgs.clk
+};
+// Owner tiles ot0 .. ot0 + not_ - 1 fold, for every segment, the segment's rows [r0, r1) (counted from the segment's first row)
+// into the partial lists.  The pieces of the same owners must be launched in ascending order of r0 on one stream.
+hipError_t launch_knn_join_fold(const KnnJoinArgs& a, uint32_t ot0, uint32_t not_, uint64_t r0, uint64_t r1, hipStream_t s);
+// The nseg partial lists of every owner -> its first k of all of them in out (nl x k) and their number in out_len (nl); *held
+// grows by the number of entries the partial lists hold
+hipError_t launch_knn_join_merge(const KnnEntry* lists, const uint32_t* len, uint64_t nl, uint32_t nseg, uint32_t k, KnnEntry* out,
+                                 uint32_t* out_len, unsigned long long* held, hipStream_t s);
 
 // ---- exact single-linkage dendrograms: the maximum-similarity spanning forest (gsim_mst.hip, gsim_db_mst) -------------------
 // Boruvka rounds.  The fold kernel is knn_fold_kernel's scheme (kKnnTile owners to a workgroup, kKnnBlock threads) with the list

@@ -24,7 +24,8 @@
 // tiles are independent, nothing waits grid-wide, nothing is merged across workgroups.  A few hundred owners against a very
 // long table therefore have little parallelism (their columns are NOT split over workgroups); the launches stay bounded, but
 // for such a range gsim_db_search with the rows as queries at k + 1 is faster per owner row (512 owners
-// against 1 M x 1024-bit rows take 714 ms here and 31 ms there; with the whole table as owners the fold is the faster one).
+// against 1 M x 1024-bit rows take 714 ms here and 31 ms there; with the whole table as owners the fold is the faster one),
+// and so is gsim_knn_join.hip's fold, which does split them and returns the same lists (GSIM_KNN_EXCLUDE_SELF; section 23).
 //
 // CSR: an exclusive scan of the lengths (rocPRIM) gives indptr, one kernel copies the lists' entries to their places.
 #include "gsim_device.h"

@@ -119,6 +119,16 @@ class FingerprintDB:
         [row_begin, row_end), each row's list by (score descending, row ascending).  No counterpart in the reference."""
         return self._table.knn(int(k), float(cutoff), metric, alpha, beta, row_begin, row_end)
 
+    def knn_join(self, left, k: int, cutoff: float, metric: int = capi.METRIC_TANIMOTO, alpha: float = 1.0, beta: float = 1.0,
+                 row_begin: int = 0, row_end=None, exclude_self: bool = False):
+        """Each left row's k most similar rows of this table at or above `cutoff` (gsim_db_knn_join / gsim_db_knn_queries) -> CSR
+        (indptr, indices, scores), each list by (score descending, row ascending).  `left`: another FingerprintDB on the same GPU
+        (its rows [row_begin, row_end)), or an array of fingerprints.  `exclude_self` (only with left = this object): a row is not
+        its own neighbour -- knn's lists.  No counterpart in the reference."""
+        if isinstance(left, FingerprintDB):
+            left = left._table
+        return self._table.knn_join(left, int(k), float(cutoff), metric, alpha, beta, row_begin, row_end, exclude_self)
+
     def join(self, left, cutoff: float, metric: int = capi.METRIC_TANIMOTO, alpha: float = 1.0, beta: float = 1.0,
              order: int = capi.JOIN_BY_ROW, row_begin: int = 0, row_end=None):
         """Every row of this table at or above `cutoff`, per left row (gsim_db_join / gsim_db_join_queries) -> CSR

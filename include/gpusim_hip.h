@@ -621,7 +621,8 @@ int gsim_db_leader(gsim_db* db, float cutoff, const uint32_t* seeds, uint32_t ns
  * gsim_db_attach_device_rows work; no host copy is needed.  The work is (row_end - row_begin) x N pair scores, cut into launches of a
  * bounded length; owner rows are spread over the device 256 to a workgroup and every workgroup walks all N candidate rows itself, so a
  * range of a few hundred rows against a very long table uses a small part of the device (its columns are not split over workgroups;
- * for such a range gsim_db_search with the rows as queries at k + 1 is the faster route -- DESIGN.md section 15 has the crossover). */
+ * for such a range gsim_db_knn_join with left == db and GSIM_KNN_EXCLUDE_SELF, which splits them and returns the same bytes, or
+ * gsim_db_search with the rows as queries at k + 1, is the faster route -- DESIGN.md sections 15 and 23 have the crossover). */
 #define GSIM_KNN_MAX_K 128u
 typedef struct {
     uint64_t rows;      /* owner rows of the call (row_end - row_begin)                                  */
@@ -638,6 +639,76 @@ typedef struct {
 int gsim_db_knn(gsim_db* db, uint32_t k, float cutoff, int metric, float alpha, float beta,
                 uint64_t row_begin, uint64_t row_end, gsim_graph** out);
 int gsim_graph_get_knn_stats(const gsim_graph* g, gsim_knn_stats* out); /* GSIM_ERR_INVALID for any other graph */
+
+/* ---- exact k-nearest-neighbour joins: each left row's k most similar rows of the table -------------------------------------------- */
+/* gsim_db_knn_join / gsim_db_knn_queries: for each of nl LEFT rows -- the rows [lrow_begin, lrow_end) of a handle `left` resident on
+ * the same device (left == db is allowed), or the nq fingerprints at `queries` (host memory, nq x fp_bits / 32 words) -- its k most
+ * similar rows of the table `db` (chemfp's knearest_tanimoto_search_arena; the nearest purchasable analogues of every virtual compound,
+ * the nearest training-set neighbours of every test compound).  No counterpart in the reference.  The output is bounded by nl x k
+ * whatever the data looks like.  The result is a gsim_graph of its own kind: gsim_graph_shape / _copy / _destroy work on it,
+ * gsim_graph_get_stats reports the call's totals (fold + merge launches, their time in tile_ms, entries in pairs),
+ * gsim_graph_get_knn_join_stats the details; gsim_graph_get_join_stats and gsim_graph_get_knn_stats return GSIM_ERR_INVALID for it.
+ * THE RESULT RULE:
+ *   - list i is indexed by left row - lrow_begin, or by position in `queries`, and is exactly the hits of gsim_db_search(query = left
+ *     row i, k, cutoff, metric, alpha, beta) on `db`: the same rows, the same score bits (a = popc(left row), b = popc(table row)),
+ *     the same order (score descending, row ascending); the boundary tie group keeps its lowest rows; it is shorter than k when fewer
+ *     rows qualify;
+ *   - NaN (0 / 0) is never >= cutoff: an all-zero left row has an empty list, an all-zero table row is in nobody's list;
+ *   - no pair is excluded by default.  left == db is allowed: every non-zero row's list then starts at 1.0 with itself or a
+ *     lower-numbered duplicate.  With GSIM_KNN_EXCLUDE_SELF (only with left == db) the pair (left row i, table row i) is left out, by
+ *     row identity: the result is gsim_db_knn's rule and equals its output on the same range byte for byte;
+ *   - cutoff must be in (0, 1]; the smallest positive float means "every row with a non-zero score";
+ *   - metrics: GSIM_METRIC_TANIMOTO, and GSIM_METRIC_TVERSKY with any finite alpha >= 0, beta >= 0 -- asymmetric included: every pair
+ *     is computed from the left row's side;
+ *   - rows of up to 4096 bits; 1 <= k <= GSIM_KNN_MAX_K;
+ *   - indices = table row + the TABLE handle's row base; the left handle's base plays no part; indptr has nl + 1 entries;
+ *   - the output is byte-identical from run to run and does not depend on how the work is cut into launches or into column segments
+ *     (GSIM_KNN_JOIN_LAUNCH_PAIRS, GSIM_KNN_JOIN_SEGMENTS, read once per handle, the table's).  Ranges of left rows,
+ *     concatenated, give the full call's lists -- ranges are how a large left side is done in pieces.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / left / out (NULL queries with nq > 0), k == 0 or k > GSIM_KNN_MAX_K,
+ * cutoff outside (0, 1] or NaN, unknown metric, Tversky alpha / beta negative or not finite, unknown flag bits, GSIM_KNN_EXCLUDE_SELF
+ * with left != db, lrow_begin > lrow_end or lrow_end past the left handle's count, handles of different fp_bits, rows wider than 4096
+ * bits, nl >= 2^32, a table of 2^32 rows or more.  *out is cleared on every failure.  GSIM_ERR_STATE: either handle multi-shard, folded
+ * or not on a GPU; handles on different devices.  GSIM_ERR_NOMEM: the call's device memory cannot be had; nothing is truncated, nothing
+ * leaked.  nl == 0 gives an empty graph (indptr = {0}) and GSIM_OK.
+ * Execution: on the table handle's stream under the one-call-at-a-time rule (of both handles); the search state of both is left as it
+ * was found (a gsim_db_search before and after returns identical bytes).  Tables from gsim_db_generate and gsim_db_attach_device_rows
+ * work on either side; no host copy is needed.  The work is nl x N pair scores.  Left rows are spread over the device 256 to a
+ * workgroup, and where those workgroups alone are fewer than two per compute unit the table's rows are cut into S contiguous segments
+ * (S = ceil(2 x CUs / owner tiles), at most the table's tiles of 256 rows) that separate workgroups fold into a partial list per
+ * (left row, segment); one more kernel merges an owner's S partial lists into its first k, exactly.  The call allocates nl x S x k x 8
+ * bytes for the partial lists -- under that rule less than 2 x (2 x CUs) x 256 x k x 8 bytes, 256 MiB at k = 128 on 256 CUs -- plus,
+ * for S > 1, nl x k x 8 for the merged lists, a few words per left row, at most nl x k x 8 again for the compacted CSR while it is
+ * copied out, and, as gsim_db_knn, 4 bytes per TABLE row (popcounts) and zero-padded copies of both sides where the rows are not 128,
+ * 256, 512, 1024, 2048 or 4096 bits wide.  All of it is freed by the call.
+ * Against gsim_db_search with the left rows as queries, 256 per call (the same lists), measured on 1 M x 1024-bit rows (DESIGN.md
+ * section 23): at the smallest cutoff the join is 6 to 10 times faster at k = 8, 3 to 8 times at k = 32, and at k = 128 from 0.9 times
+ * as fast (512 left rows: every segment fills a list of its own) to 4 to 5 times faster (4096); at a cutoff that few rows reach (0.5
+ * there) gsim_db_search, which filters on the cutoff before it scores, is 2.4 to 2.9 times FASTER than the join, whose time is then
+ * the bare fold of nl x N pairs. */
+#define GSIM_KNN_EXCLUDE_SELF 1u   /* only with left == db: the pair (left row i, table row i) is not listed */
+typedef struct {
+    uint64_t left_rows;       /* left rows of the call (nl)                                                     */
+    uint64_t table_rows;      /* table rows (N)                                                                 */
+    uint64_t segments;        /* column segments the table was cut into (S)                                     */
+    uint64_t fold_launches;   /* launches of the fold kernel                                                    */
+    uint64_t merge_launches;  /* launches of the merge kernel (0 when S == 1)                                   */
+    uint64_t pairs;           /* left x table pairs scored (nl x N)                                             */
+    uint64_t inserts;         /* list insertions made (the fold kernel's slow path)                             */
+    uint64_t partial_entries; /* entries held by the partial lists, before the merge                            */
+    uint64_t entries;         /* entries listed (nnz), after the merge                                          */
+    double kernel_ms;         /* HIP events on the table handle's stream around all fold launches               */
+    double merge_ms;          /* ... around the merge                                                           */
+    double csr_ms;            /* offsets + compaction on the device                                             */
+    double d2h_ms;            /* CSR into host memory                                                           */
+    double wall_ms;           /* the whole call, host clock                                                     */
+    double clock_mhz;         /* shader clock the fold kernel ran at (as gsim_graph_stats.clock_mhz)            */
+} gsim_knn_join_stats;
+int gsim_db_knn_join(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, uint32_t k, float cutoff,
+                     int metric, float alpha, float beta, uint32_t flags, gsim_graph** out);
+int gsim_db_knn_queries(gsim_db* db, const uint32_t* queries, uint64_t nq, uint32_t k, float cutoff,
+                        int metric, float alpha, float beta, gsim_graph** out);
+int gsim_graph_get_knn_join_stats(const gsim_graph* g, gsim_knn_join_stats* out); /* GSIM_ERR_INVALID for any other graph */
 
 /* ---- similarity histograms and hit counts: how many table rows score in each bin, per left row ------------------------------------ */
 /* gsim_db_histogram_queries / gsim_db_histogram: for each of nl LEFT rows -- the nq fingerprints at `queries` (host memory, nq x
