@@ -1,0 +1,71 @@
+// capi_front.cpp -- the shared fronts of capi_front.h.
+#include "capi_front.h"
+
+namespace gsim_host
+{
+
+int check_metric(const char* prefix, int metric, float alpha, float beta)
+{
+    if (metric != GSIM_METRIC_TANIMOTO && metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
+    if (metric == GSIM_METRIC_TVERSKY && !(std::isfinite(alpha) && alpha >= 0.0f && std::isfinite(beta) && beta >= 0.0f))
+        return fail(GSIM_ERR_INVALID, std::string(prefix) + ": Tversky alpha and beta must be finite and >= 0");
+    return GSIM_OK;
+}
+
+int check_pair_state(const gsim_db* db, const char* plural, const char* which)
+{
+    if (!db->finalized) return fail(GSIM_ERR_STATE, std::string(which) + " not finalized (no rows on a GPU)");
+    if (db->fold > 1) return fail(GSIM_ERR_STATE, std::string(plural) + " do not support folded tables: " + which);
+    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, std::string(plural) + " need single-shard handles: " + which);
+    return GSIM_OK;
+}
+
+int check_left_handle(const gsim_db* db, const gsim_db* left, uint64_t lrow_end)
+{
+    if (!left) return fail(GSIM_ERR_INVALID, "NULL left handle");
+    if (lrow_end > left->nrows) return fail(GSIM_ERR_INVALID, "left row range outside the left table");
+    if (left->fp_bits != db->fp_bits) return fail(GSIM_ERR_INVALID, "the two handles have different fp_bits");
+    return GSIM_OK;
+}
+
+int LeftSide::from_handle(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, const char* plural)
+{
+    int rc = check_pair_state(db, plural, "table");
+    if (rc == GSIM_OK && left != db) rc = check_pair_state(left, plural, "left table");
+    if (rc != GSIM_OK) return rc;
+    if (left->shards[0].device != db->shards[0].device) return fail(GSIM_ERR_STATE, "the two handles are on different devices");
+    // One call at a time on either handle.  std::lock takes the two mutexes without an order of its own: f(A, left = B) beside
+    // f(B, left = A) on two threads cannot deadlock, as they would if each took `db` first.
+    lock_db = std::unique_lock<std::mutex>(db->search_mutex, std::defer_lock);
+    if (left != db) {
+        lock_left = std::unique_lock<std::mutex>(left->search_mutex, std::defer_lock);
+        std::lock(lock_db, lock_left);
+    } else {
+        lock_db.lock();
+    }
+    rows = static_cast<const uint32_t*>(left->shards[0].d_rows) + lrow_begin * left->shards[0].W;
+    nl = lrow_end - lrow_begin;
+    in_table = left == db;
+    row0 = lrow_begin;
+    return GSIM_OK;
+}
+
+int LeftSide::from_queries(gsim_db* db, const uint32_t* queries, uint64_t nq, const char* plural, const char* what, bool upload)
+{
+    if (nq && !queries) return fail(GSIM_ERR_INVALID, "NULL queries");
+    const int rc = check_pair_state(db, plural, "table");
+    if (rc != GSIM_OK) return rc;
+    lock_db = std::unique_lock<std::mutex>(db->search_mutex);
+    Shard& s = db->shards[0];
+    if (nq && upload) {
+        GSIM_HIP(set_device(s.device));
+        const size_t bytes = static_cast<size_t>(nq) * s.W * 4;
+        if (d_left.grow(bytes) != hipSuccess) return fail(GSIM_ERR_NOMEM, std::string("device memory for ") + what);
+        GSIM_HIP(hipMemcpyAsync(d_left, queries, bytes, hipMemcpyHostToDevice, s.stream));
+    }
+    rows = d_left.as<uint32_t>();
+    nl = nq;
+    return GSIM_OK;
+}
+
+} // namespace gsim_host

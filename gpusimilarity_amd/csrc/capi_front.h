@@ -1,0 +1,58 @@
+// capi_front.h -- what a call does before and after its launches, where several entry points had each carried a copy: the metric
+// check, the state check and the left side of the two-table families (threshold joins, k-NN joins, histograms, score matrices:
+// capi_join / capi_knn_join / capi_hist / capi_scores.cpp), and the wrapper of the graph-returning calls.  Each family keeps its own
+// argument checks.  Implemented in capi_front.cpp; DESIGN.md section 24.  Internal.
+#pragma once
+
+#include "capi_pairs.h"
+
+namespace gsim_host
+{
+
+// INVALID "unknown metric", then "<prefix>: Tversky alpha and beta must be finite and >= 0"
+int check_metric(const char* prefix, int metric, float alpha, float beta);
+
+// The STATE errors of a two-table family (`plural`: "joins", "knn joins", "histograms", "score matrices") about one side (`which`:
+// "table", "left table"), in one order: not finalized, folded, more than one shard.
+int check_pair_state(const gsim_db* db, const char* plural, const char* which);
+
+// The INVALID errors of a left handle, in this order: NULL, a range past its rows, fp_bits other than the table's.
+int check_left_handle(const gsim_db* db, const gsim_db* left, uint64_t lrow_end);
+
+// The left rows of a two-table call: a front fills it, the family's core reads it.  It owns the uploaded copy and the lock or
+// locks (one call at a time on either handle), so it lives as long as the call.
+struct LeftSide {
+    const uint32_t* rows = nullptr; // nl rows of the table's W words, on the table's device
+    uint64_t nl = 0;
+    bool in_table = false;          // they are the table's own rows row0 ...: a core that pads the table need not pad them again
+    uint64_t row0 = 0;
+
+    // The rows [lrow_begin, lrow_end) of `left`, which check_left_handle has passed.  STATE: the table's state, the left
+    // table's where it is another handle, "different devices"; then the locks.
+    int from_handle(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, const char* plural);
+    // nq host rows, copied on the shard's stream into device memory of the name `what` ("the join's left rows"; not at all with
+    // `upload` false, for a core that will not read them).  INVALID "NULL queries" when nq > 0, the table's state, the lock.
+    int from_queries(gsim_db* db, const uint32_t* queries, uint64_t nq, const char* plural, const char* what, bool upload = true);
+
+private:
+    std::unique_lock<std::mutex> lock_db, lock_left;
+    DevBuf<> d_left; // (freed before the locks go)
+};
+
+// A graph-returning call: fn(g) fills a new graph, which becomes *out when it returns GSIM_OK.  NOMEM `nomem_what` when it
+// runs out of host memory.
+template <class Fn> int make_graph(gsim_graph** out, const char* nomem_what, Fn&& fn)
+{
+    std::unique_ptr<gsim_graph> g(new (std::nothrow) gsim_graph);
+    if (!g) return fail(GSIM_ERR_NOMEM, "graph");
+    int rc;
+    try {
+        rc = fn(g.get());
+    } catch (const std::bad_alloc&) {
+        rc = fail(GSIM_ERR_NOMEM, nomem_what);
+    }
+    if (rc == GSIM_OK) *out = g.release();
+    return rc;
+}
+
+} // namespace gsim_host

@@ -1,11 +1,10 @@
-// capi_hist.cpp -- gsim_db_histogram / gsim_db_histogram_queries: per left row, how many table rows score in each bin.  Two thin
-// fronts of one core that takes "left rows in device memory, nl of them", as the joins; the argument checks, the launch plans of
-// both routes and the copies of a call.  The device side is gsim_hist.hip.  The rule is stated in include/gpusim_hip.h.
-#include "capi_pairs.h"
+// capi_hist.cpp -- gsim_db_histogram / gsim_db_histogram_queries: per left row, how many table rows score in each bin.  The
+// family's argument checks, the launch plans of both routes and one core that takes a front's LeftSide (capi_front.h), as the
+// joins, with the copies of a call.  The device side is gsim_hist.hip.  The rule is stated in include/gpusim_hip.h.
+#include "capi_front.h"
 #include "gsim_prefilter.h"
 
 #include <chrono>
-#include <cmath>
 
 namespace gsim_host
 {
@@ -80,12 +79,12 @@ struct HistCall {
     gsim_hist_stats* stats;
 };
 
-// left rows d_left[0 .. nl) (W words each, on s's device; `left_in_table`: they are the table's own rows self0 ...) against s's table
-int histogram(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, bool left_in_table, uint64_t left_row0, const HistCall& c)
+// the left rows (W words each, on s's device) against s's table
+int histogram(gsim_db* db, Shard& s, const LeftSide& ls, const HistCall& c)
 {
     const auto t0 = std::chrono::steady_clock::now();
     auto wall = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-    const uint64_t N = s.nrows;
+    const uint64_t N = s.nrows, nl = ls.nl;
     const uint32_t nb = c.nedges + 1;
     gsim_hist_stats hs{};
     hs.left_rows = nl;
@@ -133,7 +132,7 @@ int histogram(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, bool l
             h.metric = c.metric;
             h.alpha = c.alpha;
             h.beta = c.beta;
-            h.left = d_left;
+            h.left = ls.rows;
             h.self0 = c.self0;
             h.bins = bins;
             h.hist = d_hist;
@@ -150,13 +149,13 @@ int histogram(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, bool l
             if (const int rc = table.alloc(N, s.W, WP, "the histogram (popcounts)", "the histogram (padded rows)")) return rc;
             if (const int rc = table.prepare(s.d_rows, N, st)) return rc;
             // (the kernel counts the left rows' bits itself: only their padded copy is wanted, where the table's does not hold them)
-            const uint32_t* lrows = d_left;
+            const uint32_t* lrows = ls.rows;
             if (WP != s.W) {
-                if (left_in_table) {
-                    lrows = table.rows() + left_row0 * WP;
+                if (ls.in_table) {
+                    lrows = table.rows() + ls.row0 * WP;
                 } else {
                     if (const int rc = left.alloc(nl, s.W, WP, "the histogram (popcounts of the left rows)", "the histogram (padded left rows)")) return rc;
-                    if (const int rc = left.prepare(d_left, nl, st)) return rc;
+                    if (const int rc = left.prepare(ls.rows, nl, st)) return rc;
                     lrows = left.rows();
                 }
             }
@@ -214,9 +213,7 @@ int histogram(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, bool l
 int check_hist_args(gsim_db* db, uint64_t nl, const HistCall& c, uint32_t flags)
 {
     if (!db) return fail(GSIM_ERR_INVALID, "NULL argument");
-    if (c.metric != GSIM_METRIC_TANIMOTO && c.metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
-    if (c.metric == GSIM_METRIC_TVERSKY && !(std::isfinite(c.alpha) && c.alpha >= 0.0f && std::isfinite(c.beta) && c.beta >= 0.0f))
-        return fail(GSIM_ERR_INVALID, "histogram: Tversky alpha and beta must be finite and >= 0");
+    if (const int rc = check_metric("histogram", c.metric, c.alpha, c.beta)) return rc;
     if (!c.edges) return fail(GSIM_ERR_INVALID, "histogram: NULL edges");
     if (c.nedges < 1 || c.nedges > GSIM_HIST_MAX_EDGES) return fail(GSIM_ERR_INVALID, "histogram: nedges must be in [1, GSIM_HIST_MAX_EDGES = 128]");
     for (uint32_t i = 0; i < c.nedges; i++) {
@@ -232,18 +229,10 @@ int check_hist_args(gsim_db* db, uint64_t nl, const HistCall& c, uint32_t flags)
     return GSIM_OK;
 }
 
-int check_hist_state(const gsim_db* db, const char* which)
-{
-    if (!db->finalized) return fail(GSIM_ERR_STATE, std::string(which) + " not finalized (no rows on a GPU)");
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, std::string("histograms do not support folded tables: ") + which);
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, std::string("histograms need single-shard handles: ") + which);
-    return GSIM_OK;
-}
-
-int run_histogram(gsim_db* db, const uint32_t* d_left, uint64_t nl, bool left_in_table, uint64_t left_row0, const HistCall& c)
+int run_histogram(gsim_db* db, const LeftSide& left, const HistCall& c)
 {
     try {
-        return histogram(db, db->shards[0], d_left, nl, left_in_table, left_row0, c);
+        return histogram(db, db->shards[0], left, c);
     } catch (const std::bad_alloc&) {
         return fail(GSIM_ERR_NOMEM, "host memory for the histogram");
     }
@@ -262,19 +251,10 @@ int gsim_db_histogram_queries(gsim_db* db, const uint32_t* queries, uint64_t nq,
     const HistCall c{edges, nedges, metric, alpha, beta, ~0ull, hist, total, stats};
     int rc = check_hist_args(db, nq, c, 0);
     if (rc != GSIM_OK) return rc;
-    if (nq && !queries) return fail(GSIM_ERR_INVALID, "NULL queries");
-    rc = check_hist_state(db, "table");
+    LeftSide left;
+    rc = left.from_queries(db, queries, nq, "histograms", "the histogram's left rows");
     if (rc != GSIM_OK) return rc;
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    Shard& s = db->shards[0];
-    DevBuf<> d_left;
-    if (nq) {
-        GSIM_HIP(set_device(s.device));
-        const size_t bytes = static_cast<size_t>(nq) * s.W * 4;
-        GSIM_ALLOC(d_left, bytes, "the histogram's left rows");
-        GSIM_HIP(hipMemcpyAsync(d_left, queries, bytes, hipMemcpyHostToDevice, s.stream));
-    }
-    return run_histogram(db, d_left.as<uint32_t>(), nq, false, 0, c);
+    return run_histogram(db, left, c);
 }
 
 int gsim_db_histogram(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, const float* edges, uint32_t nedges, int metric,
@@ -285,20 +265,13 @@ int gsim_db_histogram(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t 
     const HistCall c{edges, nedges, metric, alpha, beta, exclude ? lrow_begin : ~0ull, hist, total, stats};
     int rc = check_hist_args(db, lrow_end - lrow_begin, c, flags);
     if (rc != GSIM_OK) return rc;
-    if (!left) return fail(GSIM_ERR_INVALID, "NULL left handle");
-    if (exclude && left != db) return fail(GSIM_ERR_INVALID, "histogram: GSIM_HIST_EXCLUDE_SELF needs left == db");
-    if (lrow_end > left->nrows) return fail(GSIM_ERR_INVALID, "left row range outside the left table");
-    if (left->fp_bits != db->fp_bits) return fail(GSIM_ERR_INVALID, "the two handles have different fp_bits");
-    rc = check_hist_state(db, "table");
-    if (rc == GSIM_OK && left != db) rc = check_hist_state(left, "left table");
+    if (exclude && left && left != db) return fail(GSIM_ERR_INVALID, "histogram: GSIM_HIST_EXCLUDE_SELF needs left == db");
+    rc = check_left_handle(db, left, lrow_end);
     if (rc != GSIM_OK) return rc;
-    if (left->shards[0].device != db->shards[0].device) return fail(GSIM_ERR_STATE, "the two handles are on different devices");
-    // one call at a time on either handle
-    std::unique_lock<std::mutex> g1(db->search_mutex, std::defer_lock), g2(left->search_mutex, std::defer_lock);
-    if (left != db) std::lock(g1, g2);
-    else g1.lock();
-    const uint32_t* d_left = static_cast<const uint32_t*>(left->shards[0].d_rows) + lrow_begin * left->shards[0].W;
-    return run_histogram(db, d_left, lrow_end - lrow_begin, left == db, lrow_begin, c);
+    LeftSide ls;
+    rc = ls.from_handle(db, left, lrow_begin, lrow_end, "histograms");
+    if (rc != GSIM_OK) return rc;
+    return run_histogram(db, ls, c);
 }
 
 } // extern "C"

@@ -1,10 +1,10 @@
-// capi_join.cpp -- gsim_db_join / gsim_db_join_queries: every table row at or above a cutoff, per left row.  Two thin fronts of
-// one core that takes "left rows in device memory, nl of them"; the device side is gsim_join.hip (streaming route) and the
-// join instantiations of gsim_neighbors.hip's tile kernel.  The rule is stated in include/gpusim_hip.h.
-#include "capi_pairs.h"
+// capi_join.cpp -- gsim_db_join / gsim_db_join_queries: every table row at or above a cutoff, per left row.  The family's
+// argument checks and one core that takes "left rows in device memory, nl of them" from either front's LeftSide (capi_front.h);
+// the device side is gsim_join.hip (streaming route) and the join instantiations of gsim_neighbors.hip's tile kernel.  The rule
+// is stated in include/gpusim_hip.h.
+#include "capi_front.h"
 
 #include <chrono>
-#include <cmath>
 
 namespace gsim_host
 {
@@ -146,46 +146,24 @@ int join(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, float cutof
     return GSIM_OK;
 }
 
-// what both entry points check before any device state
+// what both entry points check before any device state (a NULL db leaves *out as it was: DESIGN.md section 24)
 int check_join_args(gsim_db* db, gsim_graph** out, uint64_t nl, float cutoff, int metric, float alpha, float beta, int order)
 {
     if (!db || !out) return fail(GSIM_ERR_INVALID, "NULL argument");
     *out = nullptr;
-    if (metric != GSIM_METRIC_TANIMOTO && metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
+    if (const int rc = check_metric("join", metric, alpha, beta)) return rc;
     if (order != GSIM_JOIN_BY_ROW && order != GSIM_JOIN_BY_SCORE) return fail(GSIM_ERR_INVALID, "unknown join order");
     if (!(cutoff > 0.0f && cutoff <= 1.0f)) return fail(GSIM_ERR_INVALID, "join cutoff must be in (0, 1]");
-    if (metric == GSIM_METRIC_TVERSKY && !(std::isfinite(alpha) && alpha >= 0.0f && std::isfinite(beta) && beta >= 0.0f))
-        return fail(GSIM_ERR_INVALID, "join: Tversky alpha and beta must be finite and >= 0");
     if (nl > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "join: 2^32 left rows or more");
     if (db->nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "join: tables of 2^32 rows or more");
     if (gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, "joins support rows of up to 4096 bits");
     return GSIM_OK;
 }
 
-int check_join_state(const gsim_db* db, const char* which)
+int run_join(gsim_db* db, const LeftSide& left, float cutoff, int metric, float alpha, float beta, int order, gsim_graph** out)
 {
-    if (!db->finalized) return fail(GSIM_ERR_STATE, std::string(which) + " not finalized (no rows on a GPU)");
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, std::string("joins do not support folded tables: ") + which);
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, std::string("joins need single-shard handles: ") + which);
-    return GSIM_OK;
-}
-
-int run_join(gsim_db* db, const uint32_t* d_left, uint64_t nl, float cutoff, int metric, float alpha, float beta, int order, gsim_graph** out)
-{
-    gsim_graph* g = new (std::nothrow) gsim_graph;
-    if (!g) return fail(GSIM_ERR_NOMEM, "graph");
-    int rc;
-    try {
-        rc = join(db, db->shards[0], d_left, nl, cutoff, metric, alpha, beta, order, g);
-    } catch (const std::bad_alloc&) {
-        rc = fail(GSIM_ERR_NOMEM, "host memory for the join's lists");
-    }
-    if (rc != GSIM_OK) {
-        delete g;
-        return rc;
-    }
-    *out = g;
-    return GSIM_OK;
+    return make_graph(out, "host memory for the join's lists",
+                      [&](gsim_graph* g) { return join(db, db->shards[0], left.rows, left.nl, cutoff, metric, alpha, beta, order, g); });
 }
 
 } // namespace
@@ -200,19 +178,10 @@ int gsim_db_join_queries(gsim_db* db, const uint32_t* queries, uint64_t nq, floa
 {
     int rc = check_join_args(db, out, nq, cutoff, metric, alpha, beta, order);
     if (rc != GSIM_OK) return rc;
-    if (nq && !queries) return fail(GSIM_ERR_INVALID, "NULL queries");
-    rc = check_join_state(db, "table");
+    LeftSide left;
+    rc = left.from_queries(db, queries, nq, "joins", "the join's left rows");
     if (rc != GSIM_OK) return rc;
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    Shard& s = db->shards[0];
-    DevBuf<> d_left;
-    if (nq) {
-        GSIM_HIP(set_device(s.device));
-        const size_t bytes = static_cast<size_t>(nq) * s.W * 4;
-        GSIM_ALLOC(d_left, bytes, "the join's left rows");
-        GSIM_HIP(hipMemcpyAsync(d_left, queries, bytes, hipMemcpyHostToDevice, s.stream));
-    }
-    return run_join(db, d_left.as<uint32_t>(), nq, cutoff, metric, alpha, beta, order, out);
+    return run_join(db, left, cutoff, metric, alpha, beta, order, out);
 }
 
 int gsim_db_join(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, float cutoff, int metric, float alpha, float beta,
@@ -223,20 +192,12 @@ int gsim_db_join(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_
         return fail(GSIM_ERR_INVALID, "left row range: begin past end");
     }
     int rc = check_join_args(db, out, lrow_end - lrow_begin, cutoff, metric, alpha, beta, order);
+    if (rc == GSIM_OK) rc = check_left_handle(db, left, lrow_end);
     if (rc != GSIM_OK) return rc;
-    if (!left) return fail(GSIM_ERR_INVALID, "NULL left handle");
-    if (lrow_end > left->nrows) return fail(GSIM_ERR_INVALID, "left row range outside the left table");
-    if (left->fp_bits != db->fp_bits) return fail(GSIM_ERR_INVALID, "the two handles have different fp_bits");
-    rc = check_join_state(db, "table");
-    if (rc == GSIM_OK && left != db) rc = check_join_state(left, "left table");
+    LeftSide ls;
+    rc = ls.from_handle(db, left, lrow_begin, lrow_end, "joins");
     if (rc != GSIM_OK) return rc;
-    if (left->shards[0].device != db->shards[0].device) return fail(GSIM_ERR_STATE, "the two handles are on different devices");
-    // one call at a time on either handle
-    std::unique_lock<std::mutex> g1(db->search_mutex, std::defer_lock), g2(left->search_mutex, std::defer_lock);
-    if (left != db) std::lock(g1, g2);
-    else g1.lock();
-    const uint32_t* d_left = static_cast<const uint32_t*>(left->shards[0].d_rows) + lrow_begin * left->shards[0].W;
-    return run_join(db, d_left, lrow_end - lrow_begin, cutoff, metric, alpha, beta, order, out);
+    return run_join(db, ls, cutoff, metric, alpha, beta, order, out);
 }
 
 } // extern "C"

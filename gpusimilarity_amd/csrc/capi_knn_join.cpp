@@ -1,11 +1,11 @@
 // capi_knn_join.cpp -- gsim_db_knn_join / gsim_db_knn_queries: for every left row its k most similar rows of the table, exactly,
-// as CSR.  Two thin fronts of one core that takes "left rows in device memory, nl of them", as the threshold joins; the argument
-// checks, the plan (column segments and launches) and the CSR build of a call.  The device side is gsim_knn_join.hip (the
-// two-table, segmented fold and the merge) and gsim_knn.hip's offsets and compaction.  The rule is stated in include/gpusim_hip.h.
-#include "capi_pairs.h"
+// as CSR.  The family's argument checks, the plan (column segments and launches, gsim_db_knn's too) and one core that takes a
+// front's LeftSide (capi_front.h), as the threshold joins; the lists become CSR in capi_pairs.cpp (build_knn_csr).  The device side
+// is gsim_knn_join.hip (the two-table, segmented fold and the merge) and gsim_knn.hip's offsets and compaction.  The rule is stated
+// in include/gpusim_hip.h.
+#include "capi_front.h"
 
 #include <chrono>
-#include <cmath>
 
 namespace gsim_host
 {
@@ -17,12 +17,14 @@ namespace gsim_host
 // instead.  Either way S is at most the table's column tiles and kKnnJoinMaxSegments, and 1 for 2^31 owners or more (the merge's
 // grid).  Under the automatic rule the partial lists hold nl x S x k entries <= (2 x CUs + owner tiles) x 256 x k, i.e. less than
 // 2 x (2 x CUs) x 256 x k x 8 bytes: 256 MiB at k = 128 on 256 CUs.
-// Launches: plan_knn's, with a workgroup per (owner tile, segment) where plan_knn has one per owner tile -- as many owner
-// tiles as the tile budget admits at one column tile per segment each, as many columns PER SEGMENT as then still fit, never more
-// than the budget gives one lane when it is spread over the device's 65 536 lanes; `pairs` > 0 (GSIM_KNN_JOIN_LAUNCH_PAIRS)
-// replaces both bounds: at most that many owner x candidate pairs over all segments, at least one column tile per segment.  A
-// launch covers the rows [r0, r1) of every segment, counted from the segment's first row; the pieces of a group of owner tiles
-// follow each other in ascending order.  With S == 1 this is plan_knn.
+// Launches: the fold kernels' unit of parallelism is the (owner tile, segment) alone (a workgroup walks every candidate of its
+// launch), so a launch takes as many owner tiles as the tile kernel's budget admits at one column tile per segment each
+// (launch_tile_budget: the same pricing, the same 2.5e11 units) and as many columns PER SEGMENT as then still fit -- and never more
+// columns than the budget gives ONE lane when it is spread over the device's 65 536 lanes, which bounds the launch of a small
+// owner range, whose few waves walk alone.  `pairs` > 0 (GSIM_KNN_JOIN_LAUNCH_PAIRS, GSIM_KNN_LAUNCH_PAIRS) replaces both
+// bounds: at most that many owner x candidate pairs over all segments, at least one column tile per segment.  A launch covers
+// the rows [r0, r1) of every segment, counted from the segment's first row; the pieces of a group of owner tiles follow each
+// other in ascending order.
 KnnJoinPlan plan_knn_join(uint64_t nl, uint64_t N, uint32_t WP, int num_cus, int segments, long long pairs)
 {
     const uint64_t tile = gsim::kKnnTile, ctile = gsim::kKnnColTile;
@@ -52,6 +54,14 @@ KnnJoinPlan plan_knn_join(uint64_t nl, uint64_t N, uint32_t WP, int num_cus, int
     return out;
 }
 
+// gsim_db_knn and gsim_db_mst: one segment, the whole table (the device's size then plays no part)
+std::vector<KnnLaunch> plan_knn(uint64_t nout, uint64_t N, uint32_t WP, long long pairs)
+{
+    std::vector<KnnLaunch> out;
+    for (const KnnJoinLaunch& l : plan_knn_join(nout, N, WP, 1, 1, pairs).launches) out.push_back({l.ot0, l.not_, l.r0, l.r1});
+    return out;
+}
+
 namespace
 {
 
@@ -63,12 +73,11 @@ struct KnnJoinCall {
     uint64_t self0; // GSIM_KNN_EXCLUDE_SELF: left row o is table row self0 + o; ~0: no pair is excluded
 };
 
-// left rows d_left[0 .. nl) (W words each, on s's device; `left_in_table`: they are the table's own rows left_row0 ...) against s's table
-int knn_join(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, bool left_in_table, uint64_t left_row0, const KnnJoinCall& c,
-             gsim_graph* g)
+// the left rows (W words each, on s's device) against s's table
+int knn_join(gsim_db* db, Shard& s, const LeftSide& ls, const KnnJoinCall& c, gsim_graph* g)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t N = s.nrows;
+    const uint64_t N = s.nrows, nl = ls.nl;
     const uint32_t k = c.k;
     const uint32_t WP = gsim::nbr_padded_words(s.W);
     g->kind = gsim_graph::Kind::kKnnJoin;
@@ -93,8 +102,7 @@ int knn_join(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, bool le
     PaddedRows table, left;
     DevBuf<> ctl, tmp;
     DevBuf<gsim::KnnEntry> parts, merged;
-    DevBuf<uint32_t> part_len, merged_len, d_indices;
-    DevBuf<float> d_scores;
+    DevBuf<uint32_t> part_len, merged_len;
     DevBuf<uint64_t> d_indptr;
     size_t tmp_bytes = 0;
     GSIM_HIP(gsim::knn_scan_bytes(nl + 1, &tmp_bytes));
@@ -116,13 +124,13 @@ int knn_join(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, bool le
     GSIM_HIP(hipMemsetAsync(ctl, 0, (2 + 4 * nlaunch) * 8, st));
     if (const int rc = table.prepare(s.d_rows, N, st)) return rc;
     // (the kernel counts the left rows' bits itself: only their padded copy is wanted, where the table's does not hold them)
-    const uint32_t* lrows = d_left;
+    const uint32_t* lrows = ls.rows;
     if (WP != s.W) {
-        if (left_in_table) {
-            lrows = table.rows() + left_row0 * WP;
+        if (ls.in_table) {
+            lrows = table.rows() + ls.row0 * WP;
         } else {
             if (const int rc = left.alloc(nl, s.W, WP, "the k-nearest-neighbour join (popcounts of the left rows)", "the k-nearest-neighbour join (padded left rows)")) return rc;
-            if (const int rc = left.prepare(d_left, nl, st)) return rc;
+            if (const int rc = left.prepare(ls.rows, nl, st)) return rc;
             lrows = left.rows();
         }
     }
@@ -145,11 +153,9 @@ int knn_join(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, bool le
     a.len = part_len;
     a.inserts = d_ctl;
 
-    EventPair ev_fold, ev_merge, ev_csr, ev_d2h;
+    EventPair ev_fold, ev_merge;
     GSIM_HIP(ev_fold.create());
     GSIM_HIP(ev_merge.create());
-    GSIM_HIP(ev_csr.create());
-    GSIM_HIP(ev_d2h.create());
     GSIM_HIP(hipEventRecord(ev_fold.a, st));
     for (size_t l = 0; l < nlaunch; l++) {
         const KnnJoinLaunch& p = plan.launches[l];
@@ -161,54 +167,26 @@ int knn_join(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, bool le
     GSIM_HIP(hipEventRecord(ev_merge.a, st));
     if (S > 1) GSIM_HIP(gsim::launch_knn_join_merge(parts, part_len, nl, a.nseg, k, merged, merged_len, d_ctl + 1, st));
     GSIM_HIP(hipEventRecord(ev_merge.b, st));
-    const gsim::KnnEntry* lists = S > 1 ? merged : parts;
-    const uint32_t* len = S > 1 ? merged_len : part_len;
+    KnnCsr csr;
+    if (const int rc = build_knn_csr(db, s, S > 1 ? merged : parts, S > 1 ? merged_len : part_len, nl, k, tmp, d_indptr, ctl,
+                                     "the k-nearest-neighbour join's CSR", "knn join", g, &csr))
+        return rc;
 
-    // indptr on the device; its last entry sizes the compacted arrays
-    GSIM_HIP(hipEventRecord(ev_csr.a, st));
-    GSIM_HIP(gsim::launch_knn_offsets(tmp, tmp_bytes, len, nl + 1, d_indptr, st));
-    std::vector<unsigned long long> h_ctl(2 + 4 * nlaunch);
-    GSIM_HIP(hipMemcpyAsync(g->indptr.data(), d_indptr, (nl + 1) * 8, hipMemcpyDeviceToHost, st));
-    GSIM_HIP(hipMemcpyAsync(h_ctl.data(), ctl, h_ctl.size() * 8, hipMemcpyDeviceToHost, st));
-    GSIM_HIP(hipStreamSynchronize(st));
-    const uint64_t total = g->indptr[nl];
-    if (total > nl * k) return fail(GSIM_ERR_STATE, "knn join: the device reported impossible list lengths");
-    GSIM_ALLOC(d_indices, total * 4, "the k-nearest-neighbour join's CSR");
-    GSIM_ALLOC(d_scores, total * 4, "the k-nearest-neighbour join's CSR");
-    GSIM_HIP(gsim::launch_knn_compact(lists, len, d_indptr, nl, k, db->row_base, d_indices, d_scores, st));
-    GSIM_HIP(hipEventRecord(ev_csr.b, st));
-    g->indices.resize(total);
-    g->scores.resize(total);
-    GSIM_HIP(hipEventRecord(ev_d2h.a, st));
-    if (total) {
-        GSIM_HIP(hipMemcpyAsync(g->indices.data(), d_indices, total * 4, hipMemcpyDeviceToHost, st));
-        GSIM_HIP(hipMemcpyAsync(g->scores.data(), d_scores, total * 4, hipMemcpyDeviceToHost, st));
-    }
-    GSIM_HIP(hipEventRecord(ev_d2h.b, st));
-    GSIM_HIP(hipStreamSynchronize(st));
-
-    clocks.add(h_ctl.data() + 2, nlaunch); // (read with the counters, in one copy)
+    clocks.add(csr.ctl.data() + 2, nlaunch); // (read with the counters, in one copy)
     ks.segments = S;
     ks.fold_launches = nlaunch;
     ks.merge_launches = S > 1 ? 1 : 0;
     ks.pairs = nl * N;
-    ks.inserts = h_ctl[0];
-    ks.partial_entries = S > 1 ? h_ctl[1] : total;
-    ks.entries = total;
+    ks.inserts = csr.ctl[0];
+    ks.partial_entries = S > 1 ? csr.ctl[1] : csr.total;
+    ks.entries = csr.total;
     ks.kernel_ms = ev_fold.ms();
     ks.merge_ms = S > 1 ? ev_merge.ms() : 0.0;
-    // (the events of the CSR build span the host's look at the total: offsets, one small read, compaction)
-    ks.csr_ms = ev_csr.ms();
-    ks.d2h_ms = ev_d2h.ms();
+    ks.csr_ms = csr.csr_ms;
+    ks.d2h_ms = csr.d2h_ms;
     ks.clock_mhz = clocks.mhz();
     ks.wall_ms = wall();
-    g->stats.launches = ks.fold_launches + ks.merge_launches;
-    g->stats.pairs = total;
-    g->stats.tile_ms = ks.kernel_ms + ks.merge_ms;
-    g->stats.csr_ms = ks.csr_ms;
-    g->stats.d2h_ms = ks.d2h_ms;
-    g->stats.clock_mhz = ks.clock_mhz;
-    g->stats.wall_ms = ks.wall_ms;
+    mirror_graph_stats(ks, ks.fold_launches + ks.merge_launches, ks.kernel_ms + ks.merge_ms, &g->stats);
     return GSIM_OK;
 }
 
@@ -219,9 +197,7 @@ int check_knn_join_args(gsim_db* db, gsim_graph** out, uint64_t nl, const KnnJoi
     if (!db || !out) return fail(GSIM_ERR_INVALID, "NULL argument");
     if (c.k < 1 || c.k > GSIM_KNN_MAX_K) return fail(GSIM_ERR_INVALID, "knn join: k must be in [1, GSIM_KNN_MAX_K = 128]");
     if (!(c.cutoff > 0.0f && c.cutoff <= 1.0f)) return fail(GSIM_ERR_INVALID, "knn join: the cutoff must be in (0, 1]");
-    if (c.metric != GSIM_METRIC_TANIMOTO && c.metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
-    if (c.metric == GSIM_METRIC_TVERSKY && !(std::isfinite(c.alpha) && std::isfinite(c.beta) && c.alpha >= 0.0f && c.beta >= 0.0f))
-        return fail(GSIM_ERR_INVALID, "knn join: Tversky alpha and beta must be finite and >= 0");
+    if (const int rc = check_metric("knn join", c.metric, c.alpha, c.beta)) return rc;
     if (flags & ~GSIM_KNN_EXCLUDE_SELF) return fail(GSIM_ERR_INVALID, "knn join: unknown flag bits");
     if (nl > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "knn join: 2^32 left rows or more");
     if (db->nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "knn join: tables of 2^32 rows or more");
@@ -229,30 +205,10 @@ int check_knn_join_args(gsim_db* db, gsim_graph** out, uint64_t nl, const KnnJoi
     return GSIM_OK;
 }
 
-int check_knn_join_state(const gsim_db* db, const char* which)
+int run_knn_join(gsim_db* db, const LeftSide& left, const KnnJoinCall& c, gsim_graph** out)
 {
-    if (!db->finalized) return fail(GSIM_ERR_STATE, std::string(which) + " not finalized (no rows on a GPU)");
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, std::string("knn joins need single-shard handles: ") + which);
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, std::string("knn joins do not support folded tables: ") + which);
-    return GSIM_OK;
-}
-
-int run_knn_join(gsim_db* db, const uint32_t* d_left, uint64_t nl, bool left_in_table, uint64_t left_row0, const KnnJoinCall& c, gsim_graph** out)
-{
-    gsim_graph* g = new (std::nothrow) gsim_graph;
-    if (!g) return fail(GSIM_ERR_NOMEM, "graph");
-    int rc;
-    try {
-        rc = knn_join(db, db->shards[0], d_left, nl, left_in_table, left_row0, c, g);
-    } catch (const std::bad_alloc&) {
-        rc = fail(GSIM_ERR_NOMEM, "host memory for the k-nearest-neighbour join's lists");
-    }
-    if (rc != GSIM_OK) {
-        delete g;
-        return rc;
-    }
-    *out = g;
-    return GSIM_OK;
+    return make_graph(out, "host memory for the k-nearest-neighbour join's lists",
+                      [&](gsim_graph* g) { return knn_join(db, db->shards[0], left, c, g); });
 }
 
 } // namespace
@@ -268,19 +224,10 @@ int gsim_db_knn_queries(gsim_db* db, const uint32_t* queries, uint64_t nq, uint3
     const KnnJoinCall c{k, cutoff, metric, alpha, beta, ~0ull};
     int rc = check_knn_join_args(db, out, nq, c, 0);
     if (rc != GSIM_OK) return rc;
-    if (nq && !queries) return fail(GSIM_ERR_INVALID, "NULL queries");
-    rc = check_knn_join_state(db, "table");
+    LeftSide left;
+    rc = left.from_queries(db, queries, nq, "knn joins", "the k-nearest-neighbour join's left rows");
     if (rc != GSIM_OK) return rc;
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    Shard& s = db->shards[0];
-    DevBuf<> d_left;
-    if (nq) {
-        GSIM_HIP(set_device(s.device));
-        const size_t bytes = static_cast<size_t>(nq) * s.W * 4;
-        GSIM_ALLOC(d_left, bytes, "the k-nearest-neighbour join's left rows");
-        GSIM_HIP(hipMemcpyAsync(d_left, queries, bytes, hipMemcpyHostToDevice, s.stream));
-    }
-    return run_knn_join(db, d_left.as<uint32_t>(), nq, false, 0, c, out);
+    return run_knn_join(db, left, c, out);
 }
 
 int gsim_db_knn_join(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, uint32_t k, float cutoff, int metric, float alpha,
@@ -294,20 +241,13 @@ int gsim_db_knn_join(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t l
     const KnnJoinCall c{k, cutoff, metric, alpha, beta, exclude ? lrow_begin : ~0ull};
     int rc = check_knn_join_args(db, out, lrow_end - lrow_begin, c, flags);
     if (rc != GSIM_OK) return rc;
-    if (!left) return fail(GSIM_ERR_INVALID, "NULL left handle");
-    if (exclude && left != db) return fail(GSIM_ERR_INVALID, "knn join: GSIM_KNN_EXCLUDE_SELF needs left == db");
-    if (lrow_end > left->nrows) return fail(GSIM_ERR_INVALID, "left row range outside the left table");
-    if (left->fp_bits != db->fp_bits) return fail(GSIM_ERR_INVALID, "the two handles have different fp_bits");
-    rc = check_knn_join_state(db, "table");
-    if (rc == GSIM_OK && left != db) rc = check_knn_join_state(left, "left table");
+    if (exclude && left && left != db) return fail(GSIM_ERR_INVALID, "knn join: GSIM_KNN_EXCLUDE_SELF needs left == db");
+    rc = check_left_handle(db, left, lrow_end);
     if (rc != GSIM_OK) return rc;
-    if (left->shards[0].device != db->shards[0].device) return fail(GSIM_ERR_STATE, "the two handles are on different devices");
-    // one call at a time on either handle
-    std::unique_lock<std::mutex> g1(db->search_mutex, std::defer_lock), g2(left->search_mutex, std::defer_lock);
-    if (left != db) std::lock(g1, g2);
-    else g1.lock();
-    const uint32_t* d_left = static_cast<const uint32_t*>(left->shards[0].d_rows) + lrow_begin * left->shards[0].W;
-    return run_knn_join(db, d_left, lrow_end - lrow_begin, left == db, lrow_begin, c, out);
+    LeftSide ls;
+    rc = ls.from_handle(db, left, lrow_begin, lrow_end, "knn joins");
+    if (rc != GSIM_OK) return rc;
+    return run_knn_join(db, ls, c, out);
 }
 
 int gsim_graph_get_knn_join_stats(const gsim_graph* g, gsim_knn_join_stats* out)

@@ -2,7 +2,7 @@
 // (the column counts of every label in one pass), gsim_label_centroids (host: the majority votes) and gsim_db_kmeans (the loop over
 // the three, labels resident on the device).  The argument checks, the slabs and launch cuts and the copies of a call; the device
 // side is gsim_assign.hip and gsim_labels.hip.  The rules are stated in include/gpusim_hip.h; DESIGN.md section 21 has the routes.
-#include "capi_internal.h"
+#include "capi_front.h"
 
 #include <chrono>
 
@@ -185,9 +185,7 @@ int check_assign_args(const gsim_db* db, uint32_t m, uint64_t row_begin, uint64_
 {
     if (!db) return fail(GSIM_ERR_INVALID, "NULL argument");
     if (m == 0 || m > GSIM_ASSIGN_MAX_CENTRES) return fail(GSIM_ERR_INVALID, "assign: the number of centres must be 1 ... GSIM_ASSIGN_MAX_CENTRES");
-    if (metric != GSIM_METRIC_TANIMOTO && metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
-    if (metric == GSIM_METRIC_TVERSKY && !(std::isfinite(alpha) && alpha >= 0.0f && std::isfinite(beta) && beta >= 0.0f))
-        return fail(GSIM_ERR_INVALID, "assign: Tversky alpha and beta must be finite and >= 0");
+    if (const int rc = check_metric("assign", metric, alpha, beta)) return rc;
     return check_range(db, row_begin, row_end, "assign");
 }
 

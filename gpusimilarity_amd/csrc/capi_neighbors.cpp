@@ -1,6 +1,6 @@
 // capi_neighbors.cpp -- gsim_db_neighbors (every pair of rows at or above a cutoff, as CSR) and gsim_butina (Taylor-Butina
 // clustering of such a graph, host code).  The device side is gsim_neighbors.hip.
-#include "capi_pairs.h"
+#include "capi_front.h"
 
 #include <chrono>
 #include <numeric>
@@ -100,20 +100,8 @@ int gsim_db_neighbors(gsim_db* db, float cutoff, int metric, float alpha, float 
     if (db->fold > 1) return fail(GSIM_ERR_STATE, "neighbour lists do not support folded tables");
     if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, "neighbour lists need a single-shard handle");
     std::lock_guard<std::mutex> guard(db->search_mutex);
-    gsim_graph* g = new (std::nothrow) gsim_graph;
-    if (!g) return fail(GSIM_ERR_NOMEM, "graph");
-    int rc;
-    try {
-        rc = neighbors(db, db->shards[0], cutoff, metric, alpha, beta, row_begin, row_end, g);
-    } catch (const std::bad_alloc&) {
-        rc = fail(GSIM_ERR_NOMEM, "host memory for the neighbour lists");
-    }
-    if (rc != GSIM_OK) {
-        delete g;
-        return rc;
-    }
-    *out = g;
-    return GSIM_OK;
+    return make_graph(out, "host memory for the neighbour lists",
+                      [&](gsim_graph* g) { return neighbors(db, db->shards[0], cutoff, metric, alpha, beta, row_begin, row_end, g); });
 }
 
 int gsim_butina(const uint64_t* indptr, const uint32_t* indices, uint64_t nrows, uint32_t* cluster_of, uint32_t* centroids,

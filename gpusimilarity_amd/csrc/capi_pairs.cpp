@@ -192,6 +192,43 @@ int build_pair_csr(gsim_db* db, Shard& s, uint64_t total, uint64_t nout, int ord
     return GSIM_OK;
 }
 
+int build_knn_csr(gsim_db* db, Shard& s, const gsim::KnnEntry* lists, const uint32_t* len, uint64_t nout, uint32_t k, const DevBuf<>& tmp,
+                  uint64_t* d_indptr, const DevBuf<>& ctl, const char* csr_what, const char* prefix, gsim_graph* g, KnnCsr* out)
+{
+    const hipStream_t st = s.stream;
+    DevBuf<uint32_t>& d_indices = out->d_indices;
+    DevBuf<float>& d_scores = out->d_scores;
+    EventPair ev_csr, ev_d2h;
+    GSIM_HIP(ev_csr.create());
+    GSIM_HIP(ev_d2h.create());
+    // indptr on the device; its last entry sizes the compacted arrays
+    GSIM_HIP(hipEventRecord(ev_csr.a, st));
+    GSIM_HIP(gsim::launch_knn_offsets(tmp, tmp.bytes(), len, nout + 1, d_indptr, st));
+    out->ctl.resize(ctl.bytes() / 8);
+    GSIM_HIP(hipMemcpyAsync(g->indptr.data(), d_indptr, (nout + 1) * 8, hipMemcpyDeviceToHost, st));
+    GSIM_HIP(hipMemcpyAsync(out->ctl.data(), ctl, ctl.bytes(), hipMemcpyDeviceToHost, st));
+    GSIM_HIP(hipStreamSynchronize(st));
+    const uint64_t total = g->indptr[nout];
+    if (total > nout * k) return fail(GSIM_ERR_STATE, std::string(prefix) + ": the device reported impossible list lengths");
+    const std::string what = std::string("device memory for ") + csr_what;
+    if (d_indices.grow(total * 4) != hipSuccess || d_scores.grow(total * 4) != hipSuccess) return fail(GSIM_ERR_NOMEM, what);
+    GSIM_HIP(gsim::launch_knn_compact(lists, len, d_indptr, nout, k, db->row_base, d_indices, d_scores, st));
+    GSIM_HIP(hipEventRecord(ev_csr.b, st));
+    g->indices.resize(total);
+    g->scores.resize(total);
+    GSIM_HIP(hipEventRecord(ev_d2h.a, st));
+    if (total) {
+        GSIM_HIP(hipMemcpyAsync(g->indices.data(), d_indices, total * 4, hipMemcpyDeviceToHost, st));
+        GSIM_HIP(hipMemcpyAsync(g->scores.data(), d_scores, total * 4, hipMemcpyDeviceToHost, st));
+    }
+    GSIM_HIP(hipEventRecord(ev_d2h.b, st));
+    GSIM_HIP(hipStreamSynchronize(st));
+    out->total = total;
+    out->csr_ms = ev_csr.ms();
+    out->d2h_ms = ev_d2h.ms();
+    return GSIM_OK;
+}
+
 } // namespace gsim_host
 
 using namespace gsim_host;

@@ -1,6 +1,7 @@
 // capi_pairs.h -- what gsim_db_neighbors (capi_neighbors.cpp) and the threshold joins (capi_join.cpp) share: the result
 // object, the handle's pair buffer with its overflow / exact-regrow protocol, the tile kernel's launch plan, and the CSR
-// build.  Implemented in capi_pairs.cpp.  Internal.
+// build; and what the k-NN calls (capi_knn.cpp, capi_knn_join.cpp, capi_mst.cpp) share: the fold launches' plan and the CSR
+// build of their lists.  Implemented in capi_pairs.cpp (the k-NN plan: capi_knn_join.cpp).  Internal.
 #pragma once
 
 #include "capi_internal.h"
@@ -32,13 +33,6 @@ std::vector<NbrLaunch> plan_launches(uint64_t nlt, uint64_t nct, bool tri, uint3
 // ... each of at most pair_budget pairs instead (at least one tile; 0: the work budget) -- gsim_db_components' knob
 std::vector<NbrLaunch> plan_launches(uint64_t nlt, uint64_t nct, bool tri, uint32_t WP, uint64_t pair_budget);
 
-// The fold launches of gsim_db_knn and gsim_db_mst over nout owner rows x N candidate rows (capi_knn.cpp has the rule)
-struct KnnLaunch {
-    uint32_t ot0, not_; // owner tiles
-    uint64_t c0, c1;    // candidate rows
-};
-std::vector<KnnLaunch> plan_knn(uint64_t nout, uint64_t N, uint32_t WP, long long pairs);
-
 // The column segments and fold launches of gsim_db_knn_join* over nl owner rows x N table rows on num_cus compute units
 // (capi_knn_join.cpp has the rule; `segments`, `pairs`: GSIM_KNN_JOIN_SEGMENTS, GSIM_KNN_JOIN_LAUNCH_PAIRS).  Pure.  With
 // segments == 0 the partial lists, nl x S x k x 8 bytes, stay below 2 x (2 x num_cus) x 256 x k x 8: 256 MiB at k = 128, 256 CUs.
@@ -51,6 +45,13 @@ struct KnnJoinPlan {
     std::vector<KnnJoinLaunch> launches;
 };
 KnnJoinPlan plan_knn_join(uint64_t nl, uint64_t N, uint32_t WP, int num_cus, int segments, long long pairs);
+// The fold launches of gsim_db_knn and gsim_db_mst over nout owner rows x N candidate rows: plan_knn_join's with one segment,
+// whose rows are the table's
+struct KnnLaunch {
+    uint32_t ot0, not_; // owner tiles
+    uint64_t c0, c1;    // candidate rows
+};
+std::vector<KnnLaunch> plan_knn(uint64_t nout, uint64_t N, uint32_t WP, long long pairs);
 
 // Where a launch appends: the shard's pair buffer as it is now
 struct PairSink {
@@ -74,5 +75,30 @@ int run_pair_launches(Shard& s, size_t n, unsigned long long* d_cursor, unsigned
 // The pair buffer's `total` entries (keys = list << 32 | column) -> g's CSR over nout lists, columns + db->row_base; each list
 // by column (GSIM_JOIN_BY_ROW) or by (score descending, column) (GSIM_JOIN_BY_SCORE).  Fills g->stats.csr_ms / d2h_ms.
 int build_pair_csr(gsim_db* db, Shard& s, uint64_t total, uint64_t nout, int order, gsim_graph* g);
+
+// The k-NN calls' lists (nout of them, k slots each, `len` entries used; one more length, zero) -> g's CSR, columns +
+// db->row_base: offsets by a scan (scratch `tmp`) into d_indptr, then, once the host has seen the total, compaction into
+// device memory of the name `csr_what`.  The control block `ctl` comes back with the offsets, in the same group of copies.
+// STATE "<prefix>: the device reported impossible list lengths".  Returns with the stream idle.
+struct KnnCsr {
+    uint64_t total = 0;                  // entries of the CSR
+    double csr_ms = 0.0, d2h_ms = 0.0;   // HIP events; csr_ms spans the host's look at the total: offsets, one small read, compaction
+    std::vector<unsigned long long> ctl; // the control block as the fold (and merge) launches left it
+    DevBuf<uint32_t> d_indices;          // the compacted arrays: the caller's to free, after it has taken its wall time
+    DevBuf<float> d_scores;
+};
+int build_knn_csr(gsim_db* db, Shard& s, const gsim::KnnEntry* lists, const uint32_t* len, uint64_t nout, uint32_t k, const DevBuf<>& tmp,
+                  uint64_t* d_indptr, const DevBuf<>& ctl, const char* csr_what, const char* prefix, gsim_graph* g, KnnCsr* out);
+// g->stats from the fields that gsim_knn_stats and gsim_knn_join_stats share, once those are final
+template <class Stats> void mirror_graph_stats(const Stats& ks, uint64_t launches, double tile_ms, gsim_graph_stats* gs)
+{
+    gs->launches = launches;
+    gs->pairs = ks.entries;
+    gs->tile_ms = tile_ms;
+    gs->csr_ms = ks.csr_ms;
+    gs->d2h_ms = ks.d2h_ms;
+    gs->clock_mhz = ks.clock_mhz;
+    gs->wall_ms = ks.wall_ms;
+}
 
 } // namespace gsim_host

@@ -1,11 +1,10 @@
 // capi_scores.cpp -- gsim_db_scores / gsim_db_scores_queries / gsim_db_scores_device: the dense matrix of scores of a block of
-// left rows against a range of table rows.  Two thin fronts (handle rows, host queries) and the device front over one core that
-// takes "left rows in device memory, nl of them", as the histograms; the argument checks, the prepare step, the launch plan and
-// the staging slabs of the host-output calls.  The device side is gsim_scores.hip.  The rule is stated in include/gpusim_hip.h.
-#include "capi_internal.h"
+// left rows against a range of table rows.  The family's argument checks and one core that takes "left rows in device memory, nl
+// of them" from a front's LeftSide (capi_front.h), as the histograms, with the prepare step, the launch plan and the staging slabs
+// of the host-output calls.  The device side is gsim_scores.hip.  The rule is stated in include/gpusim_hip.h.
+#include "capi_front.h"
 
 #include <chrono>
-#include <cmath>
 
 namespace gsim_host
 {
@@ -144,39 +143,30 @@ int scores(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, const Sco
     return GSIM_OK;
 }
 
-// what every entry point checks before any device state (left == nullptr: the queries entry, nl = nq)
-int check_scores_args(gsim_db* db, const gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, uint64_t rrow_begin, uint64_t rrow_end, int metric,
-                      float alpha, float beta, const void* out, uint64_t ld)
+// what every entry point checks before any device state (`handle`: the left rows are `left`'s; else the queries entry, nl = nq)
+int check_scores_args(gsim_db* db, bool handle, const gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, uint64_t rrow_begin, uint64_t rrow_end,
+                      int metric, float alpha, float beta, const void* out, uint64_t ld)
 {
     if (!db) return fail(GSIM_ERR_INVALID, "NULL argument");
-    if (metric != GSIM_METRIC_TANIMOTO && metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
-    if (metric == GSIM_METRIC_TVERSKY && !(std::isfinite(alpha) && alpha >= 0.0f && std::isfinite(beta) && beta >= 0.0f))
-        return fail(GSIM_ERR_INVALID, "scores: Tversky alpha and beta must be finite and >= 0");
+    if (const int rc = check_metric("scores", metric, alpha, beta)) return rc;
     if (lrow_begin > lrow_end) return fail(GSIM_ERR_INVALID, "left row range: begin past end");
-    if (left && lrow_end > left->nrows) return fail(GSIM_ERR_INVALID, "left row range outside the left table");
+    // (ahead of the count of left rows: a handle's range is refused as outside its table, whatever its length)
+    if (handle)
+        if (const int rc = check_left_handle(db, left, lrow_end)) return rc;
     if (rrow_begin > rrow_end) return fail(GSIM_ERR_INVALID, "table row range: begin past end");
     if (rrow_end > db->nrows) return fail(GSIM_ERR_INVALID, "table row range outside the table");
     const uint64_t nl = lrow_end - lrow_begin, nr = rrow_end - rrow_begin;
     if (nl > 0xFFFFFFFFull || nr > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "scores: 2^32 rows or more on one side");
     if (ld < nr) return fail(GSIM_ERR_INVALID, "scores: ld is less than the number of table rows");
-    if (left && left->fp_bits != db->fp_bits) return fail(GSIM_ERR_INVALID, "the two handles have different fp_bits");
     if (gsim::scores_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, "score matrices support rows of up to 4096 bits");
     if (!out && nl > 0 && nr > 0) return fail(GSIM_ERR_INVALID, "scores: NULL output");
     return GSIM_OK;
 }
 
-int check_scores_state(const gsim_db* db, const char* which)
-{
-    if (!db->finalized) return fail(GSIM_ERR_STATE, std::string(which) + " not finalized (no rows on a GPU)");
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, std::string("score matrices do not support folded tables: ") + which);
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, std::string("score matrices need single-shard handles: ") + which);
-    return GSIM_OK;
-}
-
-int run_scores(gsim_db* db, const uint32_t* d_left, uint64_t nl, const ScoresCall& c)
+int run_scores(gsim_db* db, const LeftSide& left, const ScoresCall& c)
 {
     try {
-        return scores(db, db->shards[0], d_left, nl, c);
+        return scores(db, db->shards[0], left.rows, left.nl, c);
     } catch (const std::bad_alloc&) {
         return fail(GSIM_ERR_NOMEM, "host memory for the score matrix");
     }
@@ -186,20 +176,13 @@ int run_scores(gsim_db* db, const uint32_t* d_left, uint64_t nl, const ScoresCal
 int scores_of_handle(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, uint64_t rrow_begin, uint64_t rrow_end, int metric,
                      float alpha, float beta, float* out, float* d_out, uint64_t ld, gsim_scores_stats* stats)
 {
-    if (!left) return fail(GSIM_ERR_INVALID, "NULL left handle");
-    int rc = check_scores_args(db, left, lrow_begin, lrow_end, rrow_begin, rrow_end, metric, alpha, beta, out ? static_cast<void*>(out) : d_out, ld);
+    int rc = check_scores_args(db, true, left, lrow_begin, lrow_end, rrow_begin, rrow_end, metric, alpha, beta, out ? static_cast<void*>(out) : d_out, ld);
     if (rc != GSIM_OK) return rc;
-    rc = check_scores_state(db, "table");
-    if (rc == GSIM_OK && left != db) rc = check_scores_state(left, "left table");
+    LeftSide ls;
+    rc = ls.from_handle(db, left, lrow_begin, lrow_end, "score matrices");
     if (rc != GSIM_OK) return rc;
-    if (left->shards[0].device != db->shards[0].device) return fail(GSIM_ERR_STATE, "the two handles are on different devices");
-    // one call at a time on either handle
-    std::unique_lock<std::mutex> g1(db->search_mutex, std::defer_lock), g2(left->search_mutex, std::defer_lock);
-    if (left != db) std::lock(g1, g2);
-    else g1.lock();
-    const uint32_t* d_left = static_cast<const uint32_t*>(left->shards[0].d_rows) + lrow_begin * left->shards[0].W;
     const ScoresCall c{rrow_begin, rrow_end - rrow_begin, metric, alpha, beta, out, d_out, ld, stats};
-    return run_scores(db, d_left, lrow_end - lrow_begin, c);
+    return run_scores(db, ls, c);
 }
 
 } // namespace
@@ -224,22 +207,14 @@ int gsim_db_scores_device(gsim_db* db, gsim_db* left, uint64_t lrow_begin, uint6
 int gsim_db_scores_queries(gsim_db* db, const uint32_t* queries, uint64_t nq, uint64_t rrow_begin, uint64_t rrow_end, int metric, float alpha,
                            float beta, float* out, uint64_t ld, gsim_scores_stats* stats)
 {
-    int rc = check_scores_args(db, nullptr, 0, nq, rrow_begin, rrow_end, metric, alpha, beta, out, ld);
+    int rc = check_scores_args(db, false, nullptr, 0, nq, rrow_begin, rrow_end, metric, alpha, beta, out, ld);
     if (rc != GSIM_OK) return rc;
-    if (nq && !queries) return fail(GSIM_ERR_INVALID, "NULL queries");
-    rc = check_scores_state(db, "table");
+    LeftSide left;
+    // (no table rows: the core reads no left row)
+    rc = left.from_queries(db, queries, nq, "score matrices", "the score matrix's left rows", rrow_end > rrow_begin);
     if (rc != GSIM_OK) return rc;
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    Shard& s = db->shards[0];
-    DevBuf<> d_left;
-    if (nq && rrow_end > rrow_begin) {
-        GSIM_HIP(set_device(s.device));
-        const size_t bytes = static_cast<size_t>(nq) * s.W * 4;
-        GSIM_ALLOC(d_left, bytes, "the score matrix's left rows");
-        GSIM_HIP(hipMemcpyAsync(d_left, queries, bytes, hipMemcpyHostToDevice, s.stream));
-    }
     const ScoresCall c{rrow_begin, rrow_end - rrow_begin, metric, alpha, beta, out, nullptr, ld, stats};
-    return run_scores(db, d_left.as<uint32_t>(), nq, c);
+    return run_scores(db, left, c);
 }
 
 } // extern "C"

@@ -8,7 +8,9 @@
 //   * under the automatic rule the partial lists stay below 2 x (2 x CUs) x 256 x k x 8 bytes;
 //   * no launch walks more columns than gsim_db_knn's per-lane bound, a launch prices within the tile budget (or is one column
 //     tile per segment), a pair budget is kept (or the launch is one column tile per segment);
-//   * with S == 1 the launches are plan_knn's.
+//   * with S == 1 the launches are plan_knn's;
+//   * plan_knn, which is plan_knn_join with one segment, gives launch for launch what its own loop gave before the two were one
+//     (restated here as plan_knn_before).
 #include "../../gpusimilarity_amd/csrc/capi_pairs.h"
 
 #include <cstdio>
@@ -33,6 +35,30 @@ uint64_t g_nl, g_N;
 uint32_t g_WP;
 int g_cus, g_seg;
 long long g_pairs;
+
+// gsim_db_knn's plan as it was written out before it became plan_knn_join with one segment: the oracle of plan_knn
+std::vector<KnnLaunch> plan_knn_before(uint64_t nout, uint64_t N, uint32_t WP, long long pairs)
+{
+    const uint64_t tile = gsim::kKnnTile, ctile = gsim::kKnnColTile;
+    const uint64_t not_total = (nout + tile - 1) / tile;
+    const uint64_t max_tiles = launch_tile_budget(WP);
+    const uint64_t group = std::min<uint64_t>(std::min(not_total, max_tiles), 1u << 30);
+    std::vector<KnnLaunch> out;
+    for (uint64_t t0 = 0; t0 < not_total; t0 += group) {
+        const uint64_t nt = std::min(group, not_total - t0);
+        uint64_t cols;
+        if (pairs > 0) {
+            const uint64_t owners = std::min(nt * tile, nout - t0 * tile);
+            cols = static_cast<uint64_t>(pairs) / owners / ctile * ctile;
+        } else {
+            cols = std::min(max_tiles / nt * ctile, max_tiles / ctile * ctile);
+        }
+        cols = std::max(cols, ctile);
+        for (uint64_t c0 = 0; c0 < N; c0 += cols)
+            out.push_back({static_cast<uint32_t>(t0), static_cast<uint32_t>(nt), c0, std::min(c0 + cols, N)});
+    }
+    return out;
+}
 
 void check_one(uint64_t nl, uint64_t N, uint32_t WP, int cus, int segments, long long pairs)
 {
@@ -93,8 +119,11 @@ void check_one(uint64_t nl, uint64_t N, uint32_t WP, int cus, int segments, long
     for (uint64_t t = 0; t < ot; t++)
         for (uint64_t s = 0; s < S; s++) CHECK(done[t * S + s] == gsim::knn_join_seg_begin(s + 1, S, N) - gsim::knn_join_seg_begin(s, S, N));
 
+    const std::vector<KnnLaunch> ref = plan_knn(nl, N, WP, pairs), before = plan_knn_before(nl, N, WP, pairs);
+    CHECK(ref.size() == before.size()); // (whatever this call's S, CUs and `segments` are)
+    for (size_t i = 0; i < ref.size() && i < before.size(); i++)
+        CHECK(ref[i].ot0 == before[i].ot0 && ref[i].not_ == before[i].not_ && ref[i].c0 == before[i].c0 && ref[i].c1 == before[i].c1);
     if (S == 1) {
-        const std::vector<KnnLaunch> ref = plan_knn(nl, N, WP, pairs);
         CHECK(ref.size() == plan.launches.size());
         for (size_t i = 0; i < ref.size() && i < plan.launches.size(); i++)
             CHECK(ref[i].ot0 == plan.launches[i].ot0 && ref[i].not_ == plan.launches[i].not_ && ref[i].c0 == plan.launches[i].r0 &&
