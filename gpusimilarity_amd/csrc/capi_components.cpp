@@ -1,9 +1,8 @@
 // capi_components.cpp -- gsim_db_components (single-linkage clustering: the connected components of the threshold graph at up to
 // eight cutoffs, in one pass over the pairs) and gsim_components (the same rule on a symmetric CSR graph, host code).  The argument
 // checks and the launch sequence of a call; the device side is gsim_components.hip.  The rule is stated in include/gpusim_hip.h.
-#include "capi_pairs.h"
+#include "capi_front.h"
 
-#include <chrono>
 #include <cmath>
 
 namespace gsim_host
@@ -112,22 +111,9 @@ int components(gsim_db* db, Shard& s, const float* cutoffs, uint32_t nlevels, in
         st->d2h_ms = ev_d2h.ms();
         clocks.add(h_ctl.data() + gsim::kCompCounters, plan.size()); // (read with the counters, in one copy)
         st->clock_mhz = clocks.mhz();
-        st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        st->wall_ms = ms_since(t0);
     }
     return GSIM_OK;
-}
-
-// the forest of gsim_components: the smaller index wins every hook, so a tree's root is its smallest row
-uint32_t host_root(std::vector<uint32_t>& parent, uint32_t x)
-{
-    uint32_t r = x;
-    while (parent[r] != r) r = parent[r];
-    while (parent[x] != r) {
-        const uint32_t p = parent[x];
-        parent[x] = r;
-        x = p;
-    }
-    return r;
 }
 
 } // namespace
@@ -147,66 +133,30 @@ int gsim_db_components(gsim_db* db, const float* cutoffs, uint32_t nlevels, int 
         if (!(cutoffs[l] > 0.0f && cutoffs[l] <= 1.0f)) return fail(GSIM_ERR_INVALID, "components: every cutoff must be in (0, 1]");
         if (l && !(cutoffs[l - 1] < cutoffs[l])) return fail(GSIM_ERR_INVALID, "components: the cutoffs must be strictly ascending");
     }
-    if (metric != GSIM_METRIC_TANIMOTO && metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
-    if (metric == GSIM_METRIC_TVERSKY && !(alpha == beta))
-        return fail(GSIM_ERR_INVALID, "components need a symmetric metric (Tversky with alpha == beta)");
-    if (metric == GSIM_METRIC_TVERSKY && !(std::isfinite(alpha) && alpha >= 0.0f))
-        return fail(GSIM_ERR_INVALID, "components: Tversky alpha = beta must be finite and >= 0");
+    if (const int rc = check_symmetric_metric("components need", "components", metric, alpha, beta)) return rc;
     if (db->fp_bits > 4096 || gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, "components: rows wider than 4096 bits");
     const uint64_t N = db->nrows;
     if (N > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "components: tables of 2^32 rows or more");
     for (uint32_t l = 0; l < nlevels; l++) ncomponents[l] = 0;
     if (N == 0) return GSIM_OK;
-    if (!db->finalized) return fail(GSIM_ERR_STATE, "table not finalized (no rows on a GPU)");
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, "components do not support folded tables");
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, "components need a single-shard handle");
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    Shard& s = db->shards[0];
-    int rc;
-    try {
-        rc = components(db, s, cutoffs, nlevels, metric, alpha, beta, component_of, ncomponents, first_row, sizes, stats);
-    } catch (const std::bad_alloc&) {
-        rc = fail(GSIM_ERR_NOMEM, "host memory for components");
-    }
-    if (rc != GSIM_OK) s.state_dirty = true; // (launches of the call may have failed mid-stream: the next enqueue re-zeroes the search state)
-    return rc;
+    if (const int rc = check_table_state(db, "components", true)) return rc;
+    return on_one_shard(db, "host memory for components", [&](Shard& s) {
+        return components(db, s, cutoffs, nlevels, metric, alpha, beta, component_of, ncomponents, first_row, sizes, stats);
+    });
 }
 
 int gsim_components(const uint64_t* indptr, const uint32_t* indices, uint64_t nrows, uint32_t* component_of, uint32_t* first_row,
                     uint32_t* sizes, uint64_t* ncomponents)
 {
     if (!indptr || !ncomponents || (nrows && !component_of)) return fail(GSIM_ERR_INVALID, "NULL argument");
-    if (nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "more than 2^32-1 rows");
-    if (indptr[0] != 0) return fail(GSIM_ERR_INVALID, "indptr[0] must be 0");
-    for (uint64_t r = 0; r < nrows; r++)
-        if (indptr[r + 1] < indptr[r]) return fail(GSIM_ERR_INVALID, "indptr must not decrease");
-    const uint64_t nnz = indptr[nrows];
-    if (nnz && !indices) return fail(GSIM_ERR_INVALID, "NULL indices");
-    for (uint64_t e = 0; e < nnz; e++)
-        if (indices[e] >= nrows) return fail(GSIM_ERR_INVALID, "column index outside the graph");
+    uint64_t nnz = 0;
+    if (const int rc = check_csr_offsets(indptr, nrows, &nnz)) return rc;
+    if (const int rc = check_csr_indices(indices, nnz, nrows)) return rc;
     try {
-        std::vector<uint32_t> parent(nrows);
-        for (uint64_t r = 0; r < nrows; r++) parent[r] = static_cast<uint32_t>(r);
+        Forest f(nrows);
         for (uint64_t r = 0; r < nrows; r++)
-            for (uint64_t e = indptr[r]; e < indptr[r + 1]; e++) {
-                const uint32_t x = host_root(parent, static_cast<uint32_t>(r)), y = host_root(parent, indices[e]);
-                if (x != y) parent[std::max(x, y)] = std::min(x, y);
-            }
-        // rows ascending: a root comes before every other row of its component and takes the next number
-        uint32_t nc = 0;
-        for (uint64_t r = 0; r < nrows; r++) {
-            const uint32_t root = host_root(parent, static_cast<uint32_t>(r));
-            if (root == r) {
-                component_of[r] = nc;
-                if (first_row) first_row[nc] = static_cast<uint32_t>(r);
-                if (sizes) sizes[nc] = 1;
-                nc++;
-            } else {
-                component_of[r] = component_of[root];
-                if (sizes) sizes[component_of[root]]++;
-            }
-        }
-        *ncomponents = nc;
+            for (uint64_t e = indptr[r]; e < indptr[r + 1]; e++) f.unite(static_cast<uint32_t>(r), indices[e]);
+        *ncomponents = number_components(f, nrows, component_of, first_row, sizes);
     } catch (const std::bad_alloc&) {
         return fail(GSIM_ERR_NOMEM, "components");
     }

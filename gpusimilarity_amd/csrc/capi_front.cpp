@@ -1,6 +1,8 @@
 // capi_front.cpp -- the shared fronts of capi_front.h.
 #include "capi_front.h"
 
+#include <unordered_set>
+
 namespace gsim_host
 {
 
@@ -65,6 +67,47 @@ int LeftSide::from_queries(gsim_db* db, const uint32_t* queries, uint64_t nq, co
     }
     rows = d_left.as<uint32_t>();
     nl = nq;
+    return GSIM_OK;
+}
+
+int check_table_state(const gsim_db* db, const char* subject, bool plural)
+{
+    if (!db->finalized) return fail(GSIM_ERR_STATE, "table not finalized (no rows on a GPU)");
+    if (db->fold > 1) return fail(GSIM_ERR_STATE, std::string(subject) + (plural ? " do not" : " does not") + " support folded tables");
+    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, std::string(subject) + (plural ? " need" : " needs") + " a single-shard handle");
+    return GSIM_OK;
+}
+
+int check_symmetric_metric(const char* needs, const char* prefix, int metric, float alpha, float beta)
+{
+    if (metric != GSIM_METRIC_TANIMOTO && metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
+    if (metric != GSIM_METRIC_TVERSKY) return GSIM_OK;
+    if (!(alpha == beta)) return fail(GSIM_ERR_INVALID, std::string(needs) + " a symmetric metric (Tversky with alpha == beta)");
+    if (prefix && !(std::isfinite(alpha) && alpha >= 0.0f))
+        return fail(GSIM_ERR_INVALID, std::string(prefix) + ": Tversky alpha = beta must be finite and >= 0");
+    return GSIM_OK;
+}
+
+int check_row_range(const gsim_db* db, uint64_t row_begin, uint64_t row_end)
+{
+    if (row_begin > row_end) return fail(GSIM_ERR_INVALID, "row range: begin past end");
+    if (row_end > db->nrows) return fail(GSIM_ERR_INVALID, "row range outside the table");
+    return GSIM_OK;
+}
+
+int check_seeds(const gsim_db* db, const uint32_t* seeds, uint32_t nseeds, const char* nomem_what)
+{
+    if (nseeds && !seeds) return fail(GSIM_ERR_INVALID, "NULL seeds");
+    try {
+        std::unordered_set<uint32_t> seen;
+        for (uint32_t j = 0; j < nseeds; j++) {
+            if (seeds[j] < db->row_base || static_cast<uint64_t>(seeds[j]) >= db->row_base + db->nrows)
+                return fail(GSIM_ERR_INVALID, "seed row outside the table");
+            if (!seen.insert(seeds[j]).second) return fail(GSIM_ERR_INVALID, "repeated seed row");
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(GSIM_ERR_NOMEM, nomem_what);
+    }
     return GSIM_OK;
 }
 

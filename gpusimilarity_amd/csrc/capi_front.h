@@ -1,7 +1,8 @@
 // capi_front.h -- what a call does before and after its launches, where several entry points had each carried a copy: the metric
 // check, the state check and the left side of the two-table families (threshold joins, k-NN joins, histograms, score matrices:
-// capi_join / capi_knn_join / capi_hist / capi_scores.cpp), and the wrapper of the graph-returning calls.  Each family keeps its own
-// argument checks.  Implemented in capi_front.cpp; DESIGN.md section 24.  Internal.
+// capi_join / capi_knn_join / capi_hist / capi_scores.cpp), the wrapper of the graph-returning calls, and the checks and the runner
+// of the calls on one table.  Each family keeps its own argument checks.  Implemented in capi_front.cpp; DESIGN.md sections 24 and
+// 25.  Internal.
 #pragma once
 
 #include "capi_pairs.h"
@@ -52,6 +53,40 @@ template <class Fn> int make_graph(gsim_graph** out, const char* nomem_what, Fn&
         rc = fail(GSIM_ERR_NOMEM, nomem_what);
     }
     if (rc == GSIM_OK) *out = g.release();
+    return rc;
+}
+
+// ---- the calls on one table ----
+
+// The STATE errors of a single-table call, in one order: not finalized, "<subject> does not|do not support folded tables",
+// "<subject> needs|need a single-shard handle".
+int check_table_state(const gsim_db* db, const char* subject, bool plural);
+
+// INVALID "unknown metric", then "<needs> a symmetric metric (Tversky with alpha == beta)" (`needs`: "maxmin needs", "components
+// need"), then "<prefix>: Tversky alpha = beta must be finite and >= 0" -- not with prefix == nullptr: gsim_db_neighbors has never
+// had that line.
+int check_symmetric_metric(const char* needs, const char* prefix, int metric, float alpha, float beta);
+
+// INVALID "row range: begin past end", then "row range outside the table"
+int check_row_range(const gsim_db* db, uint64_t row_begin, uint64_t row_end);
+
+// INVALID "NULL seeds", then per seed "seed row outside the table" and "repeated seed row"; NOMEM `nomem_what`
+int check_seeds(const gsim_db* db, const uint32_t* seeds, uint32_t nseeds, const char* nomem_what);
+
+// The call on the handle's one shard, which check_table_state has passed: one call at a time per handle; NOMEM `nomem_what` when
+// core(shard) runs out of host memory; a failed core may have stopped between its launches, so the shard is marked and the next
+// enqueue re-zeroes the search state (rezero_dirty_state).
+template <class Fn> int on_one_shard(gsim_db* db, const char* nomem_what, Fn&& core)
+{
+    std::lock_guard<std::mutex> guard(db->search_mutex);
+    Shard& s = db->shards[0];
+    int rc;
+    try {
+        rc = core(s);
+    } catch (const std::bad_alloc&) {
+        rc = fail(GSIM_ERR_NOMEM, nomem_what);
+    }
+    if (rc != GSIM_OK) s.state_dirty = true;
     return rc;
 }
 

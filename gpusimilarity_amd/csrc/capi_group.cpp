@@ -2,9 +2,7 @@
 // queries.  The argument checks and the launch sequence of a call; the device side is gsim_group.hip (the scan, cut into
 // launches; `which` behind the tail's rebuilt hits) and the four-kernel pipeline's own tail (capi_query.cpp enqueue_scan_tail).
 // The rule is stated in include/gpusim_hip.h.
-#include "capi_internal.h"
-
-#include <chrono>
+#include "capi_front.h"
 
 namespace gsim_host
 {
@@ -113,7 +111,7 @@ int search_group(gsim_db* db, Shard& s, const uint32_t* queries, uint32_t nq, in
         if (hipEventElapsedTime(&ms, e0, e2) == hipSuccess) st->kernel_ms = ms;
         st->launches = launches;
         st->pairs = s.nrows * nq;
-        st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        st->wall_ms = ms_since(t0);
     }
     return GSIM_OK;
 }
@@ -139,19 +137,10 @@ int gsim_db_search_group(gsim_db* db, const uint32_t* queries, uint32_t nq, int 
         return fail(GSIM_ERR_INVALID, "group search: Tversky needs finite alpha >= 0, beta >= 0 and alpha + beta >= 1 (pair scores within [0, 1])");
     if (db->fp_bits > 4096) return fail(GSIM_ERR_INVALID, "group search: rows wider than 4096 bits");
     if (db->nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "group search: tables of 2^32 rows or more");
-    if (!db->finalized) return fail(GSIM_ERR_STATE, "table not finalized (no rows on a GPU)");
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, "group searches do not support folded tables");
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, "group searches need a single-shard handle");
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    Shard& s = db->shards[0];
-    int rc;
-    try {
-        rc = search_group(db, s, queries, nq, mode, k, cutoff, metric, alpha, beta, hits, count, approx, stats);
-    } catch (const std::bad_alloc&) {
-        rc = fail(GSIM_ERR_NOMEM, "host memory for a group search");
-    }
-    if (rc != GSIM_OK) s.state_dirty = true; // (the per-query state may not be zero: re-zeroed before the next enqueue)
-    return rc;
+    if (const int rc = check_table_state(db, "group searches", true)) return rc;
+    return on_one_shard(db, "host memory for a group search", [&](Shard& s) {
+        return search_group(db, s, queries, nq, mode, k, cutoff, metric, alpha, beta, hits, count, approx, stats);
+    });
 }
 
 } // extern "C"

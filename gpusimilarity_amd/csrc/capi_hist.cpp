@@ -4,7 +4,6 @@
 #include "capi_front.h"
 #include "gsim_prefilter.h"
 
-#include <chrono>
 
 namespace gsim_host
 {
@@ -83,7 +82,7 @@ struct HistCall {
 int histogram(gsim_db* db, Shard& s, const LeftSide& ls, const HistCall& c)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    auto wall = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    auto wall = [&] { return ms_since(t0); };
     const uint64_t N = s.nrows, nl = ls.nl;
     const uint32_t nb = c.nedges + 1;
     gsim_hist_stats hs{};

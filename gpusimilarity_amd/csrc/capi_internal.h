@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -274,6 +275,12 @@ inline uint32_t next_pow2_u32(uint64_t x)
     uint64_t p = 1;
     while (p < x) p <<= 1;
     return p > 0x80000000ull ? 0x80000000u : static_cast<uint32_t>(p);
+}
+
+// milliseconds since t0: the wall time a call's stats report
+inline double ms_since(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 inline uint32_t popcount_words(const uint32_t* q, uint32_t W)

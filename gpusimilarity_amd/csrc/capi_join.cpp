@@ -4,8 +4,6 @@
 // is stated in include/gpusim_hip.h.
 #include "capi_front.h"
 
-#include <chrono>
-
 namespace gsim_host
 {
 
@@ -42,7 +40,7 @@ int join(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, float cutof
     g->kind = gsim_graph::Kind::kJoin;
     g->indptr.assign(nl + 1, 0);
     if (nl == 0 || N == 0) {
-        g->join.wall_ms = g->stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g->join.wall_ms = g->stats.wall_ms = ms_since(t0);
         return GSIM_OK;
     }
     GSIM_HIP(set_device(s.device));
@@ -142,7 +140,7 @@ int join(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, float cutof
     if (rc != GSIM_OK) return rc;
     g->join.csr_ms = g->stats.csr_ms;
     g->join.d2h_ms = g->stats.d2h_ms;
-    g->join.wall_ms = g->stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    g->join.wall_ms = g->stats.wall_ms = ms_since(t0);
     return GSIM_OK;
 }
 

@@ -3,8 +3,6 @@
 // gsim_knn.hip (the fold kernel, offsets, compaction).  The rule is stated in include/gpusim_hip.h.
 #include "capi_front.h"
 
-#include <chrono>
-
 namespace gsim_host
 {
 namespace
@@ -19,9 +17,8 @@ int knn(gsim_db* db, Shard& s, uint32_t k, float cutoff, int metric, float alpha
     g->kind = gsim_graph::Kind::kKnn;
     g->knn.rows = nout;
     g->indptr.assign(nout + 1, 0);
-    auto wall = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
     if (nout == 0 || N < 2) {
-        g->knn.wall_ms = g->stats.wall_ms = wall();
+        g->knn.wall_ms = g->stats.wall_ms = ms_since(t0);
         return GSIM_OK;
     }
     GSIM_HIP(set_device(s.device));
@@ -88,7 +85,7 @@ int knn(gsim_db* db, Shard& s, uint32_t k, float cutoff, int metric, float alpha
     ks.csr_ms = csr.csr_ms;
     ks.d2h_ms = csr.d2h_ms;
     ks.clock_mhz = clocks.mhz();
-    ks.wall_ms = wall();
+    ks.wall_ms = ms_since(t0);
     mirror_graph_stats(ks, ks.launches, ks.kernel_ms, &g->stats);
     return GSIM_OK;
 }
@@ -111,12 +108,11 @@ int gsim_db_knn(gsim_db* db, uint32_t k, float cutoff, int metric, float alpha, 
     if (row_begin > row_end || row_end > db->nrows) return fail(GSIM_ERR_INVALID, "row range outside the table");
     if (db->fp_bits > 4096 || gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, "knn: rows wider than 4096 bits");
     if (db->nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "knn: tables of 2^32 rows or more");
-    if (!db->finalized) return fail(GSIM_ERR_STATE, "table not finalized (no rows on a GPU)");
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, "knn needs a single-shard handle");
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, "knn does not support folded tables");
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    return make_graph(out, "host memory for the k-nearest-neighbour lists",
-                      [&](gsim_graph* g) { return knn(db, db->shards[0], k, cutoff, metric, alpha, beta, row_begin, row_end, g); });
+    if (const int rc = check_table_state(db, "knn", false)) return rc;
+    const char* nomem = "host memory for the k-nearest-neighbour lists";
+    return on_one_shard(db, nomem, [&](Shard& s) {
+        return make_graph(out, nomem, [&](gsim_graph* g) { return knn(db, s, k, cutoff, metric, alpha, beta, row_begin, row_end, g); });
+    });
 }
 
 } // extern "C"

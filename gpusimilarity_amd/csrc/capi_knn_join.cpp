@@ -5,8 +5,6 @@
 // in include/gpusim_hip.h.
 #include "capi_front.h"
 
-#include <chrono>
-
 namespace gsim_host
 {
 
@@ -85,7 +83,7 @@ int knn_join(gsim_db* db, Shard& s, const LeftSide& ls, const KnnJoinCall& c, gs
     ks.left_rows = nl;
     ks.table_rows = N;
     g->indptr.assign(nl + 1, 0);
-    auto wall = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    auto wall = [&] { return ms_since(t0); };
     if (nl == 0 || N == 0) {
         ks.wall_ms = g->stats.wall_ms = wall();
         return GSIM_OK;

@@ -4,8 +4,6 @@
 // side is gsim_assign.hip and gsim_labels.hip.  The rules are stated in include/gpusim_hip.h; DESIGN.md section 21 has the routes.
 #include "capi_front.h"
 
-#include <chrono>
-
 namespace gsim_host
 {
 namespace
@@ -21,11 +19,6 @@ constexpr uint64_t kAssignSlabRows = 1ull << 20;
 static_assert(kAssignSlabRows % gsim::kScoresTile == 0, "slabs are whole row blocks");
 // Bytes of table rows one launch of the counting kernel reads at most (GSIM_LABELS_LAUNCH_ROWS = 0): as capi_profile.cpp
 constexpr uint64_t kLabelsLaunchBytes = (256ull << 20) * 128ull;
-
-double ms_since(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 
 // table rows of one assign launch: whole row blocks within the pair budget, at least one
 uint64_t assign_launch_rows(const gsim_db* db, uint32_t m, uint32_t WP)
@@ -174,8 +167,7 @@ int label_counts_device(gsim_db* db, Shard& s, const uint32_t* h_labels, uint32_
 // ---- what the entry points check before any device state ----
 int check_range(const gsim_db* db, uint64_t row_begin, uint64_t row_end, const char* what)
 {
-    if (row_begin > row_end) return fail(GSIM_ERR_INVALID, "row range: begin past end");
-    if (row_end > db->nrows) return fail(GSIM_ERR_INVALID, "row range outside the table");
+    if (const int rc = check_row_range(db, row_begin, row_end)) return rc;
     if (db->nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, std::string(what) + ": tables of 2^32 rows or more");
     if (db->fp_bits > 4096) return fail(GSIM_ERR_INVALID, std::string(what) + " supports rows of up to 4096 bits");
     return GSIM_OK;
@@ -187,14 +179,6 @@ int check_assign_args(const gsim_db* db, uint32_t m, uint64_t row_begin, uint64_
     if (m == 0 || m > GSIM_ASSIGN_MAX_CENTRES) return fail(GSIM_ERR_INVALID, "assign: the number of centres must be 1 ... GSIM_ASSIGN_MAX_CENTRES");
     if (const int rc = check_metric("assign", metric, alpha, beta)) return rc;
     return check_range(db, row_begin, row_end, "assign");
-}
-
-int check_state(const gsim_db* db, const char* what)
-{
-    if (!db->finalized) return fail(GSIM_ERR_STATE, "table not finalized (no rows on a GPU)");
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, std::string(what) + " does not support folded tables");
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, std::string(what) + " needs a single-shard handle");
-    return GSIM_OK;
 }
 
 int assign(gsim_db* db, Shard& s, const uint32_t* centres, uint32_t m, const AssignCall& c, uint32_t* label, float* score, gsim_assign_stats* stats)
@@ -337,19 +321,16 @@ int gsim_db_assign(gsim_db* db, const uint32_t* centres, uint32_t m, uint64_t ro
     int rc = check_assign_args(db, m, row_begin, row_end, metric, alpha, beta);
     if (rc != GSIM_OK) return rc;
     if (row_begin < row_end && (!centres || !label)) return fail(GSIM_ERR_INVALID, "assign: NULL centres or label");
-    rc = check_state(db, "assign");
+    rc = check_table_state(db, "assign", false);
     if (rc != GSIM_OK) return rc;
     if (stats) {
         *stats = gsim_assign_stats{};
         stats->centres = m;
     }
     if (row_begin == row_end) return GSIM_OK;
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    try {
-        return assign(db, db->shards[0], centres, m, AssignCall{row_begin, row_end - row_begin, metric, alpha, beta}, label, score, stats);
-    } catch (const std::bad_alloc&) {
-        return fail(GSIM_ERR_NOMEM, "host memory for the assignment");
-    }
+    return on_one_shard(db, "host memory for the assignment", [&](Shard& s) {
+        return assign(db, s, centres, m, AssignCall{row_begin, row_end - row_begin, metric, alpha, beta}, label, score, stats);
+    });
 }
 
 int gsim_db_label_counts(gsim_db* db, const uint32_t* labels, uint32_t nlabels, uint64_t row_begin, uint64_t row_end, uint32_t* counts, uint32_t* sizes,
@@ -365,7 +346,7 @@ int gsim_db_label_counts(gsim_db* db, const uint32_t* labels, uint32_t nlabels, 
         if (labels[i] >= nlabels && labels[i] != GSIM_LABEL_NONE)
             return fail(GSIM_ERR_INVALID, "label counts: the label of row " + std::to_string(row_begin + i) + " is not below nlabels");
     if (db->nrows != 0) { // (an empty table has nothing to read: zeros)
-        rc = check_state(db, "label counts");
+        rc = check_table_state(db, "label counts", false);
         if (rc != GSIM_OK) return rc;
     }
     if (stats) {
@@ -377,12 +358,8 @@ int gsim_db_label_counts(gsim_db* db, const uint32_t* labels, uint32_t nlabels, 
         if (sizes) std::fill(sizes, sizes + nlabels, 0u);
         return GSIM_OK;
     }
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    try {
-        return label_counts(db, db->shards[0], labels, nlabels, row_begin, row_end, counts, sizes, stats);
-    } catch (const std::bad_alloc&) {
-        return fail(GSIM_ERR_NOMEM, "host memory for the label counts");
-    }
+    return on_one_shard(db, "host memory for the label counts",
+                        [&](Shard& s) { return label_counts(db, s, labels, nlabels, row_begin, row_end, counts, sizes, stats); });
 }
 
 int gsim_label_centroids(const uint32_t* counts, const uint32_t* sizes, uint32_t nlabels, uint32_t fp_bits, const uint32_t* previous, uint32_t* centres)
@@ -419,15 +396,12 @@ int gsim_db_kmeans(gsim_db* db, const uint32_t* init, uint32_t m, uint32_t max_i
     if (rc != GSIM_OK) return rc;
     if (max_iter == 0) return fail(GSIM_ERR_INVALID, "k-means: max_iter == 0");
     if (!init || !centres || (db->nrows && !label)) return fail(GSIM_ERR_INVALID, "k-means: NULL init, centres or label");
-    rc = check_state(db, "k-means");
+    rc = check_table_state(db, "k-means", false);
     if (rc != GSIM_OK) return rc;
     if (db->nrows == 0) return fail(GSIM_ERR_STATE, "k-means: the table has no rows");
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    try {
-        return kmeans(db, db->shards[0], init, m, max_iter, metric, alpha, beta, centres, label, score, sizes, stats);
-    } catch (const std::bad_alloc&) {
-        return fail(GSIM_ERR_NOMEM, "host memory for k-means");
-    }
+    return on_one_shard(db, "host memory for k-means", [&](Shard& s) {
+        return kmeans(db, s, init, m, max_iter, metric, alpha, beta, centres, label, score, sizes, stats);
+    });
 }
 
 } // extern "C"

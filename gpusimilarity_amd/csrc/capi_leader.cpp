@@ -1,11 +1,9 @@
 // capi_leader.cpp -- gsim_db_leader: leader (sphere-exclusion) clustering in rounds of candidates.  The argument checks and the
 // launch sequence of a call; the device side is gsim_leader.hip (resolve, pass, compaction).  The rule is stated in
 // include/gpusim_hip.h.
-#include "capi_internal.h"
+#include "capi_front.h"
 
-#include <chrono>
 #include <cmath>
-#include <unordered_set>
 
 namespace gsim_host
 {
@@ -170,7 +168,7 @@ int leader(gsim_db* db, Shard& s, float cutoff, const uint32_t* seeds, uint32_t 
         st->resolve_ms = resolve_ms;
         st->compact_ms = compact_ms;
         st->d2h_ms = ev_d2h.ms();
-        st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        st->wall_ms = ms_since(t0);
     }
     return GSIM_OK;
 }
@@ -189,41 +187,18 @@ int gsim_db_leader(gsim_db* db, float cutoff, const uint32_t* seeds, uint32_t ns
     if (!db || !leaders || !nleaders) return fail(GSIM_ERR_INVALID, "NULL argument");
     *nleaders = 0;
     if (!(cutoff > 0.0f && cutoff <= 1.0f)) return fail(GSIM_ERR_INVALID, "leader: the cutoff must be in (0, 1]");
-    if (metric != GSIM_METRIC_TANIMOTO && metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
-    if (metric == GSIM_METRIC_TVERSKY && !(alpha == beta))
-        return fail(GSIM_ERR_INVALID, "leader needs a symmetric metric (Tversky with alpha == beta)");
-    if (metric == GSIM_METRIC_TVERSKY && !(std::isfinite(alpha) && alpha >= 0.0f))
-        return fail(GSIM_ERR_INVALID, "leader: Tversky alpha = beta must be finite and >= 0");
+    if (const int rc = check_symmetric_metric("leader needs", "leader", metric, alpha, beta)) return rc;
     const uint64_t N = db->nrows;
     if (N > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "leader: tables of 2^32 rows or more");
     if (db->fp_bits > 4096) return fail(GSIM_ERR_INVALID, "leader: rows wider than 4096 bits");
-    if (nseeds && !seeds) return fail(GSIM_ERR_INVALID, "NULL seeds");
     if (N == 0 && nseeds == 0) return GSIM_OK;
     if (max_leaders < 1 || max_leaders < nseeds || max_leaders > N)
         return fail(GSIM_ERR_INVALID, "leader: max_leaders must be at least 1, at least the number of seeds and at most the number of rows");
-    try {
-        std::unordered_set<uint32_t> seen;
-        for (uint32_t j = 0; j < nseeds; j++) {
-            if (seeds[j] < db->row_base || static_cast<uint64_t>(seeds[j]) >= db->row_base + N)
-                return fail(GSIM_ERR_INVALID, "seed row outside the table");
-            if (!seen.insert(seeds[j]).second) return fail(GSIM_ERR_INVALID, "repeated seed row");
-        }
-    } catch (const std::bad_alloc&) {
-        return fail(GSIM_ERR_NOMEM, "leader seeds");
-    }
-    if (!db->finalized) return fail(GSIM_ERR_STATE, "table not finalized (no rows on a GPU)");
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, "leader clustering does not support folded tables");
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, "leader clustering needs a single-shard handle");
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    Shard& s = db->shards[0];
-    int rc;
-    try {
-        rc = leader(db, s, cutoff, seeds, nseeds, max_leaders, metric, alpha, beta, leaders, nleaders, leader_of, row_score, stats);
-    } catch (const std::bad_alloc&) {
-        rc = fail(GSIM_ERR_NOMEM, "host memory for leader clustering");
-    }
-    if (rc != GSIM_OK) s.state_dirty = true; // (launches of the call may have failed mid-stream: the next enqueue re-zeroes the search state)
-    return rc;
+    if (const int rc = check_seeds(db, seeds, nseeds, "leader seeds")) return rc;
+    if (const int rc = check_table_state(db, "leader clustering", false)) return rc;
+    return on_one_shard(db, "host memory for leader clustering", [&](Shard& s) {
+        return leader(db, s, cutoff, seeds, nseeds, max_leaders, metric, alpha, beta, leaders, nleaders, leader_of, row_score, stats);
+    });
 }
 
 } // extern "C"

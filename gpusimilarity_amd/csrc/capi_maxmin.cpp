@@ -1,10 +1,8 @@
 // capi_maxmin.cpp -- gsim_db_maxmin: MaxMin diversity picking, one pass over the table per pick.  The device side is
 // gsim_maxmin.hip; the rule is stated in include/gpusim_hip.h.
-#include "capi_internal.h"
+#include "capi_front.h"
 
-#include <chrono>
 #include <cmath>
-#include <unordered_set>
 
 namespace gsim_host
 {
@@ -158,7 +156,7 @@ int maxmin(gsim_db* db, Shard& s, uint32_t npicks, const uint32_t* seeds, uint32
         st->rows_updated = upd;
         st->kernel_ms = ev_k.ms();
         st->d2h_ms = ev_d2h.ms();
-        st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        st->wall_ms = ms_since(t0);
     }
     return GSIM_OK;
 }
@@ -177,38 +175,18 @@ int gsim_db_maxmin(gsim_db* db, uint32_t npicks, const uint32_t* seeds, uint32_t
     if (!db || !picks || !npicked) return fail(GSIM_ERR_INVALID, "NULL argument");
     *npicked = 0;
     if (stats) *stats = gsim_maxmin_stats{};
-    if (metric != GSIM_METRIC_TANIMOTO && metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
-    if (metric == GSIM_METRIC_TVERSKY && !(alpha == beta))
-        return fail(GSIM_ERR_INVALID, "maxmin needs a symmetric metric (Tversky with alpha == beta)");
-    if (metric == GSIM_METRIC_TVERSKY && !(std::isfinite(alpha) && alpha >= 0.0f))
-        return fail(GSIM_ERR_INVALID, "maxmin: Tversky alpha = beta must be finite and >= 0");
+    if (const int rc = check_symmetric_metric("maxmin needs", "maxmin", metric, alpha, beta)) return rc;
     if (!(max_score >= 0.0f && max_score <= 1.0f)) return fail(GSIM_ERR_INVALID, "max_score must be in [0, 1]");
     const uint64_t N = db->nrows;
     if (N > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "maxmin: tables of 2^32 rows or more");
     if (npicks > N) return fail(GSIM_ERR_INVALID, "npicks exceeds the number of rows");
     if (nseeds > npicks) return fail(GSIM_ERR_INVALID, "more seeds than picks");
-    if (nseeds && !seeds) return fail(GSIM_ERR_INVALID, "NULL seeds");
-    try {
-        std::unordered_set<uint32_t> seen;
-        for (uint32_t j = 0; j < nseeds; j++) {
-            if (seeds[j] < db->row_base || static_cast<uint64_t>(seeds[j]) >= db->row_base + N)
-                return fail(GSIM_ERR_INVALID, "seed row outside the table");
-            if (!seen.insert(seeds[j]).second) return fail(GSIM_ERR_INVALID, "repeated seed row");
-        }
-    } catch (const std::bad_alloc&) {
-        return fail(GSIM_ERR_NOMEM, "maxmin seeds");
-    }
-    if (!db->finalized) return fail(GSIM_ERR_STATE, "table not finalized (no rows on a GPU)");
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, "maxmin does not support folded tables");
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, "maxmin needs a single-shard handle");
+    if (const int rc = check_seeds(db, seeds, nseeds, "maxmin seeds")) return rc;
+    if (const int rc = check_table_state(db, "maxmin", false)) return rc;
     if (npicks == 0) return GSIM_OK;
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    try {
-        return maxmin(db, db->shards[0], npicks, seeds, nseeds, metric, alpha, beta, max_score, picks, pick_scores, npicked, row_score,
-                      nearest, stats);
-    } catch (const std::bad_alloc&) {
-        return fail(GSIM_ERR_NOMEM, "host memory for maxmin");
-    }
+    return on_one_shard(db, "host memory for maxmin", [&](Shard& s) {
+        return maxmin(db, s, npicks, seeds, nseeds, metric, alpha, beta, max_score, picks, pick_scores, npicked, row_score, nearest, stats);
+    });
 }
 
 } // extern "C"

@@ -2,10 +2,9 @@
 // Boruvka rounds on the device) and its host companions gsim_mst (the same rule on a scored CSR graph), gsim_mst_linkage and
 // gsim_mst_cut.  The argument checks and the round loop of a call; the device side is gsim_mst.hip.  The rule is stated in
 // include/gpusim_hip.h.
-#include "capi_pairs.h"
+#include "capi_front.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 
 namespace gsim_host
@@ -28,10 +27,9 @@ int mst(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, float beta
 {
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t N = s.nrows;
-    auto wall = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
     if (st) st->rows = N;
     if (N < 2) {
-        if (st) st->wall_ms = wall();
+        if (st) st->wall_ms = ms_since(t0);
         return GSIM_OK;
     }
     const uint32_t WP = gsim::nbr_padded_words(s.W);
@@ -163,36 +161,11 @@ int mst(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, float beta
         ms.sort_ms = ev_sort.ms();
         ms.d2h_ms = ev_d2h.ms();
         ms.clock_mhz = clocks.mhz();
-        ms.wall_ms = wall();
+        ms.wall_ms = ms_since(t0);
         *st = ms;
     }
     return GSIM_OK;
 }
-
-// union-find over rows for the host functions: `root` with path halving
-struct Forest {
-    std::vector<uint32_t> parent;
-    explicit Forest(uint64_t n) : parent(n)
-    {
-        for (uint64_t r = 0; r < n; r++) parent[r] = static_cast<uint32_t>(r);
-    }
-    uint32_t root(uint32_t x)
-    {
-        while (parent[x] != x) {
-            parent[x] = parent[parent[x]];
-            x = parent[x];
-        }
-        return x;
-    }
-    // the smaller index wins every hook, so a tree's root is its smallest row
-    bool unite(uint32_t a, uint32_t b)
-    {
-        const uint32_t x = root(a), y = root(b);
-        if (x == y) return false;
-        parent[std::max(x, y)] = std::min(x, y);
-        return true;
-    }
-};
 
 bool before_in_e(const gsim_mst_edge& x, const gsim_mst_edge& y)
 {
@@ -225,46 +198,28 @@ int gsim_db_mst(gsim_db* db, float cutoff, int metric, float alpha, float beta, 
     if (nedges) *nedges = 0;
     if (!db || !nedges) return fail(GSIM_ERR_INVALID, "NULL argument");
     if (!(cutoff > 0.0f && cutoff <= 1.0f)) return fail(GSIM_ERR_INVALID, "mst: the cutoff must be in (0, 1]");
-    if (metric != GSIM_METRIC_TANIMOTO && metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
-    if (metric == GSIM_METRIC_TVERSKY && !(alpha == beta))
-        return fail(GSIM_ERR_INVALID, "mst needs a symmetric metric (Tversky with alpha == beta)");
-    if (metric == GSIM_METRIC_TVERSKY && !(std::isfinite(alpha) && alpha >= 0.0f))
-        return fail(GSIM_ERR_INVALID, "mst: Tversky alpha = beta must be finite and >= 0");
+    if (const int rc = check_symmetric_metric("mst needs", "mst", metric, alpha, beta)) return rc;
     if (db->fp_bits > 4096 || gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, "mst: rows wider than 4096 bits");
     const uint64_t N = db->nrows;
     if (N > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "mst: tables of 2^32 rows or more");
     if (N > 1 && !edges) return fail(GSIM_ERR_INVALID, "NULL edges");
     if (N == 0) return GSIM_OK;
-    if (!db->finalized) return fail(GSIM_ERR_STATE, "table not finalized (no rows on a GPU)");
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, "mst does not support folded tables");
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, "mst needs a single-shard handle");
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    Shard& s = db->shards[0];
-    int rc;
-    try {
-        rc = mst(db, s, cutoff, metric, alpha, beta, edges, nedges, stats);
-    } catch (const std::bad_alloc&) {
-        rc = fail(GSIM_ERR_NOMEM, "host memory for the spanning forest");
-    }
-    if (rc != GSIM_OK) s.state_dirty = true; // (launches of the call may have failed mid-stream: the next enqueue re-zeroes the search state)
-    return rc;
+    if (const int rc = check_table_state(db, "mst", false)) return rc;
+    return on_one_shard(db, "host memory for the spanning forest",
+                        [&](Shard& s) { return mst(db, s, cutoff, metric, alpha, beta, edges, nedges, stats); });
 }
 
 int gsim_mst(const uint64_t* indptr, const uint32_t* indices, const float* scores, uint64_t nrows, gsim_mst_edge* edges, uint64_t* nedges)
 {
     if (nedges) *nedges = 0;
     if (!indptr || !nedges) return fail(GSIM_ERR_INVALID, "NULL argument");
-    if (nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "more than 2^32-1 rows");
-    if (indptr[0] != 0) return fail(GSIM_ERR_INVALID, "indptr[0] must be 0");
-    for (uint64_t r = 0; r < nrows; r++)
-        if (indptr[r + 1] < indptr[r]) return fail(GSIM_ERR_INVALID, "indptr must not decrease");
-    const uint64_t nnz = indptr[nrows];
+    uint64_t nnz = 0;
+    if (const int rc = check_csr_offsets(indptr, nrows, &nnz)) return rc;
     if (nnz && (!indices || !scores)) return fail(GSIM_ERR_INVALID, "NULL indices or scores");
     if (nrows > 1 && !edges) return fail(GSIM_ERR_INVALID, "NULL edges");
-    for (uint64_t e = 0; e < nnz; e++) {
-        if (indices[e] >= nrows) return fail(GSIM_ERR_INVALID, "column index outside the graph");
+    if (const int rc = check_csr_indices(indices, nnz, nrows)) return rc;
+    for (uint64_t e = 0; e < nnz; e++)
         if (std::isnan(scores[e])) return fail(GSIM_ERR_INVALID, "mst: an edge with a NaN score");
-    }
     try {
         // every listed pair once per listing, as a < b; Kruskal skips what it has seen
         std::vector<gsim_mst_edge> all;
@@ -325,21 +280,7 @@ int gsim_mst_cut(const gsim_mst_edge* edges, uint64_t nedges, uint64_t nrows, fl
         Forest f(nrows);
         for (uint64_t e = 0; e < nedges; e++)
             if (edges[e].score >= t) f.unite(edges[e].a, edges[e].b);
-        // rows ascending: a root comes before every other row of its component and takes the next number
-        uint32_t nc = 0;
-        for (uint64_t r = 0; r < nrows; r++) {
-            const uint32_t root = f.root(static_cast<uint32_t>(r));
-            if (root == r) {
-                component_of[r] = nc;
-                if (first_row) first_row[nc] = static_cast<uint32_t>(r);
-                if (sizes) sizes[nc] = 1;
-                nc++;
-            } else {
-                component_of[r] = component_of[root];
-                if (sizes) sizes[component_of[root]]++;
-            }
-        }
-        *ncomponents = nc;
+        *ncomponents = number_components(f, nrows, component_of, first_row, sizes);
     } catch (const std::bad_alloc&) {
         return fail(GSIM_ERR_NOMEM, "mst");
     }

@@ -2,7 +2,6 @@
 // clustering of such a graph, host code).  The device side is gsim_neighbors.hip.
 #include "capi_front.h"
 
-#include <chrono>
 #include <numeric>
 
 namespace gsim_host
@@ -19,7 +18,7 @@ int neighbors(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, floa
     const bool tri = rb == 0 && re == N;
     g->indptr.assign(nout + 1, 0);
     if (nout == 0 || N < 2) {
-        g->stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g->stats.wall_ms = ms_since(t0);
         return GSIM_OK;
     }
     GSIM_HIP(set_device(s.device));
@@ -74,7 +73,7 @@ int neighbors(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, floa
     g->stats.clock_mhz = clocks.mhz();
     const int rc2 = build_pair_csr(db, s, total, nout, GSIM_JOIN_BY_ROW, g);
     if (rc2 != GSIM_OK) return rc2;
-    g->stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    g->stats.wall_ms = ms_since(t0);
     return GSIM_OK;
 }
 
@@ -91,31 +90,24 @@ int gsim_db_neighbors(gsim_db* db, float cutoff, int metric, float alpha, float 
     if (!db || !out) return fail(GSIM_ERR_INVALID, "NULL argument");
     *out = nullptr;
     if (!(cutoff > 0.0f && cutoff <= 1.0f)) return fail(GSIM_ERR_INVALID, "neighbour cutoff must be in (0, 1]");
-    if (metric != GSIM_METRIC_TANIMOTO && metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
-    if (metric == GSIM_METRIC_TVERSKY && !(alpha == beta))
-        return fail(GSIM_ERR_INVALID, "neighbour lists need a symmetric metric (Tversky with alpha == beta)");
+    // (no prefix: alpha == beta is not checked for finiteness here -- a known quirk)
+    if (const int rc = check_symmetric_metric("neighbour lists need", nullptr, metric, alpha, beta)) return rc;
     if (gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, "neighbour lists support rows of up to 4096 bits");
     if (row_begin > row_end || row_end > db->nrows) return fail(GSIM_ERR_INVALID, "row range outside the table");
-    if (!db->finalized) return fail(GSIM_ERR_STATE, "table not finalized (no rows on a GPU)");
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, "neighbour lists do not support folded tables");
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, "neighbour lists need a single-shard handle");
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    return make_graph(out, "host memory for the neighbour lists",
-                      [&](gsim_graph* g) { return neighbors(db, db->shards[0], cutoff, metric, alpha, beta, row_begin, row_end, g); });
+    if (const int rc = check_table_state(db, "neighbour lists", true)) return rc;
+    const char* nomem = "host memory for the neighbour lists";
+    return on_one_shard(db, nomem, [&](Shard& s) {
+        return make_graph(out, nomem, [&](gsim_graph* g) { return neighbors(db, s, cutoff, metric, alpha, beta, row_begin, row_end, g); });
+    });
 }
 
 int gsim_butina(const uint64_t* indptr, const uint32_t* indices, uint64_t nrows, uint32_t* cluster_of, uint32_t* centroids,
                 uint64_t* nclusters)
 {
     if (!indptr || !cluster_of || !centroids || !nclusters) return fail(GSIM_ERR_INVALID, "NULL argument");
-    if (nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "more than 2^32-1 rows");
-    if (indptr[0] != 0) return fail(GSIM_ERR_INVALID, "indptr[0] must be 0");
-    for (uint64_t r = 0; r < nrows; r++)
-        if (indptr[r + 1] < indptr[r]) return fail(GSIM_ERR_INVALID, "indptr must not decrease");
-    const uint64_t nnz = indptr[nrows];
-    if (nnz && !indices) return fail(GSIM_ERR_INVALID, "NULL indices");
-    for (uint64_t e = 0; e < nnz; e++)
-        if (indices[e] >= nrows) return fail(GSIM_ERR_INVALID, "column index outside the graph");
+    uint64_t nnz = 0;
+    if (const int rc = check_csr_offsets(indptr, nrows, &nnz)) return rc;
+    if (const int rc = check_csr_indices(indices, nnz, nrows)) return rc;
     try {
         // candidates: (neighbour count desc, row desc)
         std::vector<uint32_t> order(nrows);

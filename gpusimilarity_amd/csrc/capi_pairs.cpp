@@ -229,6 +229,43 @@ int build_knn_csr(gsim_db* db, Shard& s, const gsim::KnnEntry* lists, const uint
     return GSIM_OK;
 }
 
+int check_csr_offsets(const uint64_t* indptr, uint64_t nrows, uint64_t* nnz)
+{
+    if (nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "more than 2^32-1 rows");
+    if (indptr[0] != 0) return fail(GSIM_ERR_INVALID, "indptr[0] must be 0");
+    for (uint64_t r = 0; r < nrows; r++)
+        if (indptr[r + 1] < indptr[r]) return fail(GSIM_ERR_INVALID, "indptr must not decrease");
+    *nnz = indptr[nrows];
+    return GSIM_OK;
+}
+
+int check_csr_indices(const uint32_t* indices, uint64_t nnz, uint64_t nrows)
+{
+    if (nnz && !indices) return fail(GSIM_ERR_INVALID, "NULL indices");
+    for (uint64_t e = 0; e < nnz; e++)
+        if (indices[e] >= nrows) return fail(GSIM_ERR_INVALID, "column index outside the graph");
+    return GSIM_OK;
+}
+
+uint32_t number_components(Forest& f, uint64_t nrows, uint32_t* component_of, uint32_t* first_row, uint32_t* sizes)
+{
+    // rows ascending: a root comes before every other row of its component and takes the next number
+    uint32_t nc = 0;
+    for (uint64_t r = 0; r < nrows; r++) {
+        const uint32_t root = f.root(static_cast<uint32_t>(r));
+        if (root == r) {
+            component_of[r] = nc;
+            if (first_row) first_row[nc] = static_cast<uint32_t>(r);
+            if (sizes) sizes[nc] = 1;
+            nc++;
+        } else {
+            component_of[r] = component_of[root];
+            if (sizes) sizes[component_of[root]]++;
+        }
+    }
+    return nc;
+}
+
 } // namespace gsim_host
 
 using namespace gsim_host;

@@ -1,7 +1,8 @@
 // capi_pairs.h -- what gsim_db_neighbors (capi_neighbors.cpp) and the threshold joins (capi_join.cpp) share: the result
 // object, the handle's pair buffer with its overflow / exact-regrow protocol, the tile kernel's launch plan, and the CSR
 // build; and what the k-NN calls (capi_knn.cpp, capi_knn_join.cpp, capi_mst.cpp) share: the fold launches' plan and the CSR
-// build of their lists.  Implemented in capi_pairs.cpp (the k-NN plan: capi_knn_join.cpp).  Internal.
+// build of their lists; and what the host functions on a caller's graph share: the CSR checks, the union-find forest and the
+// numbering of its trees.  Implemented in capi_pairs.cpp (the k-NN plan: capi_knn_join.cpp).  Internal.
 #pragma once
 
 #include "capi_internal.h"
@@ -100,5 +101,40 @@ template <class Stats> void mirror_graph_stats(const Stats& ks, uint64_t launche
     gs->clock_mhz = ks.clock_mhz;
     gs->wall_ms = ks.wall_ms;
 }
+
+// ---- the host functions on a caller's graph (gsim_butina, gsim_components, gsim_mst, gsim_mst_linkage, gsim_mst_cut) ----
+
+// INVALID "more than 2^32-1 rows", "indptr[0] must be 0", "indptr must not decrease"; *nnz = indptr[nrows]
+int check_csr_offsets(const uint64_t* indptr, uint64_t nrows, uint64_t* nnz);
+// INVALID "NULL indices" when nnz > 0, "column index outside the graph"
+int check_csr_indices(const uint32_t* indices, uint64_t nnz, uint64_t nrows);
+
+// union-find over rows: `root` with path halving
+struct Forest {
+    std::vector<uint32_t> parent;
+    explicit Forest(uint64_t n) : parent(n)
+    {
+        for (uint64_t r = 0; r < n; r++) parent[r] = static_cast<uint32_t>(r);
+    }
+    uint32_t root(uint32_t x)
+    {
+        while (parent[x] != x) {
+            parent[x] = parent[parent[x]];
+            x = parent[x];
+        }
+        return x;
+    }
+    // the smaller index wins every hook, so a tree's root is its smallest row
+    bool unite(uint32_t a, uint32_t b)
+    {
+        const uint32_t x = root(a), y = root(b);
+        if (x == y) return false;
+        parent[std::max(x, y)] = std::min(x, y);
+        return true;
+    }
+};
+// The trees of f numbered by ascending first row: component_of [nrows], and per component (where not NULL) first_row and sizes.
+// Returns the number of components.
+uint32_t number_components(Forest& f, uint64_t nrows, uint32_t* component_of, uint32_t* first_row, uint32_t* sizes);
 
 } // namespace gsim_host

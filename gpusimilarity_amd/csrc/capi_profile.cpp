@@ -2,9 +2,7 @@
 // set), gsim_db_overlap_sums (every row's weighted popcount) and their host companions gsim_isim / gsim_isim_complement (the iSIM
 // index of a set from its column counts, and of the set without each row).  The argument checks, the launch cuts and the copies of a
 // call; the device side is gsim_profile.hip.  The rules are stated in include/gpusim_hip.h.
-#include "capi_internal.h"
-
-#include <chrono>
+#include "capi_front.h"
 
 namespace gsim_host
 {
@@ -20,16 +18,10 @@ uint64_t launch_rows(const gsim_db* db, uint32_t W)
     return std::max<uint64_t>(knob > 0 ? knob : kProfileLaunchBytes / (static_cast<uint64_t>(W) * 4u), 1);
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // what both device calls check after their own arguments, in this order
 int check_profile_handle(const gsim_db* db, uint64_t row_begin, uint64_t row_end)
 {
-    if (row_begin > row_end) return fail(GSIM_ERR_INVALID, "row range: begin past end");
-    if (row_end > db->nrows) return fail(GSIM_ERR_INVALID, "row range outside the table");
+    if (const int rc = check_row_range(db, row_begin, row_end)) return rc;
     if (db->nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "column counts: tables of 2^32 rows or more");
     if (db->fp_bits > 4096) return fail(GSIM_ERR_INVALID, "column counts support rows of up to 4096 bits");
     return GSIM_OK;
@@ -37,11 +29,7 @@ int check_profile_handle(const gsim_db* db, uint64_t row_begin, uint64_t row_end
 
 int check_profile_state(const gsim_db* db)
 {
-    if (db->nrows == 0) return GSIM_OK; // (nothing to read: zeros)
-    if (!db->finalized) return fail(GSIM_ERR_STATE, "table not finalized (no rows on a GPU)");
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, "column counts do not support folded tables");
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, "column counts need a single-shard handle");
-    return GSIM_OK;
+    return db->nrows == 0 ? GSIM_OK : check_table_state(db, "column counts", true); // (an empty table has nothing to read: zeros)
 }
 
 int bit_counts(gsim_db* db, Shard& s, const gsim_rowset* rs, uint64_t rb, uint64_t re, uint64_t* counts, uint64_t* counted, gsim_profile_stats* st)
@@ -236,12 +224,8 @@ int gsim_db_bit_counts(gsim_db* db, const gsim_rowset* rs, uint64_t row_begin, u
         std::fill(counts, counts + db->fp_bits, uint64_t{0});
         return GSIM_OK;
     }
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    try {
-        return bit_counts(db, db->shards[0], rs, row_begin, row_end, counts, counted, stats);
-    } catch (const std::bad_alloc&) {
-        return fail(GSIM_ERR_NOMEM, "host memory for the column counts");
-    }
+    return on_one_shard(db, "host memory for the column counts",
+                        [&](Shard& s) { return bit_counts(db, s, rs, row_begin, row_end, counts, counted, stats); });
 }
 
 int gsim_db_overlap_sums(gsim_db* db, const uint32_t* weights, uint64_t row_begin, uint64_t row_end, uint64_t* sums, uint32_t* popc,
@@ -255,12 +239,8 @@ int gsim_db_overlap_sums(gsim_db* db, const uint32_t* weights, uint64_t row_begi
     rc = check_profile_state(db);
     if (rc != GSIM_OK) return rc;
     if (db->nrows == 0) return GSIM_OK;
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    try {
-        return overlap_sums(db, db->shards[0], weights, row_begin, row_end, sums, popc, stats);
-    } catch (const std::bad_alloc&) {
-        return fail(GSIM_ERR_NOMEM, "host memory for the overlap sums");
-    }
+    return on_one_shard(db, "host memory for the overlap sums",
+                        [&](Shard& s) { return overlap_sums(db, s, weights, row_begin, row_end, sums, popc, stats); });
 }
 
 int gsim_isim(const uint64_t* counts, uint32_t fp_bits, uint64_t n, int index, double* value)

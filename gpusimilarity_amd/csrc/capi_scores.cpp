@@ -4,8 +4,6 @@
 // of the host-output calls.  The device side is gsim_scores.hip.  The rule is stated in include/gpusim_hip.h.
 #include "capi_front.h"
 
-#include <chrono>
-
 namespace gsim_host
 {
 namespace
@@ -54,7 +52,7 @@ struct ScoresCall {
 int scores(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, const ScoresCall& c)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    auto wall = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    auto wall = [&] { return ms_since(t0); };
     const uint64_t nr = c.nr;
     gsim_scores_stats ss{};
     ss.left_rows = nl;

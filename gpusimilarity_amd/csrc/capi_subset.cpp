@@ -2,9 +2,7 @@
 // row-set lifecycle, the argument checks and the route choice per call; the device side is gsim_subset.hip (the two scans, the
 // kernels that build a set) and the four-kernel pipeline's own tail (capi_query.cpp enqueue_scan_tail).  The rule is stated in
 // include/gpusim_hip.h.
-#include "capi_internal.h"
-
-#include <chrono>
+#include "capi_front.h"
 
 namespace gsim_host
 {
@@ -15,10 +13,7 @@ namespace
 int check_rowset_state(const gsim_db* db)
 {
     if (db->nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "row sets: tables of 2^32 rows or more");
-    if (!db->finalized) return fail(GSIM_ERR_STATE, "table not finalized (no rows on a GPU)");
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, "row sets do not support folded tables");
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, "row sets need a single-shard handle");
-    return GSIM_OK;
+    return check_table_state(db, "row sets", true);
 }
 
 // The set on the device: `rows` marked into a zeroed bitmap, or the caller's `bits`; inverted for an exclusion set; then the list.
@@ -135,7 +130,7 @@ int search_rows(gsim_db* db, Shard& s, const gsim_rowset* rs, const uint32_t* qu
             counts[q] = 0;
             if (approx) approx[q] = 0;
         }
-        if (st) st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (st) st->wall_ms = ms_since(t0);
         return GSIM_OK;
     }
     GSIM_HIP(set_device(s.device));
@@ -178,7 +173,7 @@ int search_rows(gsim_db* db, Shard& s, const gsim_rowset* rs, const uint32_t* qu
             (gather ? st->queries_gather : st->queries_stream) += 1;
         }
     }
-    if (st) st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (st) st->wall_ms = ms_since(t0);
     return GSIM_OK;
 }
 
@@ -247,20 +242,11 @@ int gsim_db_search_rows(gsim_db* db, const gsim_rowset* rs, const uint32_t* quer
     if (!db || !rs || !queries || !hits || !counts) return fail(GSIM_ERR_INVALID, "NULL argument");
     if (metric != GSIM_METRIC_TANIMOTO && metric != GSIM_METRIC_TVERSKY) return fail(GSIM_ERR_INVALID, "unknown metric");
     if (rs->owner != db) return fail(GSIM_ERR_INVALID, "the row set was made for another handle");
-    if (!db->finalized) return fail(GSIM_ERR_STATE, "table not finalized (no rows on a GPU)");
-    if (db->fold > 1) return fail(GSIM_ERR_STATE, "row-set searches do not support folded tables");
-    if (db->shards.size() != 1) return fail(GSIM_ERR_STATE, "row-set searches need a single-shard handle");
+    if (const int rc = check_table_state(db, "row-set searches", true)) return rc;
     if (rs->nrows != db->nrows) return fail(GSIM_ERR_STATE, "the table changed after the row set was made");
-    std::lock_guard<std::mutex> guard(db->search_mutex);
-    Shard& s = db->shards[0];
-    int rc;
-    try {
-        rc = search_rows(db, s, rs, queries, nq, k, cutoff, metric, alpha, beta, hits, counts, approx, stats);
-    } catch (const std::bad_alloc&) {
-        rc = fail(GSIM_ERR_NOMEM, "host memory for a row-set search");
-    }
-    if (rc != GSIM_OK) s.state_dirty = true; // (the per-query state may not be zero: re-zeroed before the next enqueue)
-    return rc;
+    return on_one_shard(db, "host memory for a row-set search", [&](Shard& s) {
+        return search_rows(db, s, rs, queries, nq, k, cutoff, metric, alpha, beta, hits, counts, approx, stats);
+    });
 }
 
 } // extern "C"

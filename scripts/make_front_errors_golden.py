@@ -1,10 +1,17 @@
 #!/usr/bin/env python3
-"""Records tests/golden/front_errors.json: the return code, the gsim_last_error() text and whether `*out` was cleared, for every case
-of tests/front_errors_cases.py -- the argument and state errors of the two-table fronts and gsim_db_knn on tables that are not on a
-GPU.  Needs no GPU.  Run it on a build of the commit whose behaviour is to be kept (GSIM_LIB names another build of the library),
-never on the code under test: tests/test_front_errors_host.py replays the list and demands equality.
+"""Records a golden file of front errors: the return code, the gsim_last_error() text and what became of the outputs, for every case
+of a case list -- the argument and state errors of the fronts on tables that are not on a GPU.  Needs no GPU.  Two lists:
 
-  GSIM_LIB=/path/to/parent/libgsim_hip.so python scripts/make_front_errors_golden.py"""
+  two-table  tests/front_errors_cases.py -> tests/golden/front_errors.json (the two-table fronts and gsim_db_knn;
+             replayed by tests/test_front_errors_host.py)
+  single     tests/single_front_errors_cases.py -> tests/golden/single_front_errors.json (the single-table fronts and the host
+             functions on a caller's CSR graph; replayed by tests/test_single_front_errors_host.py)
+
+Run it on a build of the commit whose behaviour is to be kept (GSIM_LIB names another build of the library), never on the code
+under test: the tests replay the list and demand equality.
+
+  GSIM_LIB=/path/to/parent/libgsim_hip.so python scripts/make_front_errors_golden.py [two-table|single]"""
+import importlib
 import json
 import os
 import sys
@@ -12,11 +19,15 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
-from front_errors_cases import run_all  # noqa: E402
+LISTS = {"two-table": ("front_errors_cases", "front_errors.json"), "single": ("single_front_errors_cases", "single_front_errors.json")}
 
 if __name__ == "__main__":
-    got = run_all()
-    path = os.path.join(ROOT, "tests", "golden", "front_errors.json")
+    which = sys.argv[1] if len(sys.argv) > 1 else "two-table"
+    if which not in LISTS:
+        sys.exit("usage: make_front_errors_golden.py [%s]" % "|".join(LISTS))
+    module, name = LISTS[which]
+    got = importlib.import_module(module).run_all()
+    path = os.path.join(ROOT, "tests", "golden", name)
     with open(path, "w") as f:
         json.dump(got, f, indent=0, sort_keys=True, allow_nan=False)
         f.write("\n")
