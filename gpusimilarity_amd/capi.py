@@ -114,6 +114,16 @@ class GsimComponentsStats(C.Structure):
                 ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
 
 
+DBSCAN_NOISE = 0xFFFFFFFF
+
+
+class GsimDbscanStats(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("launches_count", C.c_uint64), ("launches_link", C.c_uint64), ("pairs", C.c_uint64),
+                ("kept", C.c_uint64), ("cores", C.c_uint64), ("borders", C.c_uint64), ("noise", C.c_uint64), ("clusters", C.c_uint64),
+                ("unions", C.c_uint64), ("cas_failed", C.c_uint64), ("count_ms", C.c_double), ("link_ms", C.c_double),
+                ("label_ms", C.c_double), ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
+
+
 MST_MAX_ROUNDS = 33
 MST_EDGE_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("score", np.float32)])
 MST_MERGE_DTYPE = np.dtype([("left", np.uint32), ("right", np.uint32), ("score", np.float32), ("size", np.uint32)])
@@ -185,6 +195,7 @@ EXPORTS = [
     "gsim_db_scores", "gsim_db_scores_queries", "gsim_db_scores_device",
     "gsim_db_components", "gsim_components",
     "gsim_db_mst", "gsim_mst", "gsim_mst_linkage", "gsim_mst_cut",
+    "gsim_db_dbscan", "gsim_dbscan",
     "gsim_db_bit_counts", "gsim_db_overlap_sums", "gsim_isim", "gsim_isim_complement",
     "gsim_db_assign", "gsim_db_label_counts", "gsim_label_centroids", "gsim_db_kmeans",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
@@ -305,6 +316,9 @@ def load():
         "gsim_components": (C.c_int, [u64p, u32p, C.c_uint64, u32p, u32p, u32p, u64p]),
         "gsim_db_mst": (C.c_int, [vp, C.c_float, C.c_int, C.c_float, C.c_float, vp, u64p, C.POINTER(GsimMstStats)]),
         "gsim_mst": (C.c_int, [u64p, u32p, C.POINTER(C.c_float), C.c_uint64, vp, u64p]),
+        "gsim_db_dbscan": (C.c_int, [vp, C.c_float, C.c_uint32, C.c_int, C.c_float, C.c_float, u32p, u32p, u32p, u32p, u32p, u32p,
+                                     C.POINTER(GsimDbscanStats)]),
+        "gsim_dbscan": (C.c_int, [u64p, u32p, C.POINTER(C.c_float), C.c_uint64, C.c_uint32, u32p, u32p, u32p, u32p, u64p]),
         "gsim_mst_linkage": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp]),
         "gsim_mst_cut": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_float, u32p, u32p, u32p, u64p]),
         "gsim_db_bit_counts": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, u64p, u64p, C.POINTER(GsimProfileStats)]),
@@ -728,6 +742,25 @@ class Table:
         stats["scan_kernel_ms"] = list(st.scan_kernel_ms)[:st.scans]
         return edges[:ne.value].copy(), stats
 
+    def dbscan(self, cutoff, min_pts, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, degree=True, anchor=True, first_row=True, sizes=True):
+        """gsim_db_dbscan: DBSCAN density clustering -> (label_of uint32 [N] (DBSCAN_NOISE for noise), degree uint32 [N], anchor uint32
+        [N] (+ row base; DBSCAN_NOISE for noise), first_row uint32 [nclusters] (+ row base), sizes uint32 [nclusters], stats dict);
+        degree / anchor / first_row / sizes are None where not asked for.  A row is a core when degree + 1 >= min_pts; clusters are
+        the cores' connected components; a border row joins the cluster of its best-scoring core neighbour (ties: the smallest row)."""
+        n = self.count()
+        label_of = np.empty(n, dtype=np.uint32)
+        ncl = C.c_uint32(0)
+        deg = np.empty(n, dtype=np.uint32) if degree else None
+        anc = np.empty(n, dtype=np.uint32) if anchor else None
+        first = np.empty(max(n, 1), dtype=np.uint32) if first_row else None
+        size = np.empty(max(n, 1), dtype=np.uint32) if sizes else None
+        st = GsimDbscanStats()
+        check(self._L.gsim_db_dbscan(self._h, cutoff, min_pts, metric, alpha, beta, _u32(label_of), C.byref(ncl), _u32(deg) if degree else None,
+                                     _u32(anc) if anchor else None, _u32(first) if first_row else None, _u32(size) if sizes else None,
+                                     C.byref(st)))
+        return (label_of, deg, anc, first[:ncl.value].copy() if first_row else None, size[:ncl.value].copy() if sizes else None,
+                {f: getattr(st, f) for f, _ in GsimDbscanStats._fields_})
+
     def bit_counts(self, rowset=None, row_begin=0, row_end=None, stats=None):
         """gsim_db_bit_counts: how many of the counted rows have each bit set -> (counts uint64 [fp_bits], counted int).  The counted
         rows are the rows of [row_begin, row_end) (indices without the row base) that are in `rowset` (a :class:`RowSet` of this
@@ -1002,6 +1035,25 @@ def mst(indptr, indices, scores, nrows=None):
     check(load().gsim_mst(indptr.ctypes.data_as(C.POINTER(C.c_uint64)), _u32(indices), scores.ctypes.data_as(C.POINTER(C.c_float)), n,
                           edges.ctypes.data, C.byref(ne)))
     return edges[:ne.value].copy()
+
+
+def dbscan(indptr, indices, scores, min_pts, nrows=None):
+    """gsim_dbscan (host code): the rule of gsim_db_dbscan on a symmetric scored CSR graph (Table.neighbors' output) -> (label_of uint32
+    [n], anchor uint32 [n], first_row uint32 [nclusters], sizes uint32 [nclusters]); rows without any row base, DBSCAN_NOISE for noise."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.uint64)
+    indices = np.ascontiguousarray(indices, dtype=np.uint32)
+    scores = np.ascontiguousarray(scores, dtype=np.float32)
+    n = len(indptr) - 1 if nrows is None else int(nrows)
+    if n < 0 or len(indptr) < n + 1 or len(scores) != len(indices):
+        raise GsimError(-1, "indptr needs nrows + 1 entries, scores one per index")
+    label_of = np.empty(n, dtype=np.uint32)
+    anchor = np.empty(n, dtype=np.uint32)
+    first_row = np.empty(max(n, 1), dtype=np.uint32)
+    sizes = np.empty(max(n, 1), dtype=np.uint32)
+    nc = C.c_uint64(0)
+    check(load().gsim_dbscan(indptr.ctypes.data_as(C.POINTER(C.c_uint64)), _u32(indices), scores.ctypes.data_as(C.POINTER(C.c_float)), n,
+                             min_pts, _u32(label_of), _u32(anchor), _u32(first_row), _u32(sizes), C.byref(nc)))
+    return label_of, anchor, first_row[:nc.value].copy(), sizes[:nc.value].copy()
 
 
 def mst_linkage(edges, nrows):

@@ -82,6 +82,8 @@ gsim::Knobs read_knobs()
     if (const char* v = std::getenv("GSIM_SCORES_LAUNCH_PAIRS")) k.scores_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
     if (const char* v = std::getenv("GSIM_SCORES_STAGE_BYTES")) k.scores_stage_bytes = std::max(std::atoll(v), 1ll);   // (at least one row anyway)
     if (const char* v = std::getenv("GSIM_COMPONENTS_LAUNCH_PAIRS")) k.components_launch_pairs = std::max(std::atoll(v), 0ll); // (0: the neighbour lists' plan)
+    if (const char* v = std::getenv("GSIM_DBSCAN_LAUNCH_PAIRS")) k.dbscan_launch_pairs = std::max(std::atoll(v), 0ll); // (0: the neighbour lists' plan)
+    if (const char* v = std::getenv("GSIM_DBSCAN_SKIP")) k.dbscan_skip = std::atoi(v) != 0;
     if (const char* v = std::getenv("GSIM_MST_LAUNCH_PAIRS")) k.mst_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
     if (const char* v = std::getenv("GSIM_PROFILE_LAUNCH_ROWS")) k.profile_launch_rows = std::max(std::atoll(v), 0ll); // (0: 32 GiB of rows)
     if (const char* v = std::getenv("GSIM_ASSIGN_LAUNCH_PAIRS")) k.assign_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)

@@ -45,6 +45,7 @@
 
 #include "../../include/gpusim_hip.h"
 #include "gsim_device_common.h"
+#include "gsim_forest.h"
 #include "gsim_held_row.h"
 #include "gsim_prefilter.h"
 
@@ -53,57 +54,10 @@ namespace gsim
 namespace
 {
 
-__device__ __forceinline__ uint32_t parent_load(const uint32_t* p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 __global__ __launch_bounds__(256) void comp_init_kernel(uint32_t* __restrict__ parent, u64 nrows, u64 total)
 {
     const u64 t = static_cast<u64>(blockIdx.x) * 256u + threadIdx.x;
     if (t < total) parent[t] = static_cast<uint32_t>(t % nrows);
-}
-
-// Unites the components of a and b (members of them) in one forest; returns the root both belong to afterwards as this lane saw
-// it.  Invariants 2 to 5 of the head comment.
-__device__ __forceinline__ uint32_t comp_unite(uint32_t* parent, uint32_t a, uint32_t b, uint32_t& hooks, uint32_t& lost)
-{
-    for (;;) {
-        if (a == b) return a;
-        if (a < b) {
-            const uint32_t x = a;
-            a = b;
-            b = x;
-        }
-        // a > b: climb from a
-        const uint32_t pa = parent_load(parent + a);
-        if (pa != a) {
-            a = pa;
-            continue;
-        }
-        const uint32_t pb = parent_load(parent + b);
-        if (pb != b) {
-            b = pb;
-            continue;
-        }
-        const uint32_t old = atomicCAS(parent + a, a, b);
-        if (old == a) {
-            hooks++;
-            return b;
-        }
-        lost++;
-        a = old;
-    }
-}
-
-__device__ __forceinline__ uint32_t wave_min(uint32_t x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t y = static_cast<uint32_t>(__shfl_xor(static_cast<int>(x), off, 64));
-        x = y < x ? y : x;
-    }
-    return x;
 }
 
 template <int WP, int L> __global__ __launch_bounds__(kNbrBlock) void comp_tile_kernel(CompArgs a, uint32_t rt0, uint32_t ct0)

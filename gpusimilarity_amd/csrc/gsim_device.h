@@ -231,6 +231,11 @@ struct Knobs {
     long long components_launch_pairs = 0; // GSIM_COMPONENTS_LAUNCH_PAIRS  a launch of gsim_db_components' tile kernel scores at most this
                                      // many pairs (at least one 256 x 256 tile); 0: the neighbour lists' launch plan (capi_pairs.cpp;
                                      // DESIGN.md section 18).  The result does not depend on it
+    long long dbscan_launch_pairs = 0; // GSIM_DBSCAN_LAUNCH_PAIRS  a launch of either of gsim_db_dbscan's tile kernels scores at most this many
+                                     // pairs (at least one 256 x 256 tile); 0: the neighbour lists' launch plan (capi_pairs.cpp;
+                                     // DESIGN.md section 26).  The result does not depend on it
+    int dbscan_skip = 1;             // GSIM_DBSCAN_SKIP         0: the link pass scores every left row, even one that can matter to no
+                                     // lane of the wave (for timing; the result does not depend on it)
     long long mst_launch_pairs = 0;  // GSIM_MST_LAUNCH_PAIRS    a launch of gsim_db_mst's fold kernel scores at most this many owner x candidate
                                      // pairs (at least one column tile of 256 candidates); 0: as knn_launch_pairs (capi_mst.cpp;
                                      // DESIGN.md section 19).  The result does not depend on it
@@ -435,6 +440,34 @@ hipError_t comp_scan_bytes(uint64_t nrows, size_t* bytes);
 hipError_t launch_comp_label(void* tmp, size_t tmp_bytes, const uint32_t* parent, uint64_t nrows, uint32_t row_base, uint32_t* flag,
                              uint32_t* num, uint32_t* component_of, uint32_t* first_row, uint32_t* sizes, uint32_t* ncomponents,
                              hipStream_t s);
+
+// ---- DBSCAN density clustering (gsim_dbscan.hip, gsim_db_dbscan) -----------------------------------------------------------
+constexpr uint32_t kDbscanKept = 0, kDbscanUnions = 1, kDbscanCasFailed = 2, kDbscanCores = 3, kDbscanBorders = 4, kDbscanNoise = 5,
+                   kDbscanDegreeSum = 6, kDbscanCounters = 7; // DbscanArgs::counters
+struct DbscanArgs {
+    const uint32_t* rows;        // nrows x WP words, 16-byte aligned (the table itself when W == WP, else a zero-padded copy)
+    const uint32_t* pop;         // popc of every row
+    uint64_t nrows;
+    uint32_t WP;                 // words per row as the kernels read them (4, 8, ... 128)
+    int metric;
+    float alpha, beta;
+    float cutoff;
+    uint32_t min_pts;            // >= 1; row x is a core iff degree[x] + 1 >= min_pts
+    uint32_t skip;               // link pass: 1 = a wave passes over a non-core left row when it holds no core (Knobs::dbscan_skip)
+    uint32_t* degree;            // nrows words, zeroed before the degree pass, which adds to them; the link pass reads them
+    uint32_t* parent;            // one forest of nrows words over ALL rows (the protocol: gsim_components.hip); only cores are united
+    unsigned long long* best;    // nrows words, zeroed before the link pass: key(score, ~core row) of a non-core row's anchor, 0: none
+    unsigned long long* counters; // kDbscanCounters words, added to
+    unsigned long long* clk;     // as NbrArgs::clk
+};
+// tiles (rt0 .. rt0+nrt-1) x (ct0 .. ct0+nct-1) of the upper triangle, as launch_comp_tiles: the degree pass, and the link pass (each
+// launch of which launch_comp_flatten follows)
+hipError_t launch_dbscan_count(const DbscanArgs& a, uint32_t rt0, uint32_t nrt, uint32_t ct0, uint32_t nct, hipStream_t s);
+hipError_t launch_dbscan_link(const DbscanArgs& a, uint32_t rt0, uint32_t nrt, uint32_t ct0, uint32_t nct, hipStream_t s);
+// the flattened forest, the degrees and best[] -> label_of[nrows], *nclusters, the census in a.counters, anchor / first_row / sizes (or
+// nullptr; sizes zeroed before) -- flag, num: nrows words of scratch each, tmp: comp_scan_bytes
+hipError_t launch_dbscan_label(void* tmp, size_t tmp_bytes, const DbscanArgs& a, uint32_t row_base, uint32_t* flag, uint32_t* num,
+                               uint32_t* label_of, uint32_t* anchor, uint32_t* first_row, uint32_t* sizes, uint32_t* nclusters, hipStream_t s);
 
 // ---- exact k-nearest-neighbour lists of the table's own rows (gsim_knn.hip, gsim_db_knn) ----------------------------------
 constexpr int kKnnTile = 256;   // owner rows of one workgroup

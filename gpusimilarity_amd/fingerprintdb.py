@@ -181,6 +181,22 @@ class FingerprintDB:
                 members[j].append(r)
         return leaders, [(p,) + tuple(m) for p, m in zip(leaders, members)]
 
+    def dbscan(self, cutoff: float, min_pts: int, metric: int = capi.METRIC_TANIMOTO, alpha: float = 1.0, beta: float = 1.0):
+        """DBSCAN density clustering (gsim_db_dbscan) -> (clusters, noise): one tuple per cluster, in ascending order of its smallest
+        core row -- that row first, then the other members (cores and border rows), ascending (the shape of butina()); `noise` is the
+        list of the rows in no cluster.  A row is a core when it and its neighbours at `cutoff` are at least `min_pts` rows."""
+        label_of, _, _, first_row, _, _ = self._table.dbscan(float(cutoff), int(min_pts), metric, alpha, beta, degree=False, anchor=False,
+                                                             sizes=False)
+        first = first_row.tolist()
+        members = [[] for _ in first]
+        noise = []
+        for r, c in enumerate(label_of.tolist()):
+            if c == capi.DBSCAN_NOISE:
+                noise.append(r)
+            elif r != first[c]:
+                members[c].append(r)
+        return [(f,) + tuple(m) for f, m in zip(first, members)], noise
+
     def search_cpu(self, query, dbkey: str, max_return_count: int, similarity_cutoff: float
                    ) -> Tuple[List[bytes], List[bytes], List[float]]:
         """fingerprintdb_cuda.cpp:20-54 (cutoff ignored, approx not produced)."""

@@ -958,6 +958,73 @@ int gsim_mst_linkage(const gsim_mst_edge* edges, uint64_t nedges, uint64_t nrows
 int gsim_mst_cut(const gsim_mst_edge* edges, uint64_t nedges, uint64_t nrows, float t,
                  uint32_t* component_of, uint32_t* first_row /* or NULL */, uint32_t* sizes /* or NULL */, uint64_t* ncomponents);
 
+/* ---- DBSCAN density clustering ---------------------------------------------------------------------------------------------------- */
+/* gsim_db_dbscan clusters a single-shard, unfolded handle with N rows by density (DBSCAN: Ester, Kriegel, Sander, Xu, KDD 1996; no
+ * counterpart in the reference): the one clustering here that names noise, and the standard remedy where single linkage chains through
+ * sparse bridges.  None of the graph "score >= cutoff" is stored: two passes over the pairs, the first counts every row's neighbours,
+ * the second unites the dense rows in a union-find forest in device memory and attaches the others.  Memory is O(N).
+ * THE RULE:
+ *   - score: score(i, j) is bit for bit the `score` gsim_db_search returns; NaN (0 / 0) is never >= cutoff.  Metrics: gsim_db_components'
+ *     -- GSIM_METRIC_TANIMOTO, and GSIM_METRIC_TVERSKY with alpha == beta, finite and >= 0 (symmetric bit for bit).  cutoff in (0, 1];
+ *     rows of at most 4096 bits, N < 2^32;
+ *   - degree: degree(i) is the number of rows j != i with score(i, j) >= cutoff;
+ *   - core: row i is a core iff degree(i) + 1 >= min_pts -- the row counts itself (scikit-learn's min_samples).  min_pts >= 1;
+ *     min_pts == 1 makes every row a core, all-zero rows included;
+ *   - clusters: the connected components of the graph on the CORE rows whose edges are the pairs with score >= cutoff, numbered 0, 1,
+ *     ... in ascending order of their smallest core row;
+ *   - border: a non-core row with at least one core neighbour is a border row and joins the cluster of its ANCHOR: the core neighbour
+ *     with the highest score, among equal scores the smallest row -- the order gsim_db_mst's kernel encodes as (score bits << 32) | ~row.
+ *     Textbook DBSCAN leaves this to the visit order; here it is fixed, so the output is a function of the table;
+ *   - noise: every other row; label_of = GSIM_DBSCAN_NOISE;
+ *   - outputs: label_of[N] the cluster number or GSIM_DBSCAN_NOISE (no row base); *nclusters their count; degree[N] (or NULL) the
+ *     degrees; anchor[N] (or NULL) -- a core: its own row, a border row: its anchor, both plus the handle's row base, noise:
+ *     GSIM_DBSCAN_NOISE; first_row[c] (or NULL) cluster c's smallest core row plus the row base; sizes[c] (or NULL) its cores plus its
+ *     border rows.  The first *nclusters entries of first_row and sizes are written, the rest are left untouched.
+ * Consequences: the output is byte-identical from run to run and does not depend on how the passes are cut into launches
+ * (GSIM_DBSCAN_LAUNCH_PAIRS, read once per handle); with min_pts == 1, label_of, first_row and sizes equal
+ * gsim_db_components' at that cutoff byte for byte; the result equals gsim_dbscan applied to gsim_db_neighbors(cutoff)'s CSR; restricted
+ * to the core rows, the partition is the one gsim_components gives on the core-induced subgraph.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / label_of / nclusters, a cutoff outside (0, 1] or NaN, min_pts == 0, an
+ * unknown metric, asymmetric weights or weights that are negative or not finite, rows wider than 4096 bits, N >= 2^32.  N == 0:
+ * GSIM_OK, *nclusters = 0.  GSIM_ERR_STATE: a table not on a GPU, a multi-shard handle, a folded table; degrees that do not add up to
+ * twice the kept pairs, hooks other than cores - clusters, or cores + borders + noise other than N (none can happen).  GSIM_ERR_NOMEM as
+ * elsewhere, nothing leaked.
+ * Execution: on the handle's stream under the one-call-at-a-time rule; the search state is left as it was found.  Device memory of the
+ * call, allocated and freed by it: 28 B x N (4 B of degree, 4 B of forest, 8 B of anchor key, 4 B of label_of and 8 B of label
+ * scratch per row), 4 B x N more for each of anchor / first_row / sizes asked for, 4 B x N for popcounts, the zero-padded copy of the
+ * rows where their width is not 128, 256, ... 4096 bits (as the neighbour lists), and the scan's scratch. */
+#define GSIM_DBSCAN_NOISE 0xFFFFFFFFu
+typedef struct {
+    uint64_t rows;           /* N                                                                                              */
+    uint64_t launches_count; /* launches of the degree pass's tile kernel                                                      */
+    uint64_t launches_link;  /* launches of the link pass's tile kernel (each followed by one of the flatten kernel)           */
+    uint64_t pairs;          /* pairs scored by EACH pass: N (N - 1) / 2                                                       */
+    uint64_t kept;           /* pairs with score >= cutoff, counted in the degree pass: the sum of the degrees is twice this   */
+    uint64_t cores;          /* rows with degree + 1 >= min_pts                                                                */
+    uint64_t borders;        /* non-core rows with a core neighbour                                                            */
+    uint64_t noise;          /* the others: cores + borders + noise = N                                                        */
+    uint64_t clusters;       /* *nclusters                                                                                     */
+    uint64_t unions;         /* successful hooks = cores - clusters                                                            */
+    uint64_t cas_failed;     /* diagnostic, NOT reproducible: compare-and-swaps that lost a race                               */
+    double count_ms;         /* HIP events on the handle's stream: the degree pass                                             */
+    double link_ms;          /* ... the link pass, its flatten launches included                                               */
+    double label_ms;         /* ... numbering, label_of, anchor, first_row and sizes, on the device                            */
+    double d2h_ms;           /* outputs to the host                                                                            */
+    double wall_ms;          /* the whole call, host clock                                                                     */
+    double clock_mhz;        /* as gsim_graph_stats.clock_mhz, over the launches of both passes                                */
+} gsim_dbscan_stats;
+int gsim_db_dbscan(gsim_db* db, float cutoff, uint32_t min_pts, int metric, float alpha, float beta,
+                   uint32_t* label_of /* N */, uint32_t* nclusters, uint32_t* degree /* N, or NULL */, uint32_t* anchor /* N, or NULL */,
+                   uint32_t* first_row /* N, or NULL */, uint32_t* sizes /* N, or NULL */, gsim_dbscan_stats* stats /* or NULL */);
+/* The same rule on a symmetric scored CSR graph (host code, no device; gsim_components' and gsim_mst's companion), e.g.
+ * gsim_db_neighbors' output: degree(i) is the length of row i's list, self edges not counted; a core's own row, a border row's anchor
+ * and first_row carry no row base.  label_of / anchor (or NULL): nrows; first_row / sizes (or NULL): capacity nrows, the first
+ * *nclusters entries written.  GSIM_ERR_INVALID for a malformed graph (gsim_components' checks), a NaN score or min_pts == 0;
+ * nrows == 0 is legal. */
+int gsim_dbscan(const uint64_t* indptr, const uint32_t* indices, const float* scores, uint64_t nrows, uint32_t min_pts,
+                uint32_t* label_of, uint32_t* anchor /* or NULL */, uint32_t* first_row /* or NULL */, uint32_t* sizes /* or NULL */,
+                uint64_t* nclusters);
+
 /* ---- per-bit column counts and iSIM library statistics ---------------------------------------------------------------------------- */
 /* The column-wise questions about a table, a row range or a cluster (a gsim_rowset): how often is each bit set, how tight is the set,
  * which row is its medoid, which rows are outliers.  All of them are O(N) once the per-bit column counts c_k of the set's n rows are
