@@ -10,10 +10,10 @@ int ensure_batch_buffers(gsim_db* db, Shard& s, uint32_t k)
 {
     GSIM_HIP(set_device(s.device));
     if (s.bq_cap == 0 || s.bseg_cap == 0) { // first use -- or a regrow of the segments failed: they start over
-        const int wpc = db->knobs.batch_waves_per_cu;
-        s.bgeo = gsim::scan_geometry(s.nrows, s.W, s.num_cus, wpc, 8, db->knobs.scan_ragged != 0);
+        constexpr int kBatchWavesPerCu = 12; // (the VALU pass's grid)
+        s.bgeo = gsim::scan_geometry(s.nrows, s.W, s.num_cus, kBatchWavesPerCu, 8);
         const uint64_t nchunks = (s.nrows + 63) / 64;
-        uint64_t nw = static_cast<uint64_t>(s.num_cus) * static_cast<uint64_t>(wpc);
+        uint64_t nw = static_cast<uint64_t>(s.num_cus) * static_cast<uint64_t>(kBatchWavesPerCu);
         if (nw > nchunks) nw = nchunks ? nchunks : 1;
         nw = (nw + 3) / 4 * 4;
         s.bgeo.nwaves = static_cast<uint32_t>(nw);
@@ -106,8 +106,8 @@ int enqueue_batch(gsim_db* db, Shard& s, const uint32_t* queries, uint32_t nq, u
     a.metric = metric;
     a.alpha = alpha;
     a.beta = beta;
-    const uint32_t sample = static_cast<uint32_t>(db->knobs.batch_sample_chunks);
-    a.opts = (db->knobs.batch_mfma_sample ? 1u : 0u) | (db->knobs.batch_mfma_dense ? 2u : 0u) | ((static_cast<uint32_t>(db->knobs.batch_rpl) & 255u) << 8);
+    constexpr uint32_t kBatchSampleChunks = 8; // chunks per wave the sample pass scores
+    a.opts = db->knobs.batch_mfma_dense ? 2u : 0u;
     // One contraction pass on the matrix cores for all of them (gsim_batch_mfma.hip: with fewer
     // than 8 x 32 queries the waves of a workgroup share query tiles and split the rows).  With a
     // cutoff it needs the matrix-core sample pass (large tables), which also estimates how many
@@ -128,7 +128,7 @@ int enqueue_batch(gsim_db* db, Shard& s, const uint32_t* queries, uint32_t nq, u
     const int mfma_min_q = db->knobs.batch_mfma_min_q;
     if (allow_mfma && mfma_min_q > 0 && nq >= static_cast<uint32_t>(mfma_min_q) &&
         nq <= static_cast<uint32_t>(gsim::kMfmaQueries) && gsim::batch_mfma_supported(s.W) &&
-        (!(cutoff > 0.0f) || gsim::batch_mfma_sample_applies(s.W, s.nrows, nq, k, s.num_cus, db->knobs.batch_mfma_sample != 0))) {
+        (!(cutoff > 0.0f) || gsim::batch_mfma_sample_applies(s.W, s.nrows, nq, k, s.num_cus))) {
         a.q0 = 0;
         a.nq = nq;
         // the rows' popcounts: once per table; borrowed rows (gsim_db_attach_device_rows) may have changed since the
@@ -139,7 +139,7 @@ int enqueue_batch(gsim_db* db, Shard& s, const uint32_t* queries, uint32_t nq, u
             s.rowpop_valid = true;
         }
         a.rowpop = s.d_rowpop;
-        GSIM_HIP(gsim::launch_batch_mfma_pass(a, s.bgeo, s.num_cus, sample, row_base, results,
+        GSIM_HIP(gsim::launch_batch_mfma_pass(a, s.bgeo, s.num_cus, kBatchSampleChunks, row_base, results,
                                               gsim_result_block_bytes(k), s.stream, bev ? bev[0].h : nullptr,
                                               bev ? bev[1].h : nullptr));
         if (to_host)
@@ -151,7 +151,7 @@ int enqueue_batch(gsim_db* db, Shard& s, const uint32_t* queries, uint32_t nq, u
     for (uint32_t q0 = 0; q0 < nq; q0 += gsim::kBQ) {
         a.q0 = q0;
         a.nq = std::min<uint32_t>(gsim::kBQ, nq - q0);
-        GSIM_HIP(gsim::launch_batch_pass(a, rr, s.bgeo, sample, row_base, results, gsim_result_block_bytes(k),
+        GSIM_HIP(gsim::launch_batch_pass(a, rr, s.bgeo, kBatchSampleChunks, row_base, results, gsim_result_block_bytes(k),
                                          s.stream));
     }
     if (bev) GSIM_HIP(hipEventRecord(bev[1], s.stream));
@@ -329,7 +329,7 @@ int gsim_db_search_batch_device(gsim_db* db, const uint32_t* queries, uint32_t n
     const size_t blk = gsim_result_block_bytes(k);
     unsigned char* out = static_cast<unsigned char*>(d_results);
     const bool batched = nq >= 4 && k <= static_cast<uint32_t>(gsim::kSelectCap) && k > 0 && gsim::batch_supported(db->W) &&
-                         s.nrows > 0 && db->knobs.batch != 0;
+                         s.nrows > 0;
     for (uint32_t base = 0; base < nq; base += kBatchMaxQ) {
         const uint32_t nb = std::min<uint32_t>(kBatchMaxQ, nq - base);
         const uint32_t* qb = queries + static_cast<size_t>(base) * db->W;

@@ -23,6 +23,7 @@
 #include <utility>
 #include <vector>
 
+#include "capi_knobs.h"
 #include "capi_owned.h"
 #include "gsim_device.h"
 #include "gsim_synth.h"
@@ -31,7 +32,6 @@ namespace gsim_host
 {
 
 extern thread_local std::string g_last_error;
-extern thread_local bool g_force_each; // gsim_db_search_each: queries one by one, never a shared table pass
 
 int fail(int code, const std::string& msg);
 int fail_hip(hipError_t e, const char* what);
@@ -47,7 +47,6 @@ int fail_hip(hipError_t e, const char* what);
         if ((buf).grow(bytes) != hipSuccess) return fail(GSIM_ERR_NOMEM, "device memory for " what); \
     } while (0)
 
-gsim::Knobs read_knobs(); // (the one place that calls getenv for tuning knobs; gsim_db_create)
 #ifdef GSIM_TEST_HOOKS
 int env_int(const char* name, int dflt);
 #endif
@@ -112,7 +111,6 @@ struct Shard {
     gsim::ScanGeometry geo{};
     gsim::ScanGeometry fgeo{}; // single-launch path: fewer waves on small tables (every wave gets >= 4 chunks)
     bool state_dirty = false; // set when an enqueue failed: the device state is re-zeroed before the next one
-    int sample_chunks = 4; // chunks per scan wave scored by the sample kernel (0 = off)
     DevBuf<uint32_t> d_query;
     DevBuf<gsim::QueryState> d_state;
     DevBuf<unsigned long long> d_cand;
@@ -244,7 +242,7 @@ struct gsim_db {
     uint32_t fold = 1;                 // effective factor (divides W), fixed at finalize
     bool fold_full_on_device = true;   // gsim_db_set_fold_full_on_device
     uint32_t row_base = 0;
-    gsim::Knobs knobs;                 // the environment's tuning knobs as gsim_db_create found them
+    gsim_host::Knobs knobs;                 // the environment's tuning knobs as gsim_db_create found them
     bool timing = false;
     gsim_timing acc{};
     unsigned long long dense_batches = 0; // multi-query passes whose dense cutoff the matrix-core pass counted itself

@@ -6,7 +6,6 @@ namespace gsim_host
 {
 
 thread_local std::string g_last_error;
-thread_local bool g_force_each = false;
 
 int fail(int code, const std::string& msg)
 {
@@ -20,81 +19,12 @@ int fail_hip(hipError_t e, const char* what)
     return GSIM_ERR_HIP;
 }
 
-namespace
-{
-int env_value(const char* name, int dflt)
+#ifdef GSIM_TEST_HOOKS
+int env_int(const char* name, int dflt)
 {
     const char* v = std::getenv(name);
     if (!v || !*v) return dflt;
     return std::atoi(v);
-}
-} // namespace
-
-gsim::Knobs read_knobs()
-{
-    gsim::Knobs k;
-    k.scan_waves_per_cu = env_value("GSIM_SCAN_WAVES_PER_CU", k.scan_waves_per_cu);
-    k.scan_ragged = env_value("GSIM_SCAN_RAGGED", k.scan_ragged);
-    k.sample_chunks = env_value("GSIM_SAMPLE_CHUNKS", k.sample_chunks);
-    k.sample_shift = env_value("GSIM_SAMPLE_SHIFT", k.sample_shift);
-    k.fused = env_value("GSIM_FUSED", k.fused);
-    if (const char* v = std::getenv("GSIM_FUSED_MAX_ROWS")) k.fused_max_rows = std::atoll(v);
-    k.fused_debug = env_value("GSIM_FUSED_DEBUG", k.fused_debug);
-    k.fused_flags = env_value("GSIM_FUSED_FLAGS", k.fused_flags);
-    k.fused_seed_narrow = env_value("GSIM_FUSED_SEED_NARROW", k.fused_seed_narrow);
-    k.fused_publish = env_value("GSIM_FUSED_PUBLISH", k.fused_publish);
-    k.largek_binrank = env_value("GSIM_LARGEK_BINRANK", k.largek_binrank);
-    k.fused_select_max_k = std::min(std::max(env_value("GSIM_FUSED_SELECT_MAX_K", k.fused_select_max_k), 2048), static_cast<int>(gsim::kFusedMaxK)); // (the large-k sort takes k > 2048)
-    k.largek_one_block_max = env_value("GSIM_LARGEK_ONE_BLOCK_MAX", k.largek_one_block_max);
-    k.fused_backoff = env_value("GSIM_FUSED_BACKOFF", k.fused_backoff);
-    k.publish_narrow = env_value("GSIM_PUBLISH_NARROW", k.publish_narrow);
-    k.largek_binrank_max_k = env_value("GSIM_LARGEK_BINRANK_MAX_K", k.largek_binrank_max_k);
-    k.fused_publish_max_k = std::min(std::max(env_value("GSIM_FUSED_PUBLISH_MAX_K", k.fused_publish_max_k), 2048), static_cast<int>(gsim::kFusedPublishMaxK));
-    k.publish_min_rows_per_k = std::max(env_value("GSIM_PUBLISH_MIN_ROWS_PER_K", k.publish_min_rows_per_k), 0);
-    k.each_pipeline = env_value("GSIM_EACH_PIPELINE", k.each_pipeline);
-    k.each_lanes = env_value("GSIM_EACH_LANES", k.each_lanes);
-    k.each_lanes_share = env_value("GSIM_EACH_LANES_SHARE", k.each_lanes_share);
-    k.each_lanes_publish = env_value("GSIM_EACH_LANES_PUBLISH", k.each_lanes_publish);
-    k.each_lanes_max_mb = env_value("GSIM_EACH_LANES_MAX_MB", k.each_lanes_max_mb);
-    k.batch = env_value("GSIM_BATCH", k.batch);
-    k.batch_waves_per_cu = env_value("GSIM_BATCH_WAVES_PER_CU", k.batch_waves_per_cu);
-    k.batch_seg_cap = env_value("GSIM_BATCH_SEG_CAP", k.batch_seg_cap);
-    k.batch_seg_cap_init = env_value("GSIM_BATCH_SEG_CAP_INIT", k.batch_seg_cap_init);
-    k.batch_sample_chunks = env_value("GSIM_BATCH_SAMPLE_CHUNKS", k.batch_sample_chunks);
-    k.batch_rpl = env_value("GSIM_BATCH_RPL", k.batch_rpl);
-    k.batch_mfma_min_q = env_value("GSIM_BATCH_MFMA_MIN_Q", k.batch_mfma_min_q);
-    k.batch_mfma_sample = env_value("GSIM_BATCH_MFMA_SAMPLE", k.batch_mfma_sample);
-    k.batch_mfma_dense = env_value("GSIM_BATCH_MFMA_DENSE", k.batch_mfma_dense);
-    k.debug_batch = std::getenv("GSIM_DEBUG_BATCH") ? 1 : 0;
-    k.fold_full_on_device = env_value("GSIM_FOLD_FULL_ON_DEVICE", k.fold_full_on_device);
-    if (const char* v = std::getenv("GSIM_FOLD_RESCORE")) k.fold_rescore_host = std::string(v) == "host" ? 1 : 0;
-    k.join_stream_max_rows = env_value("GSIM_JOIN_STREAM_MAX_ROWS", k.join_stream_max_rows);
-    k.subset_gather_max_permille = std::max(env_value("GSIM_SUBSET_GATHER_MAX_PERMILLE", k.subset_gather_max_permille), 0);
-    if (const char* v = std::getenv("GSIM_GROUP_LAUNCH_PAIRS")) k.group_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
-    k.leader_round = std::min(std::max(env_value("GSIM_LEADER_ROUND", k.leader_round), 1), static_cast<int>(gsim::kLeaderMaxRound));
-    if (const char* v = std::getenv("GSIM_LEADER_LAUNCH_PAIRS")) k.leader_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
-    if (const char* v = std::getenv("GSIM_KNN_LAUNCH_PAIRS")) k.knn_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
-    k.knn_join_segments = std::max(env_value("GSIM_KNN_JOIN_SEGMENTS", k.knn_join_segments), 0); // (0: by the owner tiles and the CUs)
-    if (const char* v = std::getenv("GSIM_KNN_JOIN_LAUNCH_PAIRS")) k.knn_join_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
-    k.hist_stream_max_rows = env_value("GSIM_HIST_STREAM_MAX_ROWS", k.hist_stream_max_rows);
-    if (const char* v = std::getenv("GSIM_HIST_LAUNCH_PAIRS")) k.hist_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
-    k.hist_naive_add = env_value("GSIM_HIST_NAIVE_ADD", k.hist_naive_add) ? 1 : 0;
-    if (const char* v = std::getenv("GSIM_SCORES_LAUNCH_PAIRS")) k.scores_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
-    if (const char* v = std::getenv("GSIM_SCORES_STAGE_BYTES")) k.scores_stage_bytes = std::max(std::atoll(v), 1ll);   // (at least one row anyway)
-    if (const char* v = std::getenv("GSIM_COMPONENTS_LAUNCH_PAIRS")) k.components_launch_pairs = std::max(std::atoll(v), 0ll); // (0: the neighbour lists' plan)
-    if (const char* v = std::getenv("GSIM_DBSCAN_LAUNCH_PAIRS")) k.dbscan_launch_pairs = std::max(std::atoll(v), 0ll); // (0: the neighbour lists' plan)
-    if (const char* v = std::getenv("GSIM_DBSCAN_SKIP")) k.dbscan_skip = std::atoi(v) != 0;
-    if (const char* v = std::getenv("GSIM_MST_LAUNCH_PAIRS")) k.mst_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
-    if (const char* v = std::getenv("GSIM_PROFILE_LAUNCH_ROWS")) k.profile_launch_rows = std::max(std::atoll(v), 0ll); // (0: 32 GiB of rows)
-    if (const char* v = std::getenv("GSIM_ASSIGN_LAUNCH_PAIRS")) k.assign_launch_pairs = std::max(std::atoll(v), 0ll); // (0: by the row width)
-    if (const char* v = std::getenv("GSIM_LABELS_LAUNCH_ROWS")) k.labels_launch_rows = std::max(std::atoll(v), 0ll);   // (0: 32 GiB of rows)
-    return k;
-}
-
-#ifdef GSIM_TEST_HOOKS
-int env_int(const char* name, int dflt)
-{
-    return env_value(name, dflt);
 }
 
 int alias_devices()
@@ -130,6 +60,7 @@ int free_shard(Shard& s)
 }
 
 // Allocate the per-shard search scratch once the rows are in place.
+constexpr int kScanWavesPerCu = 4; // (the scan grids: one wave per SIMD)
 int setup_shard(gsim_db* db, Shard& s)
 {
     if (s.nrows > 0x7FFFFFFFull) // candidate / finalist slots are 32-bit indexed, capacity a power of two <= 2^31
@@ -141,12 +72,10 @@ int setup_shard(gsim_db* db, Shard& s)
     if (s.num_cus < 1) s.num_cus = 1;
     GSIM_HIP(s.own_stream.create(hipStreamNonBlocking));
     s.stream = s.own_stream;
-    const gsim::Knobs& kn = db->knobs;
     if (s.W == 0) s.W = db->W;
-    s.geo = gsim::scan_geometry(s.nrows, s.W, s.num_cus, kn.scan_waves_per_cu, 8, kn.scan_ragged != 0);
-    s.sample_chunks = kn.sample_chunks;
+    s.geo = gsim::scan_geometry(s.nrows, s.W, s.num_cus, kScanWavesPerCu, 8);
     s.fgeo = s.geo;
-    (void) gsim::fused_word_geometry(s.nrows, s.W, s.num_cus, &s.fgeo, kn.scan_ragged != 0); // (rows of 3 ... 11 or twice that many words: the single launch's own)
+    (void) gsim::fused_word_geometry(s.nrows, s.W, s.num_cus, &s.fgeo); // (rows of 3 ... 11 or twice that many words: the single launch's own)
     if (s.fgeo.nchunks < 4ull * s.fgeo.nwaves) { // small table: threshold checkpoints need a few trips per wave
         // (narrow rows: a chunk is 512 rows and a wave's LDS store holds 2048 -- three chunks per wave, so that a store
         // cannot fill before the one threshold such a table sees, the one after the loop)
@@ -158,7 +87,7 @@ int setup_shard(gsim_db* db, Shard& s)
     GSIM_HIP(s.d_state.grow(sizeof(gsim::QueryState)));
     GSIM_HIP(hipMemset(s.d_state, 0, sizeof(gsim::QueryState))); // the kernels keep it zero between queries
     // every workgroup of the single launch is a selector and there are at most kFusedSelectors: on a part with more CUs
-    // (or with GSIM_SCAN_WAVES_PER_CU > 4) the grid is clamped -- its waves take more chunks each -- instead of losing the path
+    // the grid is clamped -- its waves take more chunks each -- instead of losing the path
     const uint32_t fused_max_waves = static_cast<uint32_t>(gsim::kFusedSelectors) * (gsim::kScanBlock / 64);
     if (s.fgeo.nwaves > fused_max_waves) s.fgeo.nwaves = fused_max_waves;
     if (gsim::fused_supported(s.fgeo)) {
@@ -430,8 +359,7 @@ int gsim_db_finalize(gsim_db* db, int device, int ndevices)
         // later storages' folded rows and the search scratch were budgeted for.  Per device: the full rows
         // of its storages + 24 B per folded row (the four-kernel pipeline's scratch, allocated on first use) + 2 GB.
         // Without them the re-score runs on the host, as in the reference (fingerprintdb_cuda.cu:307-331).
-        const int full_on_device = db->knobs.fold_full_on_device;
-        bool keep_full = full_on_device != 0 && db->fold_full_on_device && db->nrows > 0;
+        bool keep_full = db->fold_full_on_device && db->nrows > 0;
         if (keep_full) {
             std::vector<size_t> need(static_cast<size_t>(ndev), 0);
             for (const auto& s : db->shards) need[static_cast<size_t>(s.device)] += static_cast<size_t>(s.nrows) * (static_cast<size_t>(db->W) * 4 + 24);

@@ -58,29 +58,33 @@ int ensure_result_capacity(Shard& s, uint32_t k)
 
 bool fused_applies(const gsim_db* db, const Shard& s, uint32_t k)
 {
-    const int enabled = db->knobs.fused;
-    const long long max_rows = db->knobs.fused_max_rows;
-    if (!enabled || k == 0 || k > gsim::kFusedMaxK || s.nrows == 0 || !gsim::fused_supported(s.fgeo)) return false;
+    if (!db->knobs.fused || k == 0 || k > gsim::kFusedMaxK || s.nrows == 0 || !gsim::fused_supported(s.fgeo)) return false;
     // thresholds need >= k summary keys; without them every row is published (tiny tables only)
-    if ((gsim::fused_summary_keys(s.fgeo.nwaves, k) == 0 || gsim::fused_final_keys(s.fgeo.nwaves / 4, k) == 0) && s.nrows > 8192) return false;
-    return max_rows < 0 || s.nrows <= static_cast<uint64_t>(max_rows);
+    return s.nrows <= 8192 || (gsim::fused_summary_keys(s.fgeo.nwaves, k) != 0 && gsim::fused_final_keys(s.fgeo.nwaves / 4, k) != 0);
 }
 
-// k in (fused_select_max_k, kFusedPublishMaxK]: the single launch scans and publishes (kFusedPublishOnly), the large-k kernels
+// Largest k of the publishing route (at most kFusedPublishMaxK; round 5: 32768).  Measured at 100 M rows (profiles/r06_large_k.txt):
+// k = 50 000 2.18 -> 1.93 ms (0.83 of the roofline), 100 000 2.31 -> 2.17; at 131 072 and beyond the waves' stores
+// overflow before the first useful election and the queries are handed back: slower than the four-kernel pipeline
+constexpr uint32_t kPublishMaxK = 100000;
+static_assert(kPublishMaxK <= gsim::kFusedPublishMaxK, "the publishing launch's own limit");
+// Largest k whose published rows are bin-ranked; above it they go through the radix select + sort (measured: 100 M rows, k = 100 000
+// 2.31 ms bin-ranked with hand-backs for crowded bins, 2.11 ms by the radix tail; at k = 50 000 1.94 against 1.97).  128 / 256-bit rows
+// score coarsely: from k ~ 10 000 on a top bin holds more than the emission takes (7 % of the k = 32 768 queries of an 8 M x 128-bit soak
+// were handed back), so their large k takes the radix tail.
+constexpr uint32_t kBinrankMaxK = 65536, kBinrankMaxKNarrow = 8192;
+
+// k in (fused_select_max_k, kPublishMaxK]: the single launch scans and publishes (kFusedPublishOnly), the large-k kernels
 // rank what it published -- from k = 2049, as the selectors' own ranking of thousands of rows is issue-bound.
-// Rows of 512 bits and more unless publish_narrow: the narrow widths want the sampled seed (plan_query).
+// Every width with a register scan: 128 / 256-bit rows are seeded like the ranking launch (plan_query).
 bool fused_publish_applies(const gsim_db* db, const Shard& s, uint32_t k)
 {
-    if (!db->knobs.fused || !db->knobs.fused_publish || k <= static_cast<uint32_t>(db->knobs.fused_select_max_k) || k > static_cast<uint32_t>(db->knobs.fused_publish_max_k) || s.nrows == 0 ||
-        !gsim::fused_supported(s.fgeo))
+    if (!db->knobs.fused || k <= static_cast<uint32_t>(db->knobs.fused_select_max_k) || k > kPublishMaxK || s.nrows == 0 || !gsim::fused_supported(s.fgeo))
         return false;
     if (s.fgeo.ragged_words || s.fgeo.ragged_loads) return false;
-    if (s.fgeo.lanes_per_row < 4 && !db->knobs.publish_narrow) return false; // (128 / 256-bit rows: seeded like the ranking launch, plan_query)
     if (gsim::fused_summary_keys(s.fgeo.nwaves, k, gsim::fused_publish_max_m(k)) == 0) return false; // (no thresholds: every row would be published)
     if (s.nrows < static_cast<uint64_t>(db->knobs.publish_min_rows_per_k) * k) return false; // (a short table: the thresholds come late and most of it is published)
-    if (k > 65536u && s.nrows < 32ull * k) return false; // (measured: 1 M rows, k = 100 000 -- a tenth of the table -- 286 us classic, 303 published)
-    const long long max_rows = db->knobs.fused_max_rows;
-    return max_rows < 0 || s.nrows <= static_cast<uint64_t>(max_rows);
+    return k <= 65536u || s.nrows >= 32ull * k; // (measured: 1 M rows, k = 100 000 -- a tenth of the table -- 286 us classic, 303 published)
 }
 
 namespace
@@ -104,11 +108,8 @@ QueryPlan plan_query(gsim_db* db, Shard& s, uint32_t k, bool caller_syncs, Query
     }
     if (p.route == Route::kPublishRadix && caller_syncs) {
         // The caller reads the block, so a hand-back costs a second run, not a wrong answer: bin-ranked emission (two launches, not
-        // the radix tail's four and a gap).  128 / 256-bit rows score coarsely: from k ~ 10 000 on a top bin holds more than the
-        // emission takes (7 % of the k = 32 768 queries of an 8 M x 128-bit soak were handed back), so their large k takes the radix tail.
-        const uint32_t binrank_max = (s.fgeo.lanes_per_row != 0 && s.fgeo.lanes_per_row <= 2) ? std::min<uint32_t>(8192u, static_cast<uint32_t>(db->knobs.largek_binrank_max_k))
-                                                                                             : static_cast<uint32_t>(db->knobs.largek_binrank_max_k);
-        if (k <= binrank_max) {
+        // the radix tail's four and a gap), up to kBinrankMaxK.
+        if (k <= ((s.fgeo.lanes_per_row != 0 && s.fgeo.lanes_per_row <= 2) ? kBinrankMaxKNarrow : kBinrankMaxK)) {
             if (s.binrank_backoff.take()) p.why |= kQSkipPublish;
             else if (db->knobs.largek_binrank) p.route = Route::kPublishBinrank;
         }
@@ -118,7 +119,7 @@ QueryPlan plan_query(gsim_db* db, Shard& s, uint32_t k, bool caller_syncs, Query
     // sparse tables were handed back (1/64 of the queries at 256 bits, nearly all at 128).  A strided sample first leaves a starting
     // threshold.  (Ragged word counts too: they never take the publishing routes, and every launch route has k > 0.)
     const bool narrow = (s.geo.lanes_per_row != 0 && s.geo.lanes_per_row <= 2) || s.fgeo.ragged_words;
-    p.seed = p.route != Route::kClassic && db->knobs.fused_seed_narrow && narrow && s.nrows > 1500ull * s.fgeo.nwaves && s.sample_chunks > 0;
+    p.seed = p.route != Route::kClassic && narrow && s.nrows > 1500ull * s.fgeo.nwaves;
     return p;
 }
 
@@ -184,7 +185,7 @@ gsim::FusedArgs fused_args(const gsim_db* db, Shard& s, uint32_t k, bool publish
 hipError_t seed_threshold(const QueryLaunch& q, gsim::FusedArgs& f)
 {
     bool seeded = false;
-    const hipError_t e = gsim::launch_sample(q.a, q.s.geo, 1u, q.s.stream, &seeded, q.db->knobs.sample_shift);
+    const hipError_t e = gsim::launch_sample(q.a, q.s.geo, 1u, q.s.stream, &seeded);
     if (seeded) f.xflags |= 4u;
     return e;
 }
@@ -218,13 +219,14 @@ int enqueue_largek_tail(QueryLaunch& q, uint32_t flags)
     return enqueue_largek_tail(q.db, q.s, q.a, q.row_base, q.s.nrows, flags, q.out);
 }
 
-// The four-kernel pipeline: sample -> scan -> compact -> select (`select`) or the large-k tail; gated (a.gate) behind a launch.
+// The four-kernel pipeline: sample (kSampleChunks chunks per scan wave) -> scan -> compact -> select (`select`) or the large-k tail; gated
+// (a.gate) behind a launch.
+constexpr uint32_t kSampleChunks = 4;
 // The kernels read the query from its pinned ring slot (no upload op) and the last one re-zeroes the per-query state (no memset op).
 int enqueue_classic(QueryLaunch& q, bool select, bool mark_scan_start, bool mark_scan_end)
 {
     Shard& s = q.s;
-    if (s.nrows > 0 && s.sample_chunks > 0)
-        GSIM_HIP(gsim::launch_sample(q.a, s.geo, static_cast<uint32_t>(s.sample_chunks), s.stream, nullptr, q.db->knobs.sample_shift));
+    if (s.nrows > 0) GSIM_HIP(gsim::launch_sample(q.a, s.geo, kSampleChunks, s.stream));
     if (mark_scan_start && q.ev) GSIM_HIP(hipEventRecord(q.ev[0], s.stream));
     if (s.nrows > 0) GSIM_HIP(gsim::launch_scan(q.a, s.geo, s.stream));
     if (!q.caller_syncs) { // the ring slot is free once the scan has run
@@ -626,14 +628,14 @@ int search_one(gsim_db* db, const uint32_t* query, uint32_t k, float cutoff, int
 
 // Two half-grid lanes of a shard (Shard::lanes), made on first use: the same rows, half the compute units each, own
 // stream / per-query state / regions / exchange buffer.
+constexpr int kLanes = 2; // (three and four lanes, of a quarter or a half of the CUs each, measured slower: profiles/r06_each_lanes.txt)
 int ensure_lanes(gsim_db* db, Shard& s)
 {
-    const int nl = std::min(std::max(db->knobs.each_lanes, 2), 4);
     if (!s.lanes.empty()) return GSIM_OK;
-    s.lanes.resize(static_cast<size_t>(nl));
+    s.lanes.resize(kLanes);
     for (auto& l : s.lanes) {
         l.device = s.device;
-        l.cu_share = std::max(db->knobs.each_lanes_share, 1); // (the lanes' grids: the CUs divided by this -- not necessarily by the number of lanes)
+        l.cu_share = kLanes;
         l.first_row = s.first_row;
         l.nrows = s.nrows;
         l.W = s.W;
@@ -649,14 +651,15 @@ int ensure_lanes(gsim_db* db, Shard& s)
 }
 
 // Does a pipelined call alternate this shard's queries between its two lanes?  Only where the single launch ranks the query
-// itself (k up to fused_select_max_k) on a table small enough that the chain behind the scan is a large part of the launch.
+// itself (k up to fused_select_max_k) or publishes for the large-k kernels (two small launches rank -- per lane), on a table
+// small enough that the chain behind the scan is a large part of the launch.
+constexpr uint64_t kLanesMaxBytes = 4096ull << 20; // (larger shards are HBM-bound: nothing to overlap)
 bool lanes_apply(const gsim_db* db, const Shard& s, uint32_t k, uint32_t nq)
 {
     if (db->knobs.each_lanes < 2 || nq < 4 || s.stream != s.own_stream || s.d_dbg || db->knobs.fused_debug) return false;
-    if (s.nrows * s.W * 4ull > static_cast<uint64_t>(db->knobs.each_lanes_max_mb) << 20) return false;
+    if (s.nrows * s.W * 4ull > kLanesMaxBytes) return false;
     if (s.nrows < 65536) return false; // (tiny tables: the half grid is no smaller than the whole one)
-    if (fused_publish_applies(db, s, k)) return db->knobs.each_lanes_publish != 0; // (large k: the launch publishes, two small kernels rank -- per lane)
-    return fused_applies(db, s, k);
+    return fused_publish_applies(db, s, k) || fused_applies(db, s, k);
 }
 
 // gsim_db_search_each on a single-shard handle: the queries still run strictly one after the other on the GPU (one
@@ -737,10 +740,9 @@ int check_search_args(gsim_db* db, const uint32_t* queries, int metric)
 
 using namespace gsim_host;
 
-extern "C" {
-
-int gsim_db_search(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_t kout, float cutoff, int metric,
-                   float alpha, float beta, gsim_hit* hits, uint32_t* counts, uint64_t* approx)
+// gsim_db_search, and gsim_db_search_each (`each`): its queries one by one, never a shared table pass
+static int search_host(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_t kout, float cutoff, int metric, float alpha, float beta,
+                       gsim_hit* hits, uint32_t* counts, uint64_t* approx, bool each)
 {
     int rc = check_search_args(db, queries, metric);
     if (rc != GSIM_OK) return rc;
@@ -756,13 +758,11 @@ int gsim_db_search(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_t k
         if (metric != GSIM_METRIC_TANIMOTO) return fail(GSIM_ERR_INVALID, "folded tables support Tanimoto only");
         return search_folded(db, queries, nq, kout, cutoff, hits, counts, approx);
     }
-    const bool batched = !g_force_each && nq >= 4 && k <= static_cast<uint32_t>(gsim::kSelectCap) && k > 0 &&
-                         gsim::batch_supported(db->W) && db->knobs.batch != 0;
+    const bool batched = !each && nq >= 4 && k <= static_cast<uint32_t>(gsim::kSelectCap) && k > 0 && gsim::batch_supported(db->W);
     if (batched)
         return db->comm ? search_batch_comm(db, queries, nq, k, kout, cutoff, metric, alpha, beta, hits, counts, approx)
                         : search_batched(db, queries, nq, k, kout, cutoff, metric, alpha, beta, hits, counts, approx);
-    const int pipelined = db->knobs.each_pipeline;
-    if (g_force_each && pipelined && nsh >= 1 && !db->comm && nq > 1 && k > 0 && db->nrows > 0 && !db->shards[0].d_dbg &&
+    if (each && nsh >= 1 && !db->comm && nq > 1 && k > 0 && db->nrows > 0 && !db->shards[0].d_dbg &&
         !db->knobs.fused_debug)
         return search_each_pipelined(db, queries, nq, k, kout, cutoff, metric, alpha, beta, hits, counts, approx);
     for (uint32_t q = 0; q < nq; q++) {
@@ -773,6 +773,14 @@ int gsim_db_search(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_t k
         if (rc != GSIM_OK) return rc;
     }
     return GSIM_OK;
+}
+
+extern "C" {
+
+int gsim_db_search(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_t kout, float cutoff, int metric,
+                   float alpha, float beta, gsim_hit* hits, uint32_t* counts, uint64_t* approx)
+{
+    return search_host(db, queries, nq, kout, cutoff, metric, alpha, beta, hits, counts, approx, false);
 }
 
 int gsim_db_search_timed(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_t kout, float cutoff, int metric, float alpha,
@@ -799,10 +807,7 @@ int gsim_db_search_timed(gsim_db* db, const uint32_t* queries, uint32_t nq, uint
 int gsim_db_search_each(gsim_db* db, const uint32_t* queries, uint32_t nq, uint32_t k, float cutoff, int metric,
                         float alpha, float beta, gsim_hit* hits, uint32_t* counts, uint64_t* approx)
 {
-    g_force_each = true;
-    const int rc = gsim_db_search(db, queries, nq, k, cutoff, metric, alpha, beta, hits, counts, approx);
-    g_force_each = false;
-    return rc;
+    return search_host(db, queries, nq, k, cutoff, metric, alpha, beta, hits, counts, approx, true);
 }
 
 int gsim_db_search_device(gsim_db* db, const uint32_t* query, uint32_t k, float cutoff, int metric, float alpha,

@@ -1048,9 +1048,9 @@ static uint32_t batch_mfma_sample_blocks(uint32_t W, uint64_t nrows)
 
 // Does the matrix-core sample pass apply to this table?  (Large tables only; batches with a cutoff
 // need it: it also estimates how many rows the cutoff keeps.)
-bool batch_mfma_sample_applies(uint32_t W, uint64_t nrows, uint32_t nq, uint32_t k, int num_cus, bool enabled)
+bool batch_mfma_sample_applies(uint32_t W, uint64_t nrows, uint32_t nq, uint32_t k, int num_cus)
 {
-    if (!enabled || k == 0 || nq > static_cast<uint32_t>(kMfmaQueries) || !batch_mfma_supported(W)) return false;
+    if (k == 0 || nq > static_cast<uint32_t>(kMfmaQueries) || !batch_mfma_supported(W)) return false;
     const uint32_t rb = kMChunks / (W / 4);
     const u64 nblocks = (nrows + rb - 1) / rb;
     if (nblocks < 64) return false; // tiny tables: the scan's own threshold upkeep is enough
@@ -1063,7 +1063,7 @@ bool batch_mfma_sample_applies(uint32_t W, uint64_t nrows, uint32_t nq, uint32_t
 bool launch_batch_mfma_sample(const BatchArgs& a, int num_cus, hipStream_t s, hipError_t* err)
 {
     *err = hipSuccess;
-    if (!batch_mfma_sample_applies(a.W, a.nrows, a.nq, a.k, num_cus, (a.opts & 1u) != 0)) return false;
+    if (!batch_mfma_sample_applies(a.W, a.nrows, a.nq, a.k, num_cus)) return false;
     const uint32_t rb = kMChunks / (a.W / 4);
     const u64 nblocks = (a.nrows + rb - 1) / rb;
     const uint32_t nsb = batch_mfma_sample_blocks(a.W, a.nrows);

@@ -149,114 +149,13 @@ uint32_t fused_summary_keys(uint32_t nwaves, uint32_t k, uint32_t max_m = 16);
 uint32_t fused_final_keys(uint32_t nwg, uint32_t k);
 
 // Geometry of the scan grid for a table (host side, no device work).
-// Every tuning knob of the library, read from the environment ONCE per handle -- by gsim_db_create -- and nowhere else
-// (INTEGRATION.md lists them with their meaning; nothing under a search entry point calls getenv).
-struct Knobs {
-    int scan_waves_per_cu = 4;       // GSIM_SCAN_WAVES_PER_CU
-    int scan_ragged = 1;             // GSIM_SCAN_RAGGED         0: odd widths take the LDS-staged generic scan
-    int sample_chunks = 4;           // GSIM_SAMPLE_CHUNKS
-    int sample_shift = 15;           // GSIM_SAMPLE_SHIFT
-    int fused = 1;                   // GSIM_FUSED               0: every query through the four-kernel pipeline
-    long long fused_max_rows = -1;   // GSIM_FUSED_MAX_ROWS
-    int fused_debug = 0;             // GSIM_FUSED_DEBUG         in-kernel phase stamps
-    int fused_flags = 0;             // GSIM_FUSED_FLAGS
-    int fused_seed_narrow = 1;       // GSIM_FUSED_SEED_NARROW
-    int fused_publish = 1;           // GSIM_FUSED_PUBLISH       0: k in (2048, 8192] is ranked inside the single launch, k above 8192 scans with the four-kernel pipeline
-    int fused_select_max_k = 2048;   // GSIM_FUSED_SELECT_MAX_K  largest k the single launch ranks itself (2048 ... 8192) where it can also publish for the large-k kernels
-    int largek_one_block_max = 32768; // GSIM_LARGEK_ONE_BLOCK_MAX
-    int fused_publish_max_k = 100000; // GSIM_FUSED_PUBLISH_MAX_K (up to kFusedPublishMaxK; round 5: 32768).  Measured at 100 M rows (profiles/r06_large_k.txt):
-                                      // k = 50 000 2.18 -> 1.93 ms (0.83 of the roofline), 100 000 2.31 -> 2.17; at 131 072 and beyond the waves' stores
-                                      // overflow before the first useful election and the queries are handed back: slower than the four-kernel pipeline
-    int publish_narrow = 1;           // GSIM_PUBLISH_NARROW      0: 128 / 256-bit rows never take the publishing launch for large k (round 5)
-    int largek_binrank_max_k = 65536; // GSIM_LARGEK_BINRANK_MAX_K  above it the published rows go through the radix select + sort (measured: 100 M rows, k = 100 000
-                                      // 2.31 ms bin-ranked with hand-backs for crowded bins, 2.11 ms by the radix tail; at k = 50 000 1.94 against 1.97)
-    int fused_backoff = 1;           // GSIM_FUSED_BACKOFF       0: a query handed back never routes later ones around the single launch
-    int publish_min_rows_per_k = 0;  // GSIM_PUBLISH_MIN_ROWS_PER_K  tables shorter than this many rows per hit rank large k inside the launch (up
-                                     // to round 5: 64 -- short tables publish most of their rows; measured in round 6 the publishing route is
-                                     // still 1.5 ... 6 x faster there and hands nothing back: profiles/r06_short_tables_large_k.txt)
-    int largek_binrank = 1;          // GSIM_LARGEK_BINRANK      0: the published rows of a large-k query always go through the radix select + sort
-    int each_pipeline = 1;           // GSIM_EACH_PIPELINE       0: gsim_db_search_each waits for every query before the next
-    int each_lanes = 2;              // GSIM_EACH_LANES          2 (or 4): pipelined queries of small tables alternate between that many part-grid lanes; 0: never
-    int each_lanes_share = 2;        // GSIM_EACH_LANES_SHARE    a lane's grid is sized for the CUs divided by this
-    int each_lanes_publish = 1;      // GSIM_EACH_LANES_PUBLISH  0: large k (the publishing route) stays on one stream
-    int each_lanes_max_mb = 4096;    // GSIM_EACH_LANES_MAX_MB   ... only shards of at most this many MB do (larger ones are HBM-bound: nothing to overlap)
-    int batch = 1;                   // GSIM_BATCH               0: no shared table passes
-    int batch_waves_per_cu = 12;     // GSIM_BATCH_WAVES_PER_CU
-    int batch_seg_cap = 65536;       // GSIM_BATCH_SEG_CAP
-    int batch_seg_cap_init = 4096;   // GSIM_BATCH_SEG_CAP_INIT
-    int batch_sample_chunks = 8;     // GSIM_BATCH_SAMPLE_CHUNKS
-    int batch_rpl = 0;               // GSIM_BATCH_RPL           rows per lane of the VALU pass (0: by width)
-    int batch_mfma_min_q = 4;        // GSIM_BATCH_MFMA_MIN_Q    0: batches never take the matrix cores
-    int batch_mfma_sample = 1;       // GSIM_BATCH_MFMA_SAMPLE
-    int batch_mfma_dense = 1;        // GSIM_BATCH_MFMA_DENSE    0: dense cutoffs go to the VALU pass
-    int debug_batch = 0;             // GSIM_DEBUG_BATCH         print the batch flags (instrumented builds: phase counters)
-    int fold_full_on_device = 1;     // GSIM_FOLD_FULL_ON_DEVICE
-    int fold_rescore_host = 0;       // GSIM_FOLD_RESCORE=host
-    int join_stream_max_rows = 2;    // GSIM_JOIN_STREAM_MAX_ROWS  joins of at most this many left rows stream the table once per left row, larger
-                                     // ones take the tile kernel (0: always tiles; DESIGN.md section 11 has the crossover)
-    int subset_gather_max_permille = 250; // GSIM_SUBSET_GATHER_MAX_PERMILLE  gsim_db_search_rows gathers the selected rows when
-                                     // selected x max(row bytes, 128) x 1000 <= this x N x row bytes, else streams the table under the
-                                     // mask (0: always stream, 1000 or more: always gather; DESIGN.md section 12 has the crossover)
-    long long group_launch_pairs = 0; // GSIM_GROUP_LAUNCH_PAIRS  a launch of gsim_db_search_group scores at most this many row x query
-                                     // pairs (at least one chunk of rows); 0: by the row width (capi_group.cpp group_launch_pairs;
-                                     // DESIGN.md section 13 has the rates and the arithmetic)
-    int leader_round = 256;          // GSIM_LEADER_ROUND        candidates per round of gsim_db_leader (1 ... kLeaderMaxRound); the result
-                                     // does not depend on it
-    long long leader_launch_pairs = 0; // GSIM_LEADER_LAUNCH_PAIRS  a launch of a gsim_db_leader pass scores at most this many row x leader
-                                     // pairs (at least one chunk of rows); 0: by the row width, as group_launch_pairs
-    long long knn_launch_pairs = 0;  // GSIM_KNN_LAUNCH_PAIRS    a launch of gsim_db_knn's fold kernel scores at most this many owner x candidate
-                                     // pairs (at least one column tile of 256 candidates); 0: by the row width, with the tile
-                                     // kernel's pricing and budget (capi_knn.cpp).  The result does not depend on it
-    int knn_join_segments = 0;       // GSIM_KNN_JOIN_SEGMENTS   column segments of a gsim_db_knn_join* call, each folded by workgroups of its
-                                     // own and merged afterwards; 0: 1 when the owner tiles alone give two workgroups per CU, else as
-                                     // many as make up for it; n: n, at most the table's column tiles and kKnnJoinMaxSegments
-                                     // (capi_knn_join.cpp plan_knn_join).  The result does not depend on it
-    long long knn_join_launch_pairs = 0; // GSIM_KNN_JOIN_LAUNCH_PAIRS  a launch of gsim_db_knn_join*'s fold kernel scores at most this many
-                                     // owner x candidate pairs (at least one column tile of 256 candidates per segment); 0: by the row
-                                     // width, as knn_launch_pairs.  The result does not depend on it
-    int hist_stream_max_rows = 32;   // GSIM_HIST_STREAM_MAX_ROWS  histogram calls of at most this many left rows stream the table once per left
-                                     // row, larger ones take the owner-tile kernel (0: always tiles; DESIGN.md section 16 has the crossover:
-                                     // between 32 and 64 left rows at 1 M and at 100 M x 1024-bit rows)
-    long long hist_launch_pairs = 0; // GSIM_HIST_LAUNCH_PAIRS   a launch of either histogram kernel scores at most this many left x table
-                                     // pairs (at least one 256 x 256 tile / 64 table rows); 0: by the row width, as knn_launch_pairs.
-                                     // The result does not depend on it
-    int hist_naive_add = 0;          // GSIM_HIST_NAIVE_ADD      1: the streaming kernel adds with one LDS atomic per lane instead of one per
-                                     // distinct bin of the wave (for timing the two forms; same counts)
-    long long scores_launch_pairs = 0; // GSIM_SCORES_LAUNCH_PAIRS  a launch of gsim_db_scores*'s matrix kernel computes at most this many left x
-                                     // table pairs (at least one 128 x 128 block); 0: by the padded row width (capi_scores.cpp;
-                                     // DESIGN.md section 17).  The result does not depend on it
-    long long scores_stage_bytes = 256ll << 20; // GSIM_SCORES_STAGE_BYTES  device staging of the host-output calls: a slab of whole left rows of
-                                     // at most this many bytes (at least one row) is computed, then copied out.  The result does not
-                                     // depend on it
-    long long components_launch_pairs = 0; // GSIM_COMPONENTS_LAUNCH_PAIRS  a launch of gsim_db_components' tile kernel scores at most this
-                                     // many pairs (at least one 256 x 256 tile); 0: the neighbour lists' launch plan (capi_pairs.cpp;
-                                     // DESIGN.md section 18).  The result does not depend on it
-    long long dbscan_launch_pairs = 0; // GSIM_DBSCAN_LAUNCH_PAIRS  a launch of either of gsim_db_dbscan's tile kernels scores at most this many
-                                     // pairs (at least one 256 x 256 tile); 0: the neighbour lists' launch plan (capi_pairs.cpp;
-                                     // DESIGN.md section 26).  The result does not depend on it
-    int dbscan_skip = 1;             // GSIM_DBSCAN_SKIP         0: the link pass scores every left row, even one that can matter to no
-                                     // lane of the wave (for timing; the result does not depend on it)
-    long long mst_launch_pairs = 0;  // GSIM_MST_LAUNCH_PAIRS    a launch of gsim_db_mst's fold kernel scores at most this many owner x candidate
-                                     // pairs (at least one column tile of 256 candidates); 0: as knn_launch_pairs (capi_mst.cpp;
-                                     // DESIGN.md section 19).  The result does not depend on it
-    long long profile_launch_rows = 0; // GSIM_PROFILE_LAUNCH_ROWS  a launch of gsim_db_bit_counts / gsim_db_overlap_sums takes at most this many
-                                     // rows (list entries on the gather route); 0: 32 GiB of rows (capi_profile.cpp; DESIGN.md section
-                                     // 20).  The result does not depend on it
-    long long assign_launch_pairs = 0; // GSIM_ASSIGN_LAUNCH_PAIRS  a launch of gsim_db_assign's kernel scores at most this many centre x row
-                                     // pairs (at least one block of 128 table rows against every centre); 0: by the padded row width,
-                                     // as scores_launch_pairs (capi_labels.cpp).  The result does not depend on it
-    long long labels_launch_rows = 0; // GSIM_LABELS_LAUNCH_ROWS  a launch of gsim_db_label_counts' counting kernel takes at most this many
-                                     // entries of the sorted row list; 0: 32 GiB of rows, as profile_launch_rows.  The result does not
-                                     // depend on it
-};
-
-ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll, bool ragged = true);
+ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll);
 // ... of the single launch where it differs from the four-kernel pipeline's: rows of 3, 5, 7, 9, 11 or twice that many WORDS
 // (false: it does not -- use scan_geometry's)
-bool fused_word_geometry(uint64_t nrows, uint32_t W, int num_cus, ScanGeometry* out, bool ragged = true);
+bool fused_word_geometry(uint64_t nrows, uint32_t W, int num_cus, ScanGeometry* out);
 
 // Optional K0: starting threshold from a strided sample of chunks_per_wave chunks per scan wave.
-hipError_t launch_sample(const ScanArgs& a, const ScanGeometry& g, uint32_t chunks_per_wave, hipStream_t s, bool* launched = nullptr, int sample_shift = 15);
+hipError_t launch_sample(const ScanArgs& a, const ScanGeometry& g, uint32_t chunks_per_wave, hipStream_t s, bool* launched = nullptr);
 hipError_t launch_scan(const ScanArgs& a, const ScanGeometry& g, hipStream_t s);
 
 // Compaction of candidates at or above the k-th best coarse bin into `finalists`.
@@ -349,8 +248,7 @@ struct BatchArgs {
     float cutoff;
     int metric;
     float alpha, beta;
-    uint32_t opts;           // host side only -- bit 0: matrix-core sample pass allowed, bit 1: dense-cutoff variant allowed,
-                             // bits 8-15: rows per lane of the VALU pass (0: by width) -- the handle's Knobs
+    uint32_t opts;           // host side only -- bit 1: dense-cutoff variant allowed (GSIM_BATCH_MFMA_DENSE); the other bits are not in use
 };
 
 bool batch_supported(uint32_t W);
@@ -368,7 +266,7 @@ uint32_t batch_mfma_waves(int num_cus);
 hipError_t launch_batch_mfma_scan(const BatchArgs& a, int num_cus, hipStream_t s);
 bool batch_mfma_dense_applies(int metric, float alpha, float beta, float cutoff, bool enabled);
 bool launch_batch_mfma_sample(const BatchArgs& a, int num_cus, hipStream_t s, hipError_t* err);
-bool batch_mfma_sample_applies(uint32_t W, uint64_t nrows, uint32_t nq, uint32_t k, int num_cus, bool enabled);
+bool batch_mfma_sample_applies(uint32_t W, uint64_t nrows, uint32_t nq, uint32_t k, int num_cus);
 hipError_t launch_batch_mfma_pass(const BatchArgs& a, const ScanGeometry& g, int num_cus, uint32_t sample_chunks,
                                   uint32_t row_base, void* results, size_t block_bytes, hipStream_t s,
                                   hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
@@ -453,7 +351,7 @@ struct DbscanArgs {
     float alpha, beta;
     float cutoff;
     uint32_t min_pts;            // >= 1; row x is a core iff degree[x] + 1 >= min_pts
-    uint32_t skip;               // link pass: 1 = a wave passes over a non-core left row when it holds no core (Knobs::dbscan_skip)
+    uint32_t skip;               // link pass: 1 = a wave passes over a non-core left row when it holds no core (GSIM_DBSCAN_SKIP)
     uint32_t* degree;            // nrows words, zeroed before the degree pass, which adds to them; the link pass reads them
     uint32_t* parent;            // one forest of nrows words over ALL rows (the protocol: gsim_components.hip); only cores are united
     unsigned long long* best;    // nrows words, zeroed before the link pass: key(score, ~core row) of a non-core row's anchor, 0: none

@@ -206,8 +206,8 @@ hipError_t launch_maxmin_pass_cached(const MaxMinArgs& m, const ScanGeometry& g,
 ScanGeometry maxmin_geometry(uint64_t nrows, uint32_t W, int num_cus)
 {
     ScanGeometry g{};
-    if (fused_word_geometry(nrows, W, num_cus, &g, true)) return g; // rows of 3 ... 11 or twice that many words
-    g = scan_geometry(nrows, W, num_cus, 4, 8, true);
+    if (fused_word_geometry(nrows, W, num_cus, &g)) return g; // rows of 3 ... 11 or twice that many words
+    g = scan_geometry(nrows, W, num_cus, 4, 8);
     if (g.lanes_per_row != 0 || g.ragged_loads != 0) return g;
     // generic: one row per lane, 64 rows per wave and trip; four waves per CU
     g = ScanGeometry{};

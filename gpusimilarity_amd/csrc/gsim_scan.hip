@@ -522,16 +522,16 @@ static bool is_pow2(uint32_t x)
 
 // loads per chunk of scan_ragged_kernel for rows of L sixteen-byte units: the odd part of L when that is 3, 5, ... 15, a
 // chunk holds at least one whole row (64 P / L >= 1) and a row's bits fit the packed counts' 16-bit fields, else 0
-static uint32_t ragged_loads_of(uint32_t L, bool enabled)
+static uint32_t ragged_loads_of(uint32_t L)
 {
-    if (!enabled || L == 0) return 0;
+    if (L == 0) return 0;
     uint32_t odd = L;
     while (odd % 2 == 0) odd /= 2;
     if (odd < 3 || odd > 15 || L * 128u > 65535u) return 0;
     return (64u * odd) % L == 0 && 64u * odd / L >= 1 ? odd : 0;
 }
 
-ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll, bool ragged)
+ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll)
 {
     ScanGeometry g{};
     const uint32_t lpr = (W % 4 == 0 && is_pow2(W / 4) && W / 4 <= 64) ? W / 4 : 0;
@@ -540,9 +540,9 @@ ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_pe
         unroll = 8; // (the only unroll built: 4 loads per chunk cost 12 %, 16 bought nothing -- profiles/r01_sweeps.txt)
         g.unroll = static_cast<uint32_t>(unroll);
         g.chunk_rows = g.unroll * (64 / lpr);
-    } else if (W % 4 == 0 && ragged_loads_of(W / 4, ragged) != 0) {
+    } else if (W % 4 == 0 && ragged_loads_of(W / 4) != 0) {
         // whole 16-byte units per row, odd part 3 ... 15: streamed through registers (scan_ragged_kernel)
-        g.ragged_loads = ragged_loads_of(W / 4, ragged);
+        g.ragged_loads = ragged_loads_of(W / 4);
         g.unroll = g.ragged_loads == 3 ? 3 : (g.ragged_loads == 5 ? 2 : 1); // sub-chunks per trip: 9, 10 or P loads in flight
         g.chunk_rows = g.unroll * (64u * g.ragged_loads / (W / 4));
     } else {
@@ -575,7 +575,7 @@ hipError_t launch_sample_t(const ScanArgs& a, uint32_t nsample, uint64_t stride,
 }
 
 // Starting threshold from a strided sample (large tables only).
-hipError_t launch_sample(const ScanArgs& a, const ScanGeometry& g, uint32_t chunks_per_wave, hipStream_t s, bool* launched, int sample_shift)
+hipError_t launch_sample(const ScanArgs& a, const ScanGeometry& g, uint32_t chunks_per_wave, hipStream_t s, bool* launched)
 {
     if (launched) *launched = false;
     if (a.k == 0 || chunks_per_wave == 0) return hipSuccess;
@@ -584,8 +584,7 @@ hipError_t launch_sample(const ScanArgs& a, const ScanGeometry& g, uint32_t chun
         // S = k N / 2^15 keeps that at ~32 Ki rows (a few dozen per scan wave) -- at least 64 Ki rows, at most 1 Mi, never
         // more than 1/8 of the table (down to 16 Ki rows, tables of 131 k rows: sparse 128-bit tables of 0.5 M rows were
         // handed back one query in ten without a seed); under that the scan's own warm-up is cheaper.
-        const int shift = sample_shift > 0 && sample_shift < 40 ? sample_shift : 15;
-        uint64_t want = (static_cast<uint64_t>(a.k) * a.nrows) >> shift;
+        uint64_t want = (static_cast<uint64_t>(a.k) * a.nrows) >> 15;
         if (want < 65536) want = 65536;
         if (want > (1u << 20)) want = 1u << 20;
         if (want > a.nrows / 8) want = a.nrows / 8;

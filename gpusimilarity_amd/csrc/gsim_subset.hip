@@ -423,7 +423,7 @@ ScanGeometry subset_scan_geometry(uint64_t nrows, uint32_t W, int num_cus)
 ScanGeometry subset_gather_geometry(uint64_t nsel, uint32_t W, int num_cus)
 {
     // a "table" of nsel rows, eight waves per CU (two per SIMD: a gathered load waits longer than a streamed one)
-    ScanGeometry g = scan_geometry(nsel, W, num_cus, 8, 8, false);
+    ScanGeometry g = scan_geometry(nsel, W, num_cus, 8, 8); // (a width without a power-of-two lane count: the gather's own geometry, below)
     if (g.lanes_per_row != 0) return g;
     g = ScanGeometry{};
     g.unroll = 1;
