@@ -136,6 +136,33 @@ class GsimMstStats(C.Structure):
                 ("scan_owners", C.c_uint64 * MST_MAX_ROUNDS), ("scan_kernel_ms", C.c_double * MST_MAX_ROUNDS)]
 
 
+HDBSCAN_NOISE = 0xFFFFFFFF
+HDBSCAN_EOM, HDBSCAN_LEAF, HDBSCAN_NO_ROOTS = 0, 1, 2
+
+
+class GsimMreachStats(C.Structure):
+    _fields_ = [("mst", GsimMstStats), ("core_launches", C.c_uint64), ("core_inserts", C.c_uint64), ("core_rows", C.c_uint64),
+                ("core_kernel_ms", C.c_double), ("core_tail_ms", C.c_double)]
+
+
+class GsimHdbscanStats(C.Structure):
+    _fields_ = [("forest", GsimMreachStats), ("clusters", C.c_uint64), ("noise", C.c_uint64), ("select_ms", C.c_double),
+                ("wall_ms", C.c_double)]
+
+
+def _mst_stats_dict(st):
+    stats = {f: getattr(st, f) for f, _ in GsimMstStats._fields_[:-2]}
+    stats["scan_owners"] = list(st.scan_owners)[:st.scans]
+    stats["scan_kernel_ms"] = list(st.scan_kernel_ms)[:st.scans]
+    return stats
+
+
+def _mreach_stats_dict(st):
+    stats = _mst_stats_dict(st.mst)
+    stats.update({f: getattr(st, f) for f, _ in GsimMreachStats._fields_[1:]})
+    return stats
+
+
 PROFILE_STREAMED, PROFILE_GATHERED, PROFILE_MATRIX, PROFILE_VALU = 1, 2, 4, 8
 ISIM_TANIMOTO, ISIM_RUSSELL_RAO, ISIM_SIMPLE_MATCHING = 0, 1, 2
 
@@ -196,6 +223,7 @@ EXPORTS = [
     "gsim_db_components", "gsim_components",
     "gsim_db_mst", "gsim_mst", "gsim_mst_linkage", "gsim_mst_cut",
     "gsim_db_dbscan", "gsim_dbscan",
+    "gsim_db_core_scores", "gsim_db_mreach_mst", "gsim_db_hdbscan", "gsim_mreach_mst", "gsim_mst_hdbscan",
     "gsim_db_bit_counts", "gsim_db_overlap_sums", "gsim_isim", "gsim_isim_complement",
     "gsim_db_assign", "gsim_db_label_counts", "gsim_label_centroids", "gsim_db_kmeans",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
@@ -321,6 +349,16 @@ def load():
         "gsim_dbscan": (C.c_int, [u64p, u32p, C.POINTER(C.c_float), C.c_uint64, C.c_uint32, u32p, u32p, u32p, u32p, u64p]),
         "gsim_mst_linkage": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp]),
         "gsim_mst_cut": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_float, u32p, u32p, u32p, u64p]),
+        "gsim_db_core_scores": (C.c_int, [vp, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float),
+                                          C.POINTER(GsimKnnStats)]),
+        "gsim_db_mreach_mst": (C.c_int, [vp, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, vp, u64p, C.POINTER(C.c_float),
+                                         C.POINTER(GsimMreachStats)]),
+        "gsim_db_hdbscan": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, C.c_uint32, u32p, u64p,
+                                      C.POINTER(C.c_float), u32p, u32p, C.POINTER(C.c_float), C.POINTER(C.c_double),
+                                      C.POINTER(GsimHdbscanStats)]),
+        "gsim_mreach_mst": (C.c_int, [u64p, u32p, C.POINTER(C.c_float), C.c_uint64, C.c_uint32, vp, u64p, C.POINTER(C.c_float)]),
+        "gsim_mst_hdbscan": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_float, C.c_uint32, C.c_uint32, u32p, u64p, C.POINTER(C.c_float),
+                                       u32p, u32p, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
         "gsim_db_bit_counts": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, u64p, u64p, C.POINTER(GsimProfileStats)]),
         "gsim_db_overlap_sums": (C.c_int, [vp, u32p, C.c_uint64, C.c_uint64, u64p, u32p, C.POINTER(GsimProfileStats)]),
         "gsim_isim": (C.c_int, [u64p, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
@@ -384,6 +422,17 @@ def result_block_bytes(k: int) -> int:
 
 def _u32(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def _f32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _hdbscan_buffers(n):
+    """label_of, leave [n]; first_row, sizes, birth, stability [capacity n]"""
+    m = max(n, 1)
+    return [np.empty(n, np.uint32), np.empty(n, np.float32), np.empty(m, np.uint32), np.empty(m, np.uint32), np.empty(m, np.float32),
+            np.empty(m, np.float64)]
 
 
 class RowSet:
@@ -737,10 +786,7 @@ class Table:
         ne = C.c_uint64(0)
         st = GsimMstStats()
         check(self._L.gsim_db_mst(self._h, cutoff, metric, alpha, beta, edges.ctypes.data, C.byref(ne), C.byref(st)))
-        stats = {f: getattr(st, f) for f, _ in GsimMstStats._fields_[:-2]}
-        stats["scan_owners"] = list(st.scan_owners)[:st.scans]
-        stats["scan_kernel_ms"] = list(st.scan_kernel_ms)[:st.scans]
-        return edges[:ne.value].copy(), stats
+        return edges[:ne.value].copy(), _mst_stats_dict(st)
 
     def dbscan(self, cutoff, min_pts, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, degree=True, anchor=True, first_row=True, sizes=True):
         """gsim_db_dbscan: DBSCAN density clustering -> (label_of uint32 [N] (DBSCAN_NOISE for noise), degree uint32 [N], anchor uint32
@@ -760,6 +806,44 @@ class Table:
                                      C.byref(st)))
         return (label_of, deg, anc, first[:ncl.value].copy() if first_row else None, size[:ncl.value].copy() if sizes else None,
                 {f: getattr(st, f) for f, _ in GsimDbscanStats._fields_})
+
+    def core_scores(self, min_pts, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0):
+        """gsim_db_core_scores: every row's HDBSCAN core score -> (core float32 [N], stats dict: gsim_knn_stats of the core pass).
+        core[i] is the score of row i's (min_pts - 1)-th nearest neighbour at or above the cutoff, 0 where it has fewer, 1 for
+        min_pts == 1: for t >= cutoff, core[i] >= t iff row i is a core of dbscan(t, min_pts)."""
+        core = np.empty(self.count(), dtype=np.float32)
+        st = GsimKnnStats()
+        check(self._L.gsim_db_core_scores(self._h, min_pts, cutoff, metric, alpha, beta, _f32(core), C.byref(st)))
+        return core, {f: getattr(st, f) for f, _ in GsimKnnStats._fields_}
+
+    def mreach_mst(self, min_pts, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0):
+        """gsim_db_mreach_mst: the mutual-reachability forest -> (edges, core float32 [N], stats dict).  gsim_db_mst's rule with
+        m(i, j) = min(score(i, j), core[i], core[j]) in place of the score: edges (MST_EDGE_DTYPE, a < b with the row base added,
+        score = m) in order E; the stats are `mst`'s plus the core pass's (core_launches, core_inserts, core_rows, core_kernel_ms,
+        core_tail_ms)."""
+        n = self.count()
+        edges = np.empty(max(n - 1, 1), dtype=MST_EDGE_DTYPE)
+        core = np.empty(n, dtype=np.float32)
+        ne = C.c_uint64(0)
+        st = GsimMreachStats()
+        check(self._L.gsim_db_mreach_mst(self._h, min_pts, cutoff, metric, alpha, beta, edges.ctypes.data, C.byref(ne), _f32(core), C.byref(st)))
+        return edges[:ne.value].copy(), core, _mreach_stats_dict(st)
+
+    def hdbscan(self, min_pts, min_cluster_size, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, flags=HDBSCAN_EOM):
+        """gsim_db_hdbscan: HDBSCAN clustering of the table -> (label_of uint32 [N] (HDBSCAN_NOISE for noise; no row base), leave
+        float32 [N], first_row uint32 [nclusters] (+ row base), sizes uint32 [nclusters], birth float32 [nclusters], stability
+        float64 [nclusters], stats dict).  The mutual-reachability forest at `cutoff`, its condensed tree with similarity as the
+        level, and the selection `flags` name: HDBSCAN_EOM or HDBSCAN_LEAF, either with HDBSCAN_NO_ROOTS."""
+        n = self.count()
+        out = _hdbscan_buffers(n)
+        ncl = C.c_uint64(0)
+        st = GsimHdbscanStats()
+        check(self._L.gsim_db_hdbscan(self._h, min_pts, min_cluster_size, cutoff, metric, alpha, beta, flags, _u32(out[0]), C.byref(ncl),
+                                      _f32(out[1]), _u32(out[2]), _u32(out[3]), _f32(out[4]), out[5].ctypes.data_as(C.POINTER(C.c_double)),
+                                      C.byref(st)))
+        stats = _mreach_stats_dict(st.forest)
+        stats.update({f: getattr(st, f) for f, _ in GsimHdbscanStats._fields_[1:]})
+        return tuple(out[:2]) + tuple(x[:ncl.value].copy() for x in out[2:]) + (stats,)
 
     def bit_counts(self, rowset=None, row_begin=0, row_end=None, stats=None):
         """gsim_db_bit_counts: how many of the counted rows have each bit set -> (counts uint64 [fp_bits], counted int).  The counted
@@ -1076,6 +1160,37 @@ def mst_cut(edges, nrows, t):
     nc = C.c_uint64(0)
     check(load().gsim_mst_cut(ptr, len(edges), n, t, _u32(component_of), _u32(first_row), _u32(sizes), C.byref(nc)))
     return component_of, first_row[:nc.value].copy(), sizes[:nc.value].copy()
+
+
+def mreach_mst(indptr, indices, scores, min_pts, nrows=None):
+    """gsim_mreach_mst (host code): the rule of gsim_db_mreach_mst on a symmetric scored CSR graph (Table.neighbors' output) ->
+    (edges (MST_EDGE_DTYPE, rows without any row base, score = min(score, core, core)) in order E, core float32 [n])."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.uint64)
+    indices = np.ascontiguousarray(indices, dtype=np.uint32)
+    scores = np.ascontiguousarray(scores, dtype=np.float32)
+    n = len(indptr) - 1 if nrows is None else int(nrows)
+    if n < 0 or len(indptr) < n + 1 or len(scores) != len(indices):
+        raise GsimError(-1, "indptr needs nrows + 1 entries, scores one per index")
+    edges = np.empty(max(n - 1, 1), dtype=MST_EDGE_DTYPE)
+    core = np.empty(n, dtype=np.float32)
+    ne = C.c_uint64(0)
+    check(load().gsim_mreach_mst(indptr.ctypes.data_as(C.POINTER(C.c_uint64)), _u32(indices), _f32(scores), n, min_pts, edges.ctypes.data,
+                                 C.byref(ne), _f32(core)))
+    return edges[:ne.value].copy(), core
+
+
+def mst_hdbscan(edges, nrows, floor, min_cluster_size, flags=HDBSCAN_EOM):
+    """gsim_mst_hdbscan (host code): the condensed tree of a forest in order E (rows without any row base; Table.mst's or
+    Table.mreach_mst's edges) and the selection of its clusters -> (label_of uint32 [n] (HDBSCAN_NOISE for noise), leave float32 [n],
+    first_row uint32 [nclusters], sizes uint32 [nclusters], birth float32 [nclusters], stability float64 [nclusters]).  `floor`: the
+    cutoff of the call that made the forest."""
+    edges, ptr = _mst_edges(edges)
+    n = int(nrows)
+    out = _hdbscan_buffers(n)
+    ncl = C.c_uint64(0)
+    check(load().gsim_mst_hdbscan(ptr, len(edges), n, floor, min_cluster_size, flags, _u32(out[0]), C.byref(ncl), _f32(out[1]), _u32(out[2]),
+                                  _u32(out[3]), _f32(out[4]), out[5].ctypes.data_as(C.POINTER(C.c_double))))
+    return tuple(out[:2]) + tuple(x[:ncl.value].copy() for x in out[2:])
 
 
 def _weights32(weights, fp_bits):

@@ -1,6 +1,7 @@
 // capi_knn.cpp -- gsim_db_knn: each row's k most similar other rows, exactly, as CSR.  The argument checks and the launches of a
 // call; the plan is plan_knn (capi_knn_join.cpp), the lists become CSR in capi_pairs.cpp (build_knn_csr).  The device side is
-// gsim_knn.hip (the fold kernel, offsets, compaction).  The rule is stated in include/gpusim_hip.h.
+// gsim_knn.hip (the fold kernel, offsets, compaction).  The rule is stated in include/gpusim_hip.h.  The fold launches of a plan
+// (knn_args, run_knn_fold) are also the core pass of the HDBSCAN calls (capi_hdbscan.cpp).
 #include "capi_front.h"
 
 namespace gsim_host
@@ -47,30 +48,9 @@ int knn(gsim_db* db, Shard& s, uint32_t k, float cutoff, int metric, float alpha
     GSIM_HIP(hipMemsetAsync(ctl, 0, (1 + 4 * plan.size()) * 8, st));
     if (const int rc = table.prepare(s.d_rows, N, st)) return rc;
 
-    gsim::KnnArgs a{};
-    a.rows = table.rows();
-    a.pop = table.pop();
-    a.nrows = N;
-    a.row_begin = rb;
-    a.row_end = re;
-    a.WP = WP;
-    a.k = k;
-    a.metric = metric;
-    a.alpha = alpha;
-    a.beta = beta;
-    a.cutoff = cutoff;
-    a.lists = lists;
-    a.len = len;
-    a.inserts = d_inserts;
-
     EventPair ev_fold;
-    GSIM_HIP(ev_fold.create());
-    GSIM_HIP(hipEventRecord(ev_fold.a, st));
-    for (size_t l = 0; l < plan.size(); l++) {
-        a.clk = clocks.at(l);
-        GSIM_HIP(gsim::launch_knn_fold(a, plan[l].ot0, plan[l].not_, plan[l].c0, plan[l].c1, st));
-    }
-    GSIM_HIP(hipEventRecord(ev_fold.b, st));
+    if (const int rc = run_knn_fold(knn_args(table, N, rb, re, WP, k, cutoff, metric, alpha, beta, lists, len, d_inserts), plan, clocks, ev_fold, st))
+        return rc;
 
     KnnCsr csr;
     if (const int rc = build_knn_csr(db, s, lists, len, nout, k, tmp, d_indptr, ctl, "the k-nearest-neighbour CSR", "knn", g, &csr)) return rc;
@@ -91,6 +71,40 @@ int knn(gsim_db* db, Shard& s, uint32_t k, float cutoff, int metric, float alpha
 }
 
 } // namespace
+
+gsim::KnnArgs knn_args(const PaddedRows& table, uint64_t N, uint64_t rb, uint64_t re, uint32_t WP, uint32_t k, float cutoff, int metric,
+                       float alpha, float beta, gsim::KnnEntry* lists, uint32_t* len, unsigned long long* inserts)
+{
+    gsim::KnnArgs a{};
+    a.rows = table.rows();
+    a.pop = table.pop();
+    a.nrows = N;
+    a.row_begin = rb;
+    a.row_end = re;
+    a.WP = WP;
+    a.k = k;
+    a.metric = metric;
+    a.alpha = alpha;
+    a.beta = beta;
+    a.cutoff = cutoff;
+    a.lists = lists;
+    a.len = len;
+    a.inserts = inserts;
+    return a;
+}
+
+int run_knn_fold(gsim::KnnArgs a, const std::vector<KnnLaunch>& plan, const LaunchClocks& clocks, EventPair& ev_fold, hipStream_t st)
+{
+    GSIM_HIP(ev_fold.create());
+    GSIM_HIP(hipEventRecord(ev_fold.a, st));
+    for (size_t l = 0; l < plan.size(); l++) {
+        a.clk = clocks.at(l);
+        GSIM_HIP(gsim::launch_knn_fold(a, plan[l].ot0, plan[l].not_, plan[l].c0, plan[l].c1, st));
+    }
+    GSIM_HIP(hipEventRecord(ev_fold.b, st));
+    return GSIM_OK;
+}
+
 } // namespace gsim_host
 
 using namespace gsim_host;

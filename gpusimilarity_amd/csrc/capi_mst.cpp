@@ -1,7 +1,8 @@
 // capi_mst.cpp -- gsim_db_mst (the exact single-linkage dendrogram of the table as its maximum-similarity spanning forest, by
 // Boruvka rounds on the device) and its host companions gsim_mst (the same rule on a scored CSR graph), gsim_mst_linkage and
 // gsim_mst_cut.  The argument checks and the round loop of a call; the device side is gsim_mst.hip.  The rule is stated in
-// include/gpusim_hip.h.
+// include/gpusim_hip.h.  The round loop (boruvka_forest) also serves gsim_db_mreach_mst (capi_hdbscan.cpp), with another fold
+// launcher; so do the edge order, the edge checks and Kruskal on a list of pairs (capi_pairs.h).
 #include "capi_front.h"
 
 #include <algorithm>
@@ -22,8 +23,10 @@ uint32_t mst_chunks(const KnnLaunch& l)
     return static_cast<uint32_t>(std::max<uint64_t>(1, std::min(std::min(want, most), uint64_t{65535})));
 }
 
-int mst(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, float beta, gsim_mst_edge* edges, uint64_t* nedges,
-        gsim_mst_stats* st)
+} // namespace
+
+int boruvka_forest(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, float beta, uint32_t row_base, const ForestFold& ff,
+                   gsim_mst_edge* edges, uint64_t* nedges, gsim_mst_stats* st)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t N = s.nrows;
@@ -97,6 +100,8 @@ int mst(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, float beta
     if (const int rc = table.prepare(s.d_rows, N, stream)) return rc;
     a.rows = table.rows();
     a.pop = table.pop();
+    if (ff.prepare)
+        if (const int rc = ff.prepare(table, stream)) return rc;
     GSIM_HIP(gsim::launch_mst_init(m, stream));
 
     gsim_mst_stats ms{};
@@ -112,7 +117,7 @@ int mst(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, float beta
         GSIM_HIP(hipEventRecord(ev_fold.a, stream));
         for (size_t l = 0; l < plan.size(); l++) {
             a.clk = clocks.at(l);
-            GSIM_HIP(gsim::launch_mst_fold(a, plan[l].ot0, plan[l].not_, plan[l].c0, plan[l].c1, mst_chunks(plan[l]), stream));
+            GSIM_HIP(ff.fold(a, plan[l].ot0, plan[l].not_, plan[l].c0, plan[l].c1, mst_chunks(plan[l]), stream));
         }
         GSIM_HIP(hipEventRecord(ev_fold.b, stream));
         GSIM_HIP(hipEventRecord(ev_round.a, stream));
@@ -145,7 +150,7 @@ int mst(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, float beta
     GSIM_HIP(hipEventRecord(ev_sort.a, stream));
     GSIM_HIP(gsim::launch_mst_count_roots(m, stream));
     // (the components' picks are dead now: the sort's second buffers)
-    GSIM_HIP(gsim::launch_mst_sort(m, total, tmp, sort_bytes, ckey, cscore, db->row_base, d_edges, stream));
+    GSIM_HIP(gsim::launch_mst_sort(m, total, tmp, sort_bytes, ckey, cscore, row_base, d_edges, stream));
     GSIM_HIP(hipEventRecord(ev_sort.b, stream));
     unsigned long long h_ctl[gsim::kMstCtlWords] = {};
     GSIM_HIP(hipEventRecord(ev_d2h.a, stream));
@@ -185,7 +190,28 @@ int check_edges(const gsim_mst_edge* edges, uint64_t nedges, uint64_t nrows)
     return GSIM_OK;
 }
 
-} // namespace
+int check_scored_csr(const uint64_t* indptr, const uint32_t* indices, const float* scores, uint64_t nrows, const gsim_mst_edge* edges,
+                     uint64_t* nnz)
+{
+    if (const int rc = check_csr_offsets(indptr, nrows, nnz)) return rc;
+    if (*nnz && (!indices || !scores)) return fail(GSIM_ERR_INVALID, "NULL indices or scores");
+    if (nrows > 1 && !edges) return fail(GSIM_ERR_INVALID, "NULL edges");
+    if (const int rc = check_csr_indices(indices, *nnz, nrows)) return rc;
+    for (uint64_t e = 0; e < *nnz; e++)
+        if (std::isnan(scores[e])) return fail(GSIM_ERR_INVALID, "mst: an edge with a NaN score");
+    return GSIM_OK;
+}
+
+uint64_t kruskal_in_e(std::vector<gsim_mst_edge>& all, uint64_t nrows, gsim_mst_edge* edges)
+{
+    std::sort(all.begin(), all.end(), before_in_e);
+    Forest f(nrows);
+    uint64_t n = 0;
+    for (const gsim_mst_edge& e : all)
+        if (f.unite(e.a, e.b)) edges[n++] = e;
+    return n;
+}
+
 } // namespace gsim_host
 
 using namespace gsim_host;
@@ -205,8 +231,12 @@ int gsim_db_mst(gsim_db* db, float cutoff, int metric, float alpha, float beta, 
     if (N > 1 && !edges) return fail(GSIM_ERR_INVALID, "NULL edges");
     if (N == 0) return GSIM_OK;
     if (const int rc = check_table_state(db, "mst", false)) return rc;
+    ForestFold ff;
+    ff.fold = [](const gsim::MstArgs& a, uint32_t ot0, uint32_t not_, uint64_t c0, uint64_t c1, uint32_t nchunk, hipStream_t st) {
+        return gsim::launch_mst_fold(a, ot0, not_, c0, c1, nchunk, st);
+    };
     return on_one_shard(db, "host memory for the spanning forest",
-                        [&](Shard& s) { return mst(db, s, cutoff, metric, alpha, beta, edges, nedges, stats); });
+                        [&](Shard& s) { return boruvka_forest(db, s, cutoff, metric, alpha, beta, db->row_base, ff, edges, nedges, stats); });
 }
 
 int gsim_mst(const uint64_t* indptr, const uint32_t* indices, const float* scores, uint64_t nrows, gsim_mst_edge* edges, uint64_t* nedges)
@@ -214,12 +244,7 @@ int gsim_mst(const uint64_t* indptr, const uint32_t* indices, const float* score
     if (nedges) *nedges = 0;
     if (!indptr || !nedges) return fail(GSIM_ERR_INVALID, "NULL argument");
     uint64_t nnz = 0;
-    if (const int rc = check_csr_offsets(indptr, nrows, &nnz)) return rc;
-    if (nnz && (!indices || !scores)) return fail(GSIM_ERR_INVALID, "NULL indices or scores");
-    if (nrows > 1 && !edges) return fail(GSIM_ERR_INVALID, "NULL edges");
-    if (const int rc = check_csr_indices(indices, nnz, nrows)) return rc;
-    for (uint64_t e = 0; e < nnz; e++)
-        if (std::isnan(scores[e])) return fail(GSIM_ERR_INVALID, "mst: an edge with a NaN score");
+    if (const int rc = check_scored_csr(indptr, indices, scores, nrows, edges, &nnz)) return rc;
     try {
         // every listed pair once per listing, as a < b; Kruskal skips what it has seen
         std::vector<gsim_mst_edge> all;
@@ -229,12 +254,7 @@ int gsim_mst(const uint64_t* indptr, const uint32_t* indices, const float* score
                 const uint32_t i = static_cast<uint32_t>(r), j = indices[e];
                 if (i != j) all.push_back({std::min(i, j), std::max(i, j), scores[e]});
             }
-        std::sort(all.begin(), all.end(), before_in_e);
-        Forest f(nrows);
-        uint64_t n = 0;
-        for (const gsim_mst_edge& e : all)
-            if (f.unite(e.a, e.b)) edges[n++] = e;
-        *nedges = n;
+        *nedges = kruskal_in_e(all, nrows, edges);
     } catch (const std::bad_alloc&) {
         return fail(GSIM_ERR_NOMEM, "mst");
     }

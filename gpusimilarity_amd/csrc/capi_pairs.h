@@ -2,7 +2,9 @@
 // object, the handle's pair buffer with its overflow / exact-regrow protocol, the tile kernel's launch plan, and the CSR
 // build; and what the k-NN calls (capi_knn.cpp, capi_knn_join.cpp, capi_mst.cpp) share: the fold launches' plan and the CSR
 // build of their lists; and what the host functions on a caller's graph share: the CSR checks, the union-find forest and the
-// numbering of its trees.  Implemented in capi_pairs.cpp (the k-NN plan: capi_knn_join.cpp).  Internal.
+// numbering of its trees; and what the two spanning forests share (capi_mst.cpp, capi_hdbscan.cpp): the round loop, order E, the
+// edge checks, Kruskal on a list of pairs, and the k-NN fold launches of a plan.  Implemented in capi_pairs.cpp (the k-NN plan:
+// capi_knn_join.cpp; the forests' part: capi_mst.cpp and capi_knn.cpp).  Internal.
 #pragma once
 
 #include "capi_internal.h"
@@ -136,5 +138,34 @@ struct Forest {
 // The trees of f numbered by ascending first row: component_of [nrows], and per component (where not NULL) first_row and sizes.
 // Returns the number of components.
 uint32_t number_components(Forest& f, uint64_t nrows, uint32_t* component_of, uint32_t* first_row, uint32_t* sizes);
+
+// ---- what gsim_db_mst and the mutual-reachability forests share (capi_mst.cpp; capi_hdbscan.cpp calls them) ----
+
+// What differs between the two forests on the device: `prepare` (or nothing) fills more device state once the padded table is ready,
+// before the first round -- it may wait for the stream --; `fold` enqueues one fold launch (gsim::launch_mst_fold's arguments).
+struct ForestFold {
+    std::function<int(const PaddedRows& table, hipStream_t st)> prepare;
+    std::function<hipError_t(const gsim::MstArgs& a, uint32_t ot0, uint32_t not_, uint64_t c0, uint64_t c1, uint32_t nchunk, hipStream_t st)> fold;
+};
+// The Boruvka rounds of a forest call on the handle's one shard: the call's device memory, the round loop, the sort into order E
+// (row_base added to both rows of an edge) and the copy to the host.  N < 2 returns before `prepare`.
+int boruvka_forest(gsim_db* db, Shard& s, float cutoff, int metric, float alpha, float beta, uint32_t row_base, const ForestFold& ff,
+                   gsim_mst_edge* edges, uint64_t* nedges, gsim_mst_stats* st);
+// order E
+bool before_in_e(const gsim_mst_edge& x, const gsim_mst_edge& y);
+// INVALID "NULL edges", "more than 2^32-1 rows", "mst: an edge needs a < b < nrows", "mst: an edge with a NaN score"
+int check_edges(const gsim_mst_edge* edges, uint64_t nedges, uint64_t nrows);
+// gsim_mst's checks of its graph and of the edge buffer: the CSR checks above, "NULL indices or scores", "NULL edges" with nrows > 1,
+// "mst: an edge with a NaN score"
+int check_scored_csr(const uint64_t* indptr, const uint32_t* indices, const float* scores, uint64_t nrows, const gsim_mst_edge* edges,
+                     uint64_t* nnz);
+// Kruskal over the pairs a < b of `all` (sorted here into order E; repeated pairs are harmless) -> edges, in order E; their number
+uint64_t kruskal_in_e(std::vector<gsim_mst_edge>& all, uint64_t nrows, gsim_mst_edge* edges);
+
+// The fold launches of a k-NN plan (capi_knn.cpp; the core pass of capi_hdbscan.cpp runs the same): a's table, lists and cutoff as
+// the caller set them, every launch with its clock words, HIP events around all of them.
+gsim::KnnArgs knn_args(const PaddedRows& table, uint64_t N, uint64_t rb, uint64_t re, uint32_t WP, uint32_t k, float cutoff, int metric,
+                       float alpha, float beta, gsim::KnnEntry* lists, uint32_t* len, unsigned long long* inserts);
+int run_knn_fold(gsim::KnnArgs a, const std::vector<KnnLaunch>& plan, const LaunchClocks& clocks, EventPair& ev_fold, hipStream_t st);
 
 } // namespace gsim_host

@@ -485,6 +485,19 @@ hipError_t mst_sort_bytes(uint64_t n, size_t* bytes);
 hipError_t launch_mst_sort(const MstState& m, uint64_t n, void* tmp, size_t tmp_bytes, unsigned long long* ekey2, uint32_t* eb2,
                            uint32_t row_base, void* edges, hipStream_t s);
 
+// ---- mutual-reachability forests (gsim_mreach.hip, gsim_db_core_scores / gsim_db_mreach_mst / gsim_db_hdbscan) ---------------
+// gsim_db_mst's rounds with m(i, j) = min(score(i, j), core[i], core[j]) in place of the score: only the fold kernel differs.
+struct MreachArgs {
+    MstArgs mst;
+    const float* core;           // nrows core scores: 0.0f, or a value >= cutoff
+};
+// as launch_mst_fold
+hipError_t launch_mreach_fold(const MreachArgs& a, uint32_t ot0, uint32_t not_, uint64_t c0, uint64_t c1, uint32_t nchunk, hipStream_t s);
+// core[i] = list i's last entry's score where the list is full (len[i] == k), else 0.0f; with k == 0 (min_pts 1: no lists) 1.0f.
+// *dense grows by the number of rows with core[i] >= cutoff.
+hipError_t launch_mreach_core(const KnnEntry* lists, const uint32_t* len, uint64_t nrows, uint32_t k, float cutoff, float* core,
+                              unsigned long long* dense, hipStream_t s);
+
 // ---- per-bit column counts and weighted popcounts (gsim_profile.hip, gsim_db_bit_counts / gsim_db_overlap_sums) -------------
 constexpr int kProfileBlock = 256;
 constexpr uint32_t kProfileMaxIters = 4088; // rows one thread can add into its 12 vertical counter planes: a multiple of 8 below 2^12

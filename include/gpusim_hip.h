@@ -887,7 +887,7 @@ int gsim_components(const uint64_t* indptr, const uint32_t* indices, uint64_t nr
 
 /* ---- exact single-linkage dendrograms: the maximum-similarity spanning forest ---------------------------------------------------- */
 /* gsim_db_mst returns the single-linkage dendrogram of a single-shard, unfolded handle with N rows as its maximum-similarity spanning
- * forest: at most N - 1 edges, from which every cut (gsim_mst_cut), the merge tree (gsim_mst_linkage), HDBSCAN-style stability and
+ * forest: at most N - 1 edges, from which every cut (gsim_mst_cut), the merge tree (gsim_mst_linkage), HDBSCAN-style stability (gsim_mst_hdbscan) and
  * "cut where the gap is largest" follow without another pass over the pairs (no counterpart in the reference).  Built by Boruvka
  * rounds on the device; none of the graph is stored: memory is O(N).
  * THE RULE:
@@ -1025,6 +1025,112 @@ int gsim_db_dbscan(gsim_db* db, float cutoff, uint32_t min_pts, int metric, floa
 int gsim_dbscan(const uint64_t* indptr, const uint32_t* indices, const float* scores, uint64_t nrows, uint32_t min_pts,
                 uint32_t* label_of, uint32_t* anchor /* or NULL */, uint32_t* first_row /* or NULL */, uint32_t* sizes /* or NULL */,
                 uint64_t* nclusters);
+
+/* ---- HDBSCAN: core scores, mutual-reachability forests, the condensed tree and the selection of clusters ------------------------- */
+/* Hierarchical density clustering (HDBSCAN: Campello, Moulavi, Sander, PAKDD 2013; Campello, Moulavi, Zimek, Sander, TKDD 2015; no
+ * counterpart in the reference) of a single-shard, unfolded handle with N rows: DBSCAN at every cutoff at once, and the clusters that
+ * persist over the longest range of levels picked from that hierarchy.  Its O(N^2) part is one k-nearest-neighbour fold (the core
+ * scores) and gsim_db_mst's Boruvka scans with another value per pair; none of the graph is stored, memory is O(N).  The level of the
+ * hierarchy is the similarity itself: the textbook's density 1 / distance is infinite for duplicates, a similarity of 1.0 is not.
+ * THE RULE:
+ *   - preconditions: gsim_db_mst's.  N < 2^32 rows of at most 4096 bits; GSIM_METRIC_TANIMOTO, or GSIM_METRIC_TVERSKY with alpha ==
+ *     beta, finite and >= 0; cutoff in (0, 1]; score(i, j) is bit for bit the `score` gsim_db_search returns, NaN (0 / 0) is never >=
+ *     cutoff.  min_pts counts the row itself, as in gsim_db_dbscan: 1 <= min_pts <= GSIM_KNN_MAX_K + 1;
+ *   - core score: for min_pts >= 2, core(i) is the score of the LAST entry of row i's list in gsim_db_knn(k = min_pts - 1, cutoff, ...)
+ *     where that list is full (min_pts - 1 entries); otherwise core(i) = 0.0f: the row is not dense at any level >= cutoff.  For
+ *     min_pts == 1, core(i) = 1.0f for every row, all-zero rows included.  Consequence: for every t >= cutoff, core(i) >= t iff row i
+ *     is a core of gsim_db_dbscan(t, min_pts);
+ *   - mutual-reachability score: m(i, j) = min(score(i, j), core(i), core(j)).  The pair is an edge iff score(i, j) >= cutoff and
+ *     m(i, j) >= cutoff;
+ *   - forest (gsim_db_mreach_mst): gsim_db_mst's rule with m in place of the score.  The pairs a < b that are edges, in the strict
+ *     total ORDER E: (m descending, a ascending, b ascending); Kruskal takes them in that order and keeps an edge iff its ends are not
+ *     yet connected.  Output: the kept edges in order E, the handle's row base added to a and b, `score` = m.  Ties are the normal
+ *     case here -- every edge that a row's own core score caps carries that value -- and order E is what makes the forest unique.
+ * Consequences: (1) with min_pts == 1 the edges equal gsim_db_mst's byte for byte; (2) for every t >= cutoff, gsim_mst_cut(edges, t)
+ * restricted to the rows with core >= t is the partition gsim_db_dbscan(t, min_pts) gives on its core rows (DBSCAN*: border rows are
+ * noise), and every other row is a singleton of the cut; (3) the result equals gsim_mreach_mst applied to gsim_db_neighbors(cutoff)'s
+ * CSR; (4) the output is byte-identical from run to run and does not depend on how the passes are cut into launches: the scans read
+ * GSIM_MST_LAUNCH_PAIRS and the core pass reads GSIM_KNN_LAUNCH_PAIRS (read once per handle).
+ *
+ * THE CONDENSED TREE AND THE SELECTION (gsim_mst_hdbscan: host code on any forest in order E, gsim_db_mst's output included; rows
+ * without any row base).  Inputs: the edges, nrows, `floor` <= every edge score (the cutoff of the call that made the forest),
+ * min_cluster_size >= 2, flags.
+ *   - equal scores are ONE event, so nothing depends on the order of tied merges.  For each distinct edge score s, a NODE AT s is a
+ *     connected component of {edges with score >= s} that contains an edge of score exactly s; its children are the maximal components
+ *     of {edges with score > s} inside it: nodes, or single rows;
+ *   - every tree of the forest with at least min_cluster_size rows starts a ROOT CLUSTER, born at `floor`, at the tree's top node;
+ *     the rows of smaller trees are noise;
+ *   - a cluster C born at b walks down from its node.  At a node of level s: the rows of the children smaller than min_cluster_size
+ *     leave C at s.  With no other ("large") child, C ends.  With exactly one, C continues as that child.  With two or more, C ends at
+ *     s and each large child is a new cluster born at s, with parent C; the rows of those children leave C at s;
+ *   - stability(C) = the sum, over the rows in C at its birth, of (the level at which the row left C - b), in double.  It is summed
+ *     as (number of rows that leave at a node) x (double(s) - double(b)): every term is >= 0, one term per node on C's way down;
+ *   - selection GSIM_HDBSCAN_EOM (0, "excess of mass"), bottom-up: a cluster without child clusters is selected and S^ = its stability.
+ *     Otherwise let sub = the sum of S^ over its child clusters: if stability(C) >= sub, C is selected, every descendant is deselected
+ *     and S^ = stability(C) -- equality selects the parent --, else S^ = sub.  GSIM_HDBSCAN_LEAF (1): exactly the clusters without child
+ *     clusters are selected.  GSIM_HDBSCAN_NO_ROOTS (flag bit 2, with either): a root cluster that has child clusters is never selected;
+ *   - the selected clusters are numbered 0, 1, ... in ascending order of their smallest row.  A row carries the number of the selected
+ *     cluster it was in at that cluster's birth, else GSIM_HDBSCAN_NOISE;
+ *   - outputs: label_of[nrows]; *nclusters; leave[nrows] (or NULL): the level at which the row left the last cluster it was in, 0.0f
+ *     if it was in none; first_row / sizes / birth / stability (each or NULL; capacity nrows, the first *nclusters entries written, the
+ *     rest left untouched): the selected cluster's smallest row, its rows at birth, its birth level and its stability.
+ * GSIM_ERR_INVALID: NULL edges with nedges > 0, NULL label_of with nrows > 0, NULL nclusters, gsim_mst_linkage's edge checks (a >= b,
+ * b >= nrows, a NaN score, nedges >= nrows, a score above its predecessor's, an edge whose ends are already connected), a floor above
+ * an edge score or NaN, min_cluster_size < 2, unknown flags.  nrows == 0 is legal.
+ *
+ * gsim_db_core_scores writes core[N] (useful on its own: the similarity of the k-th neighbour is the usual local-density and outlier
+ * score).  Its gsim_knn_stats (or NULL) describe the core pass: `entries` is the number of rows with core >= cutoff, `csr_ms` the tail
+ * kernel that reads the lists' last entries; no CSR is built and no list is copied to the host.
+ * gsim_db_mreach_mst writes the forest and, where core is not NULL, core[N].
+ * gsim_db_hdbscan is gsim_db_mreach_mst followed by gsim_mst_hdbscan with floor = cutoff, in one call: label_of without row base (as
+ * gsim_db_dbscan), first_row with the handle's row base added.
+ * Errors of the three device calls: GSIM_ERR_INVALID, GSIM_ERR_STATE and GSIM_ERR_NOMEM exactly as gsim_db_mst, plus GSIM_ERR_INVALID
+ * for min_pts == 0 or min_pts > GSIM_KNN_MAX_K + 1, NULL core (gsim_db_core_scores, N > 0), NULL label_of (N > 0) / nclusters,
+ * min_cluster_size < 2 and unknown flags (gsim_db_hdbscan).  N == 0: GSIM_OK.  N == 1 on a resident table: no edge, core 0.0f (1.0f
+ * for min_pts == 1).
+ * Execution: on the handle's stream under the one-call-at-a-time rule; the search state is left as it was found.  Device memory of a
+ * forest call, allocated and freed by it: gsim_db_mst's, plus 4 B x N for the core scores, plus -- during the core pass only, freed
+ * before the first scan -- gsim_db_knn's lists, N x (min_pts - 1) x 8 B, and 4 B x N of list lengths.  Lists built in pieces are not
+ * offered: where N x (min_pts - 1) x 8 B does not fit, the call returns GSIM_ERR_NOMEM. */
+#define GSIM_HDBSCAN_NOISE 0xFFFFFFFFu
+#define GSIM_HDBSCAN_EOM 0u
+#define GSIM_HDBSCAN_LEAF 1u
+#define GSIM_HDBSCAN_NO_ROOTS 2u
+typedef struct {
+    gsim_mst_stats mst;       /* the scans, the bookkeeping, the sort and the copy of the edges, as gsim_db_mst reports them     */
+    uint64_t core_launches;   /* the core pass: launches of the k-NN fold kernel (0 for min_pts == 1)                            */
+    uint64_t core_inserts;    /* ... list insertions made                                                                       */
+    uint64_t core_rows;       /* rows with core >= cutoff                                                                       */
+    double core_kernel_ms;    /* ... HIP events around its fold launches                                                        */
+    double core_tail_ms;      /* ... the kernel that reads the lists' last entries                                              */
+} gsim_mreach_stats;
+typedef struct {
+    gsim_mreach_stats forest; /* gsim_db_mreach_mst's part                                                                      */
+    uint64_t clusters;        /* *nclusters                                                                                     */
+    uint64_t noise;           /* rows labelled GSIM_HDBSCAN_NOISE                                                               */
+    double select_ms;         /* the condensed tree and the selection, host clock                                               */
+    double wall_ms;           /* the whole call, host clock                                                                     */
+} gsim_hdbscan_stats;
+int gsim_db_core_scores(gsim_db* db, uint32_t min_pts, float cutoff, int metric, float alpha, float beta,
+                        float* core /* N */, gsim_knn_stats* stats /* or NULL */);
+int gsim_db_mreach_mst(gsim_db* db, uint32_t min_pts, float cutoff, int metric, float alpha, float beta,
+                       gsim_mst_edge* edges /* capacity N - 1 */, uint64_t* nedges, float* core /* N, or NULL */,
+                       gsim_mreach_stats* stats /* or NULL */);
+int gsim_db_hdbscan(gsim_db* db, uint32_t min_pts, uint32_t min_cluster_size, float cutoff, int metric, float alpha, float beta,
+                    uint32_t flags, uint32_t* label_of /* N */, uint64_t* nclusters, float* leave /* N, or NULL */,
+                    uint32_t* first_row /* N, or NULL */, uint32_t* sizes /* N, or NULL */, float* birth /* N, or NULL */,
+                    double* stability /* N, or NULL */, gsim_hdbscan_stats* stats /* or NULL */);
+/* The forest's rule on a symmetric scored CSR graph (host code, no device; gsim_mst's companion), e.g. gsim_db_neighbors' output:
+ * core(i) is the (min_pts - 1)-th largest score of row i's list, self edges not counted (a pair listed twice counts twice), 0.0f where
+ * the list is shorter, 1.0f for min_pts == 1; a listed pair is an edge iff both rows' lists are long enough; then Kruskal in order E
+ * over min(score, core, core).  edges: capacity nrows - 1, rows without any row base; core: nrows, or NULL.  GSIM_ERR_INVALID:
+ * gsim_mst's checks, or min_pts == 0; nrows == 0 is legal. */
+int gsim_mreach_mst(const uint64_t* indptr, const uint32_t* indices, const float* scores, uint64_t nrows, uint32_t min_pts,
+                    gsim_mst_edge* edges, uint64_t* nedges, float* core /* or NULL */);
+int gsim_mst_hdbscan(const gsim_mst_edge* edges, uint64_t nedges, uint64_t nrows, float floor, uint32_t min_cluster_size, uint32_t flags,
+                     uint32_t* label_of /* nrows */, uint64_t* nclusters, float* leave /* nrows, or NULL */,
+                     uint32_t* first_row /* or NULL */, uint32_t* sizes /* or NULL */, float* birth /* or NULL */,
+                     double* stability /* or NULL */);
 
 /* ---- per-bit column counts and iSIM library statistics ---------------------------------------------------------------------------- */
 /* The column-wise questions about a table, a row range or a cluster (a gsim_rowset): how often is each bit set, how tight is the set,
