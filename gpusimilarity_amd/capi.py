@@ -192,6 +192,15 @@ class GsimKmeansStats(C.Structure):
                 ("counts_ms", C.c_double), ("update_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
+LABEL_SUMS_OWN_ONLY = 1
+
+
+class GsimLabelSumsStats(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("rows_labelled", C.c_uint64), ("labels_nonempty", C.c_uint64), ("pairs", C.c_uint64),
+                ("launches", C.c_uint64), ("sort_ms", C.c_double), ("gather_ms", C.c_double), ("kernel_ms", C.c_double),
+                ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -226,6 +235,7 @@ EXPORTS = [
     "gsim_db_core_scores", "gsim_db_mreach_mst", "gsim_db_hdbscan", "gsim_mreach_mst", "gsim_mst_hdbscan",
     "gsim_db_bit_counts", "gsim_db_overlap_sums", "gsim_isim", "gsim_isim_complement",
     "gsim_db_assign", "gsim_db_label_counts", "gsim_label_centroids", "gsim_db_kmeans",
+    "gsim_db_label_sums", "gsim_label_silhouette", "gsim_label_medoids",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -367,6 +377,11 @@ def load():
                                      C.POINTER(C.c_float), C.POINTER(GsimAssignStats)]),
         "gsim_db_label_counts": (C.c_int, [vp, u32p, C.c_uint32, C.c_uint64, C.c_uint64, u32p, u32p, C.POINTER(GsimLabelStats)]),
         "gsim_label_centroids": (C.c_int, [u32p, u32p, C.c_uint32, C.c_uint32, u32p, u32p]),
+        "gsim_db_label_sums": (C.c_int, [vp, u32p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_float, C.c_float, C.c_uint32, C.c_uint64,
+                                         C.POINTER(C.c_uint64), u32p, C.POINTER(C.c_uint64), u32p, C.POINTER(GsimLabelSumsStats)]),
+        "gsim_label_silhouette": (C.c_int, [u32p, C.POINTER(C.c_uint64), u32p, C.POINTER(C.c_uint64), u32p, C.c_uint64, C.c_uint32,
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "gsim_label_medoids": (C.c_int, [u32p, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, u32p]),
         "gsim_db_kmeans": (C.c_int, [vp, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, u32p, u32p,
                                      C.POINTER(C.c_float), u32p, C.POINTER(GsimKmeansStats)]),
         "gsim_last_error": (C.c_char_p, []),
@@ -919,6 +934,32 @@ class Table:
             stats.update({f: getattr(st, f) for f, _ in GsimLabelStats._fields_})
         return counts, sizes
 
+    def label_sums(self, labels, nlabels, row_begin=0, row_end=None, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, own_only=False, launch_pairs=0):
+        """gsim_db_label_sums: the quantised score sums of every row of [row_begin, row_end) by label -> (own_q uint64, other_label
+        uint32, other_q uint64, sizes uint32 [nlabels], stats dict); other_label and other_q are None with own_only=True (the medoid
+        route: only the pairs inside a cluster are scored).  q = floor(score * 2^31) per ordered pair, so every sum is an integer;
+        own_q[i] sums row i's scores against the other rows of its label, other_label[i] is the other label of the greatest mean
+        (exact fractions, the lowest label among equals) and other_q[i] its sum.  A LABEL_NONE row gets (0, LABEL_NONE, 0).
+        :func:`label_silhouette` and :func:`label_medoids` take the output as it is."""
+        if row_end is None:
+            row_end = self.count()
+        lab = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+        n = max(row_end - row_begin, 0)
+        if len(lab) != n:
+            raise GsimError(-1, "labels: %d entries for %d rows" % (len(lab), row_end - row_begin))
+        u64p = C.POINTER(C.c_uint64)
+        own = np.zeros(max(n, 1), dtype=np.uint64)
+        other = None if own_only else np.full(max(n, 1), LABEL_NONE, dtype=np.uint32)
+        other_q = None if own_only else np.zeros(max(n, 1), dtype=np.uint64)
+        sizes = np.zeros(max(int(nlabels), 1), dtype=np.uint32)
+        st = GsimLabelSumsStats()
+        check(self._L.gsim_db_label_sums(self._h, _u32(lab) if len(lab) else None, nlabels, row_begin, row_end, metric, alpha, beta,
+                                         LABEL_SUMS_OWN_ONLY if own_only else 0, int(launch_pairs), own.ctypes.data_as(u64p),
+                                         None if own_only else _u32(other), None if own_only else other_q.ctypes.data_as(u64p), _u32(sizes),
+                                         C.byref(st)))
+        stats = {f: getattr(st, f) for f, _ in GsimLabelSumsStats._fields_}
+        return own[:n], (None if own_only else other[:n]), (None if own_only else other_q[:n]), sizes[:int(nlabels)], stats
+
     def kmeans(self, init, max_iter=20, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0):
         """gsim_db_kmeans: Lloyd's iteration from the m centres `init` over the whole table -- assign, count, majority-vote centroid,
         until the labels repeat or `max_iter` assignments were made -> (centres uint32 [m, words], label uint32 [N], score float32
@@ -1247,6 +1288,41 @@ def label_centroids(counts, sizes, previous=None) -> np.ndarray:
     check(load().gsim_label_centroids(_u32(c) if c.size else None, _u32(z) if nlabels else None, nlabels, fp_bits,
                                       _u32(prev) if prev is not None and prev.size else None, _u32(out) if out.size else None))
     return out
+
+
+def label_silhouette(labels, own_q, other_label, other_q, sizes):
+    """gsim_label_silhouette (host code): the silhouette of every row on the distance 1 - score from Table.label_sums' output ->
+    (sil float64 [n], label_mean float64 [nlabels], mean float).  a = own_q / (size - 1) * 2^-31, b = other_q / size(other) * 2^-31,
+    sil = (a - b) / (1 - min(a, b)), 0.0 where that is 0 / 0, for a singleton, a row without another cluster and a LABEL_NONE row."""
+    u64p, f64p = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
+    lab = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+    own = np.ascontiguousarray(own_q, dtype=np.uint64).reshape(-1)
+    oth = np.ascontiguousarray(other_label, dtype=np.uint32).reshape(-1)
+    othq = np.ascontiguousarray(other_q, dtype=np.uint64).reshape(-1)
+    z = np.ascontiguousarray(sizes, dtype=np.uint32).reshape(-1)
+    n = len(lab)
+    if not (len(own) == len(oth) == len(othq) == n):
+        raise GsimError(-1, "label silhouette: own_q, other_label and other_q need one entry per label")
+    sil = np.zeros(max(n, 1), dtype=np.float64)
+    lmean = np.zeros(max(len(z), 1), dtype=np.float64)
+    mean = C.c_double(0.0)
+    check(load().gsim_label_silhouette(_u32(lab) if n else None, own.ctypes.data_as(u64p) if n else None, _u32(oth) if n else None,
+                                       othq.ctypes.data_as(u64p) if n else None, _u32(z) if len(z) else None, n, len(z),
+                                       sil.ctypes.data_as(f64p), lmean.ctypes.data_as(f64p), C.byref(mean)))
+    return sil[:n], lmean[:len(z)], mean.value
+
+
+def label_medoids(labels, own_q, nlabels) -> np.ndarray:
+    """gsim_label_medoids (host code): for every label the row of the greatest own_q (Table.label_sums, own_only=True is enough), the
+    lowest row among equals -> uint32 [nlabels]; LABEL_NONE for a label without rows."""
+    lab = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+    own = np.ascontiguousarray(own_q, dtype=np.uint64).reshape(-1)
+    if len(own) != len(lab):
+        raise GsimError(-1, "label medoids: own_q needs one entry per label")
+    out = np.zeros(max(int(nlabels), 1), dtype=np.uint32)
+    check(load().gsim_label_medoids(_u32(lab) if len(lab) else None, own.ctypes.data_as(C.POINTER(C.c_uint64)) if len(lab) else None, len(lab),
+                                    nlabels, _u32(out)))
+    return out[:int(nlabels)]
 
 
 def litmus(test: int, workgroups: int = 256, iterations: int = 100000, device: int = 0) -> dict:

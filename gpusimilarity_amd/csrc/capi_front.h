@@ -90,4 +90,24 @@ template <class Fn> int on_one_shard(gsim_db* db, const char* nomem_what, Fn&& c
     return rc;
 }
 
+// ---- the label sort of gsim_db_label_counts and gsim_db_label_sums (capi_labels.cpp; the device side is gsim_labels.hip) ----
+
+// keys = min(label, nlabels) and row numbers, one stable radix sort, the segment starts: the rows of a label become one ascending
+// segment of vals2, GSIM_LABEL_NONE sorts behind every label.  The call's 16 bytes a row beside the labels themselves.
+struct LabelSort {
+    DevBuf<uint32_t> keys, vals; // before the sort
+    DevBuf<uint32_t> keys2;      // the label of every sorted position ...
+    DevBuf<uint32_t> vals2;      // ... and its table row (r0 + the index into the labels)
+    DevBuf<uint32_t> first;      // nlabels + 1 segment starts; first[nlabels]: the labelled rows
+    DevBuf<> tmp;
+    size_t tmp_bytes = 0;
+    std::vector<uint32_t> h_first; // first on the host, once the stream has been waited for
+
+    // NOMEM "device memory for <what> (sort keys)", ... in the order above
+    int alloc(uint64_t n, uint32_t nlabels, const char* what);
+    // The labels of the n > 0 rows from table row r0 on -- h_labels (copied into d_labels first) or d_labels as it is: enqueues the
+    // keys, the sort, the starts and their copy into h_first
+    int enqueue(const uint32_t* h_labels, uint32_t* d_labels, uint64_t n, uint32_t nlabels, uint64_t r0, hipStream_t st);
+};
+
 } // namespace gsim_host

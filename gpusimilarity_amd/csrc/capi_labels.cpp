@@ -2,10 +2,36 @@
 // (the column counts of every label in one pass), gsim_label_centroids (host: the majority votes) and gsim_db_kmeans (the loop over
 // the three, labels resident on the device).  The argument checks, the slabs and launch cuts and the copies of a call; the device
 // side is gsim_assign.hip and gsim_labels.hip.  The rules are stated in include/gpusim_hip.h; DESIGN.md section 21 has the routes.
+// The label sort (LabelSort, declared in capi_front.h) is also the first step of gsim_db_label_sums (capi_label_sums.cpp).
 #include "capi_front.h"
 
 namespace gsim_host
 {
+
+int LabelSort::alloc(uint64_t n, uint32_t nlabels, const char* what)
+{
+    const std::string w = std::string("device memory for ") + what;
+    GSIM_HIP(gsim::labels_sort_bytes(n, nlabels, &tmp_bytes));
+    if (keys.grow(n * 4) != hipSuccess) return fail(GSIM_ERR_NOMEM, w + " (sort keys)");
+    if (vals.grow(n * 4) != hipSuccess) return fail(GSIM_ERR_NOMEM, w + " (row numbers)");
+    if (keys2.grow(n * 4) != hipSuccess) return fail(GSIM_ERR_NOMEM, w + " (sorted keys)");
+    if (vals2.grow(n * 4) != hipSuccess) return fail(GSIM_ERR_NOMEM, w + " (sorted row numbers)");
+    if (tmp.grow(tmp_bytes) != hipSuccess) return fail(GSIM_ERR_NOMEM, w + " (the sort's scratch)");
+    if (first.grow((static_cast<size_t>(nlabels) + 1) * 4) != hipSuccess) return fail(GSIM_ERR_NOMEM, w + " (segment starts)");
+    h_first.assign(static_cast<size_t>(nlabels) + 1, 0);
+    return GSIM_OK;
+}
+
+int LabelSort::enqueue(const uint32_t* h_labels, uint32_t* d_labels, uint64_t n, uint32_t nlabels, uint64_t r0, hipStream_t st)
+{
+    if (h_labels) GSIM_HIP(hipMemcpyAsync(d_labels, h_labels, n * 4, hipMemcpyHostToDevice, st));
+    GSIM_HIP(gsim::launch_labels_keys(d_labels, n, nlabels, static_cast<uint32_t>(r0), keys, vals, st));
+    GSIM_HIP(gsim::launch_labels_sort(tmp, tmp_bytes, keys, keys2, vals, vals2, n, nlabels, st));
+    GSIM_HIP(gsim::launch_labels_bounds(keys2, n, nlabels, first, st));
+    GSIM_HIP(hipMemcpyAsync(h_first.data(), first, h_first.size() * 4, hipMemcpyDeviceToHost, st));
+    return GSIM_OK;
+}
+
 namespace
 {
 
@@ -106,29 +132,18 @@ int label_counts_device(gsim_db* db, Shard& s, const uint32_t* h_labels, uint32_
     const hipStream_t st = s.stream;
     const uint32_t F = db->fp_bits;
     const size_t ncount = static_cast<size_t>(nlabels) * F;
-    DevBuf<uint32_t> keys, vals, keys2, vals2, first, d_counts;
-    DevBuf<> tmp;
-    size_t tmp_bytes = 0;
-    GSIM_HIP(gsim::labels_sort_bytes(n, nlabels, &tmp_bytes));
-    GSIM_ALLOC(keys, n * 4, "the label counts (sort keys)");
-    GSIM_ALLOC(vals, n * 4, "the label counts (row numbers)");
-    GSIM_ALLOC(keys2, n * 4, "the label counts (sorted keys)");
-    GSIM_ALLOC(vals2, n * 4, "the label counts (sorted row numbers)");
-    GSIM_ALLOC(tmp, tmp_bytes, "the label counts (the sort's scratch)");
-    GSIM_ALLOC(first, (static_cast<size_t>(nlabels) + 1) * 4, "the label counts (segment starts)");
+    LabelSort sort;
+    DevBuf<uint32_t> d_counts;
+    if (const int rc = sort.alloc(n, nlabels, "the label counts")) return rc;
     if (counts) GSIM_ALLOC(d_counts, ncount * 4, "the label counters");
     EventPair ev_sort, ev_run, ev_d2h;
     GSIM_HIP(ev_sort.create());
     GSIM_HIP(ev_run.create());
     GSIM_HIP(ev_d2h.create());
-    std::vector<uint32_t> h_first(static_cast<size_t>(nlabels) + 1);
 
     GSIM_HIP(hipEventRecord(ev_sort.a, st));
-    if (h_labels) GSIM_HIP(hipMemcpyAsync(d_labels, h_labels, n * 4, hipMemcpyHostToDevice, st));
-    GSIM_HIP(gsim::launch_labels_keys(d_labels, n, nlabels, static_cast<uint32_t>(r0), keys, vals, st));
-    GSIM_HIP(gsim::launch_labels_sort(tmp, tmp_bytes, keys, keys2, vals, vals2, n, nlabels, st));
-    GSIM_HIP(gsim::launch_labels_bounds(keys2, n, nlabels, first, st));
-    GSIM_HIP(hipMemcpyAsync(h_first.data(), first, h_first.size() * 4, hipMemcpyDeviceToHost, st));
+    if (const int rc = sort.enqueue(h_labels, d_labels, n, nlabels, r0, st)) return rc;
+    const std::vector<uint32_t>& h_first = sort.h_first;
     if (counts) GSIM_HIP(hipMemsetAsync(d_counts, 0, ncount * 4, st));
     GSIM_HIP(hipEventRecord(ev_sort.b, st));
     GSIM_HIP(hipStreamSynchronize(st));
@@ -143,8 +158,8 @@ int label_counts_device(gsim_db* db, Shard& s, const uint32_t* h_labels, uint32_
     gsim::LabelCountArgs a{};
     a.rows = static_cast<const uint32_t*>(s.d_rows);
     a.W = s.W;
-    a.keys = keys2;
-    a.list = vals2;
+    a.keys = sort.keys2;
+    a.list = sort.vals2;
     a.counts = d_counts;
     a.nlabels = nlabels;
     const uint64_t knob = static_cast<uint64_t>(db->knobs.labels_launch_rows);

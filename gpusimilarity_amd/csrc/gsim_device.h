@@ -642,6 +642,41 @@ hipError_t launch_labels_count(const LabelCountArgs& a, uint64_t i0, uint64_t i1
 // *changed (zeroed by the caller) += the number of i < n with a[i] != b[i]
 hipError_t launch_labels_changed(const uint32_t* a, const uint32_t* b, uint64_t n, unsigned long long* changed, hipStream_t s);
 
+// ---- quantised score sums by label (gsim_label_sums.hip, gsim_db_label_sums) -------------------------------------------------
+constexpr int kLsumTile = 256;          // owner rows of one workgroup
+constexpr int kLsumBlock = 256;         // 4 waves, 64 owners each
+constexpr uint32_t kLsumColTile = 256;  // launches are cut at multiples of this many candidates
+// What an owner carries from launch to launch (32 bytes)
+struct LsumState {
+    unsigned long long run_q;    // the sum over the part seen so far of the segment that the last launch ended in (0: it ended at a segment's end)
+    unsigned long long own_q;    // Q[i, labels[i]]
+    unsigned long long best_q;   // Q[i, best_label]
+    uint32_t best_label;         // GSIM_LABEL_NONE: no other segment folded yet
+    uint32_t pad;
+};
+struct LsumArgs {
+    const uint32_t* rows;        // the labelled rows in sorted order: n x WP words, 16-byte aligned, zero-padded
+    const uint32_t* pop;         // popc of every one
+    const uint32_t* keys;        // the label of every sorted position (ascending)
+    const uint32_t* first;       // nlabels + 1 segment starts: label l is [first[l], first[l + 1])
+    uint64_t n;                  // labelled rows: owners and candidates are the sorted positions [0, n)
+    uint32_t WP;                 // words per row as the kernel reads them (4, 8, ... 128)
+    int metric;
+    float alpha, beta;           // the owner is the query side: alpha weighs its bits
+    LsumState* state;            // n entries; before the first launch {0, 0, 0, GSIM_LABEL_NONE}
+    unsigned long long* clk;     // as KnnArgs.clk
+};
+// out (n x WP words) = the table rows list[0 .. n) of W words each, zero-padded
+hipError_t launch_lsum_gather(const uint32_t* rows, uint32_t W, uint32_t WP, const uint32_t* list, uint64_t n, uint32_t* out, hipStream_t s);
+hipError_t launch_lsum_init(LsumState* state, uint64_t n, hipStream_t s);
+// Owner tiles ot0 .. ot0 + not_ - 1 (tile t = sorted positions t * kLsumTile ..) fold the candidates [c0, c1) into their state; with
+// own_only a wave walks only the part of [c0, c1) that holds its owners' own segments.  The pieces of the same owners must be launched
+// in ascending, gapless column order on one stream.
+hipError_t launch_lsum_fold(const LsumArgs& a, bool own_only, uint32_t ot0, uint32_t not_, uint64_t c0, uint64_t c1, hipStream_t s);
+// The state of sorted position p -> the outputs of row list[p] - row0 (other_label / other_q: or nullptr)
+hipError_t launch_lsum_scatter(const LsumState* state, const uint32_t* list, uint64_t n, uint32_t row0, unsigned long long* own_q, uint32_t* other_label,
+                               unsigned long long* other_q, hipStream_t s);
+
 // ---- MaxMin diversity picking (gsim_maxmin.hip, gsim_db_maxmin) ----------------------------------------------------------
 // ctl words of a call (zeroed by the host before the first pass; the ticket on its own 128-byte line)
 constexpr uint32_t kMaxMinDone = 0;    // 1: picking has ended (early stop or no unpicked row left); later passes return at once

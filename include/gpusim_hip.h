@@ -1306,6 +1306,84 @@ int gsim_db_kmeans(gsim_db* db, const uint32_t* init /* m x words */, uint32_t m
                    uint32_t* centres /* m x words */, uint32_t* label /* N */, float* score /* or NULL */,
                    uint32_t* sizes /* m, or NULL */, gsim_kmeans_stats* stats /* or NULL */);
 
+/* ---- how good a labelling is, and which row stands for a cluster: score sums by label, silhouettes, exact medoids ----------------- */
+/* Every call above that returns labels (gsim_butina, gsim_db_leader, gsim_db_components / gsim_mst_cut, gsim_db_dbscan,
+ * gsim_db_hdbscan, gsim_db_kmeans, gsim_db_maxmin's `nearest`) can be judged and given representatives by one all-pairs pass over the
+ * labelled rows; neither the score matrix nor a graph is stored.  No counterpart in the reference.
+ *
+ * gsim_db_label_sums, THE RESULT RULE (labels[i] is the label of row row_begin + i, as in gsim_db_label_counts; host memory):
+ *   - a row labelled GSIM_LABEL_NONE is neither an owner nor a candidate: own_q = 0, other_label = GSIM_LABEL_NONE, other_q = 0.
+ *     sizes[l] (or NULL) is the number of rows with label l;
+ *   - s(i, j) is the reference's one f32 divide with row i as the query side -- alpha weighs i's own bits, exactly as gsim_db_knn
+ *     scores an owner against a candidate --, 0 / 0 is 0.0f.  Metrics: GSIM_METRIC_TANIMOTO, and GSIM_METRIC_TVERSKY with any finite
+ *     alpha >= 0, beta >= 0: every ORDERED pair is scored, so symmetry is not needed;
+ *   - q(s) = (uint32) floor(s * 2^31).  The product is exact in f32 (a power of two), the conversion truncates: scores of 2^-8 and
+ *     above convert exactly, smaller ones lose less than 2^-31.  Every sum is therefore a sum of INTEGERS: byte-identical from run to
+ *     run, independent of the order of addition and of how the call is cut into launches; with fewer than 2^32 rows it stays below 2^63;
+ *   - Q[i, l] is the sum of q(s(i, j)) over the rows j of the range with labels[j] == l and j != i; own_q[i] = Q[i, labels[i]];
+ *   - other_label[i] is the label l != labels[i] with sizes[l] > 0 of the greatest MEAN Q[i, l] / sizes[l].  Means are compared as
+ *     exact fractions (Q1 * n2 against Q2 * n1, 96-bit products), never as rounded doubles; among equal means the LOWEST label wins.
+ *     other_q[i] = Q[i, other_label[i]]; when no other label has rows, other_label[i] = GSIM_LABEL_NONE and other_q[i] = 0;
+ *   - GSIM_LABEL_SUMS_OWN_ONLY (bit 0 of flags) computes own_q and sizes only: other_label / other_q may be NULL and are not written,
+ *     and only the pairs inside a cluster are scored -- the sum over the labels of sizes[l]^2 of them, not n^2.  The medoid route;
+ *   - owners and candidates are the rows of the range; the row base plays no part (indices as in gsim_db_bit_counts);
+ *   - launch_pairs: a launch of the kernel scores at most this many owner x candidate pairs, and at least one tile of 256 owners
+ *     against 256 candidates; 0: priced by the row width, as GSIM_KNN_LAUNCH_PAIRS = 0 is.  The result does not depend on it.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / own_q, NULL other_label / other_q without GSIM_LABEL_SUMS_OWN_ONLY,
+ * nlabels == 0, NULL labels with a non-empty range, a label >= nlabels other than GSIM_LABEL_NONE, an unknown flag bit, row_begin >
+ * row_end or row_end past the count, an unknown metric, Tversky alpha / beta negative or not finite, a table of 2^32 rows or more, rows
+ * wider than 4096 bits.  GSIM_ERR_STATE: a table not on a GPU, a folded table, a multi-shard handle.  GSIM_ERR_NOMEM: the call's
+ * device memory cannot be had; nothing leaked.  An empty range: GSIM_OK, sizes zeroed.
+ * Execution: on the handle's stream under the one-call-at-a-time rule, every temporary freed, the search state left as it was found.
+ * Owner tiles are independent and their candidates are not split over workgroups (as gsim_db_knn): a short range against nothing else
+ * has little parallelism.  Device memory of a call, with n_lab labelled rows of the range: their label-sorted copy, zero-padded to WP
+ * words (n_lab x WP x 4 bytes; WP = 4, 8, 16, 32, 64 or 128, the first that holds a row), 4 bytes a row of popcounts, the sort's 20 bytes
+ * per row of the range and its scratch, nlabels + 1 segment starts, 32 bytes a row of carried state, 20 bytes per row of the range of
+ * outputs (8 with GSIM_LABEL_SUMS_OWN_ONLY). */
+#define GSIM_LABEL_SUMS_OWN_ONLY 1u
+typedef struct {
+    uint64_t rows;            /* row_end - row_begin                                                                    */
+    uint64_t rows_labelled;   /* ... whose label is not GSIM_LABEL_NONE: n_lab                                          */
+    uint64_t labels_nonempty; /* labels with at least one row                                                           */
+    uint64_t pairs;           /* ordered pairs scored, i != j: n_lab^2 - n_lab, own-only: the sum of sizes[l]^2 - n_lab */
+    uint64_t launches;        /* launches of the fold kernel                                                            */
+    double sort_ms;           /* HIP events: labels to the device, keys, the sort, the segment starts                   */
+    double gather_ms;         /* ... the sorted copy, its popcounts, the carried state's first values                   */
+    double kernel_ms;         /* ... all fold launches                                                                  */
+    double d2h_ms;            /* ... the outputs back to row order and to the host                                      */
+    double wall_ms;           /* the whole call, host clock                                                             */
+    double clock_mhz;         /* as gsim_knn_stats.clock_mhz                                                            */
+} gsim_label_sums_stats;
+int gsim_db_label_sums(gsim_db* db, const uint32_t* labels /* host, row_end - row_begin */, uint32_t nlabels,
+                       uint64_t row_begin, uint64_t row_end, int metric, float alpha, float beta,
+                       uint32_t flags, uint64_t launch_pairs /* 0 = automatic */,
+                       uint64_t* own_q, uint32_t* other_label, uint64_t* other_q /* each row_end - row_begin */,
+                       uint32_t* sizes /* nlabels, or NULL */, gsim_label_sums_stats* stats /* or NULL */);
+
+/* The silhouette of every row on the distance 1 - s, from gsim_db_label_sums' output (host code, no device, no handle).  For a row i
+ * with label L, sizes[L] >= 2 and other_label[i] != GSIM_LABEL_NONE, in IEEE doubles, one rounding per operation, in this order:
+ *     a = ((double) own_q[i] / (double) (sizes[L] - 1)) * 0x1p-31         the mean score to its own cluster's other rows
+ *     b = ((double) other_q[i] / (double) sizes[other_label[i]]) * 0x1p-31  ... to the nearest other cluster
+ *     d = 1.0 - fmin(a, b)                                                 max(1 - a, 1 - b)
+ *     sil[i] = d > 0 ? (a - b) / d : 0.0
+ * (the conversions of integers above 2^53 round to nearest even; the scalings by 2^-31 are exact).  A singleton, a row without
+ * another cluster and a GSIM_LABEL_NONE row get 0.0.  label_mean[l] (or NULL) is the sum of sil over label l's rows, added in
+ * ascending row order from 0.0, divided by (double) sizes[l]; an empty label gives 0.0.  *mean (or NULL) is the sum over all
+ * labelled rows in ascending row order divided by their number; no labelled row gives 0.0.
+ * GSIM_ERR_INVALID, nothing written: NULL labels / own_q / other_label / other_q / sizes with n > 0, NULL sizes / sil where they
+ * have entries, nlabels == 0, a label >= nlabels other than GSIM_LABEL_NONE, an other_label equal to the row's own label or
+ * >= nlabels other than GSIM_LABEL_NONE, an other_label without rows, a sizes[] that disagrees with labels. */
+int gsim_label_silhouette(const uint32_t* labels, const uint64_t* own_q, const uint32_t* other_label,
+                          const uint64_t* other_q, const uint32_t* sizes, uint64_t n, uint32_t nlabels,
+                          double* sil /* n */, double* label_mean /* nlabels, or NULL */, double* mean /* or NULL */);
+
+/* The exact medoid of every label (host code): medoid[l] is the row i < n with labels[i] == l of the greatest own_q[i] -- the row
+ * most similar to the rest of its cluster --, the LOWEST row among equals; GSIM_LABEL_NONE for a label without rows.
+ * GSIM_ERR_INVALID, nothing written: NULL labels / own_q with n > 0, NULL medoid, nlabels == 0, n >= 2^32, a label >= nlabels other
+ * than GSIM_LABEL_NONE. */
+int gsim_label_medoids(const uint32_t* labels, const uint64_t* own_q, uint64_t n, uint32_t nlabels,
+                       uint32_t* medoid /* nlabels */);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
