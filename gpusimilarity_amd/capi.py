@@ -201,6 +201,12 @@ class GsimLabelSumsStats(C.Structure):
                 ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
 
 
+class GsimLabelSearchStats(C.Structure):
+    _fields_ = [("queries", C.c_uint64), ("labels", C.c_uint64), ("passes", C.c_uint64), ("passes_lds", C.c_uint64),
+                ("passes_global", C.c_uint64), ("launches", C.c_uint64), ("scan_ms", C.c_double), ("finish_ms", C.c_double),
+                ("d2h_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -236,6 +242,7 @@ EXPORTS = [
     "gsim_db_bit_counts", "gsim_db_overlap_sums", "gsim_isim", "gsim_isim_complement",
     "gsim_db_assign", "gsim_db_label_counts", "gsim_label_centroids", "gsim_db_kmeans",
     "gsim_db_label_sums", "gsim_label_silhouette", "gsim_label_medoids",
+    "gsim_labelset_create", "gsim_labelset_sizes", "gsim_labelset_destroy", "gsim_db_search_labels",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -382,6 +389,11 @@ def load():
         "gsim_label_silhouette": (C.c_int, [u32p, C.POINTER(C.c_uint64), u32p, C.POINTER(C.c_uint64), u32p, C.c_uint64, C.c_uint32,
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "gsim_label_medoids": (C.c_int, [u32p, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, u32p]),
+        "gsim_labelset_create": (C.c_int, [vp, u32p, C.c_uint32, C.POINTER(vp)]),
+        "gsim_labelset_sizes": (C.c_int, [vp, u32p, u64p, u64p]),
+        "gsim_labelset_destroy": (C.c_int, [vp]),
+        "gsim_db_search_labels": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, C.c_uint64,
+                                            vp, u32p, u32p, u64p, u64p, vp, u32p, C.POINTER(GsimLabelSearchStats)]),
         "gsim_db_kmeans": (C.c_int, [vp, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, u32p, u32p,
                                      C.POINTER(C.c_float), u32p, C.POINTER(GsimKmeansStats)]),
         "gsim_last_error": (C.c_char_p, []),
@@ -475,6 +487,41 @@ class RowSet:
         if getattr(self, "_h", None):
             self._L.gsim_rowset_destroy(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LabelSet:
+    """``gsim_labelset``: a labelling of one :class:`Table` on the device (Table.labelset makes it, Table.search_labels searches by
+    it).  It lives in the table's device memory: close it (or drop it) before the table."""
+
+    def __init__(self, table, handle, nlabels):
+        self._L = table._L
+        self._h = handle
+        self._table = table  # (keeps the handle it belongs to alive)
+        self.nlabels = int(nlabels)
+
+    def sizes(self):
+        """-> (sizes uint32 [nlabels], rows whose label is not LABEL_NONE, labels with at least one row)"""
+        sizes = np.zeros(self.nlabels, dtype=np.uint32)
+        labelled, nonempty = C.c_uint64(0), C.c_uint64(0)
+        check(self._L.gsim_labelset_sizes(self._h, _u32(sizes), C.byref(labelled), C.byref(nonempty)))
+        return sizes, labelled.value, nonempty.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.gsim_labelset_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:
@@ -1009,6 +1056,42 @@ class Table:
         out = [hits[i, :counts[i]].copy() for i in range(nq)], approx
         if stats:
             out += ({f: getattr(st, f) for f, _ in GsimRowsetStats._fields_},)
+        return out
+
+    def labelset(self, labels, nlabels) -> LabelSet:
+        """gsim_labelset_create: labels[r] is the label of table row r (without the row base): below `nlabels`, or LABEL_NONE for a
+        row that belongs nowhere -- the outputs of :meth:`leader`, :meth:`dbscan`, :meth:`hdbscan`, :meth:`kmeans`, :meth:`maxmin`
+        with assign=True and :func:`butina` go in as they are."""
+        lab = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+        if len(lab) != self.count():
+            raise GsimError(-1, "labels: %d entries for %d rows" % (len(lab), self.count()))
+        h = C.c_void_p()
+        check(self._L.gsim_labelset_create(self._h, _u32(lab) if len(lab) else None, nlabels, C.byref(h)))
+        return LabelSet(self, h, nlabels)
+
+    def search_labels(self, labelset, queries, k, cutoff=0.0, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, launch_rows=0, per_label=False,
+                      stats=False):
+        """gsim_db_search_labels: per query the best kept row of every label, best labels first -> a dict of arrays:
+        ``hits`` (HIT_DTYPE [nq, max(k, 1)]), ``hit_labels`` (uint32, the same shape), ``counts`` (uint32 [nq]: the valid entries of
+        both), ``approx`` (uint64 [nq]: labels with a kept row), ``rows_kept`` (uint64 [nq]); with per_label=True also ``label_best``
+        (HIT_DTYPE [nq, nlabels]; row 0xFFFFFFFF for a label without a kept row) and ``label_kept`` (uint32 [nq, nlabels]); with
+        stats=True ``stats``, the call's gsim_label_search_stats as a dict."""
+        q = np.ascontiguousarray(queries, dtype=np.uint32).reshape(-1, self.W)
+        nq = q.shape[0]
+        u64p = C.POINTER(C.c_uint64)
+        out = {"hits": np.zeros((nq, max(k, 1)), dtype=HIT_DTYPE), "hit_labels": np.zeros((nq, max(k, 1)), dtype=np.uint32),
+               "counts": np.zeros(nq, dtype=np.uint32), "approx": np.zeros(nq, dtype=np.uint64), "rows_kept": np.zeros(nq, dtype=np.uint64)}
+        if per_label:
+            out["label_best"] = np.zeros((nq, labelset.nlabels), dtype=HIT_DTYPE)
+            out["label_kept"] = np.zeros((nq, labelset.nlabels), dtype=np.uint32)
+        st = GsimLabelSearchStats()
+        check(self._L.gsim_db_search_labels(self._h, labelset._h, _u32(q) if nq else None, nq, k, cutoff, metric, alpha, beta, int(launch_rows),
+                                            out["hits"].ctypes.data_as(C.c_void_p), _u32(out["hit_labels"]), _u32(out["counts"]),
+                                            out["approx"].ctypes.data_as(u64p), out["rows_kept"].ctypes.data_as(u64p),
+                                            out["label_best"].ctypes.data_as(C.c_void_p) if per_label else None,
+                                            _u32(out["label_kept"]) if per_label else None, C.byref(st)))
+        if stats:
+            out["stats"] = {f: getattr(st, f) for f, _ in GsimLabelSearchStats._fields_}
         return out
 
     def search_group(self, queries, k, mode=GROUP_MAX, cutoff=0.0, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, stats=False):

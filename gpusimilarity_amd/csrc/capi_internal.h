@@ -229,6 +229,18 @@ struct gsim_rowset {
     gsim_host::DevBuf<uint32_t> d_list; // count rows, ascending, without the row base
 };
 
+// A label set (gsim_labelset_*, capi_label_search.cpp): device memory of the handle it was made for, immutable.
+struct gsim_labelset {
+    gsim_db* owner = nullptr;
+    int device = 0;
+    uint64_t nrows = 0;          // rows of the owner's table when the set was made
+    uint32_t nlabels = 0;
+    uint64_t labelled = 0;       // rows whose label is not GSIM_LABEL_NONE
+    uint64_t nonempty = 0;       // labels with at least one row
+    std::vector<uint32_t> sizes; // nlabels, counted on the host
+    gsim_host::DevBuf<uint32_t> d_labels; // nrows labels
+};
+
 struct gsim_db {
     uint32_t fp_bits = 0;
     uint32_t W = 0;

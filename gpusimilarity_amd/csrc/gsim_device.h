@@ -769,6 +769,43 @@ hipError_t launch_group_scan(const ScanArgs& a, const ScanGeometry& g, const Gro
 // Behind the tail: `which` of hits [h0, h1) of a block whose header carries flag 1 (device-side test; ga.c0 / c1 / first unused).
 hipError_t launch_group_which(const ScanArgs& a, const GroupArgs& ga, uint32_t row_base, void* block, uint32_t h0, uint32_t h1, hipStream_t s);
 
+// ---- label-grouped search (gsim_label_search.hip, gsim_db_search_labels) -----------------------------------------------------------
+constexpr uint32_t kLabelScanWavesPerCu = 16; // every launch of the scan keeps this many waves on a compute unit, whatever its route
+constexpr uint32_t kLabelLdsBudget = 144u * 1024u; // route LDS: the largest per-workgroup table (of the CU's 160 KiB)
+struct LabelSearchArgs {
+    const void* rows;        // device, nrows x W words
+    uint64_t nrows;
+    uint32_t W;
+    const uint32_t* labels;  // device, nrows labels (< nlabels, or GSIM_LABEL_NONE)
+    uint32_t nlabels;
+    const uint32_t* queries; // device, the pass's nq x W words
+    const uint32_t* qpop;    // device, their popcounts
+    uint32_t nq;
+    float cutoff;
+    int metric;
+    float alpha, beta;
+    unsigned long long* best; // device, nq x nlabels candidate keys (make_key; 0: no row yet), carried from launch to launch
+    uint32_t* kept;           // device, nq x nlabels kept rows -- or NULL: not counted (cutoff <= 0, or nobody asked)
+    uint64_t c0, c1;          // this launch: chunks [c0, c1) of label_chunk_rows(W) rows
+    uint32_t nwaves;          // waves of the grid: chunk c belongs to wave c % nwaves
+    uint32_t block;           // threads of a workgroup: 256, 512 or 1024
+    uint32_t lds_bytes;       // route LDS: the workgroup's table, nq x nlabels x (8, + 4 when counting) bytes; 0: route global
+};
+uint32_t label_chunk_rows(uint32_t W);
+// the threads of a workgroup whose LDS table has `lds_bytes` (0: route global), so that kLabelScanWavesPerCu waves fit a compute unit
+uint32_t label_block_threads(uint32_t lds_bytes);
+hipError_t launch_label_scan(const LabelSearchArgs& a, hipStream_t s);
+// Behind the last scan launch, per query of the pass: label_best[q, l] (the hit of best[q, l]: common and popc_db again from the row,
+// `row` with the row base; {0xFFFFFFFF, 0, 0, 0} where best is 0), totals[2 q] += labels with a row, totals[2 q + 1] += kept[q, l]
+// (not with kept == NULL)
+hipError_t launch_label_finish(const LabelSearchArgs& a, uint32_t row_base, void* label_best, unsigned long long* totals, hipStream_t s);
+// best[0 .. nlabels) of one query, descending, into sorted (rocprim's radix sort; tmp from label_rank_bytes)
+hipError_t label_rank_bytes(uint32_t nlabels, size_t* bytes);
+hipError_t launch_label_rank(void* tmp, size_t tmp_bytes, const unsigned long long* best, unsigned long long* sorted, uint32_t nlabels, hipStream_t s);
+// hits[i], hit_labels[i] for i < kk: the label of sorted[i]'s row and that label's label_best; a zero key ends the list
+hipError_t launch_label_emit(const unsigned long long* sorted, const uint32_t* labels, const void* label_best, uint32_t kk, void* hits,
+                             uint32_t* hit_labels, hipStream_t s);
+
 // ---- leader (sphere-exclusion) clustering (gsim_leader.hip, gsim_db_leader) --------------------------------------------------------
 constexpr uint32_t kLeaderMaxRound = 4096; // largest GSIM_LEADER_ROUND (the resolve's leader mask: one 64-bit word per lane of a wave)
 // ctl words of a call (device memory; the host reads them once per round)

@@ -1384,6 +1384,72 @@ int gsim_label_silhouette(const uint32_t* labels, const uint64_t* own_q, const u
 int gsim_label_medoids(const uint32_t* labels, const uint64_t* own_q, uint64_t n, uint32_t nlabels,
                        uint32_t* medoid /* nlabels */);
 
+/* ---- label-grouped search: the best hit and the hit count of every cluster ------------------------------------------------------- */
+/* A gsim_labelset is a labelling of ONE single-shard, unfolded handle on the device -- the output of gsim_butina, gsim_db_leader,
+ * gsim_db_components / gsim_mst_cut, gsim_db_dbscan, gsim_db_hdbscan, gsim_db_kmeans or gsim_db_maxmin's `nearest`, as it is --;
+ * gsim_db_search_labels answers, per query and in one pass over the table, "the best hit of every cluster, best clusters first" (the
+ * diverse hit list) and "how many hits has each cluster above the cutoff" (the enrichment).  It is gsim_db_search_group transposed:
+ * that call reduces over the queries per row, this one over the rows per label.  No counterpart in the reference.
+ * gsim_db_search_labels, THE RESULT RULE, per query q (labels[r] is the label of table row r, without the row base):
+ *   - pair score: gsim_db_search's -- score = metric(query, row), then score = score >= cutoff ? score : 0, NaN becoming 0;
+ *   - a row labelled GSIM_LABEL_NONE is never scored, kept or counted;
+ *   - the kept rows are all labelled rows when cutoff <= 0, else the labelled rows with score != 0;
+ *   - label_kept[q, l] (or NULL) is the number of kept rows with label l: with cutoff <= 0 that is sizes[l].  rows_kept[q] (or NULL) is
+ *     their sum over l; with no GSIM_LABEL_NONE row it equals gsim_db_search's approx;
+ *   - label_best[q, l] (or NULL) is the kept row of label l that comes first in (score descending, row ascending) order, as a gsim_hit:
+ *     `row` includes the row base, `score`, `common` and `popc_db` are bit for bit what gsim_db_search returns for that row.  A label
+ *     without a kept row gets {row = 0xFFFFFFFF, score = 0, common = 0, popc_db = 0};
+ *   - approx[q] (or NULL) is the number of labels with at least one kept row;
+ *   - hits[q * k ..] are the first min(k, approx[q]) label bests in (score descending, row ascending) order, hit_labels[q * k ..] their
+ *     labels, counts[q] their number.  k == 0 is legal and returns no hits; k is the stride, as in gsim_db_search.
+ * Identities the rule implies:
+ *   - with labels[r] = r the call returns gsim_db_search's hits, counts and approx byte for byte, and hit_labels = row - row_base;
+ *   - with one label it returns gsim_db_search at k = 1;
+ *   - label_best[q, l] and label_kept[q, l] are the hit and the approx of gsim_db_search_rows at k = 1 on the row set
+ *     {r : labels[r] == l}.
+ * Metrics: GSIM_METRIC_TANIMOTO, and GSIM_METRIC_TVERSKY with any finite alpha >= 0, beta >= 0 (no streaming filter is involved, so
+ * scores above 1 are harmless: the candidate key orders any float).
+ * Lifetime: a label set belongs to the handle it was made for, takes 4 bytes per table row of that handle's device memory, is
+ * immutable and serves any number of searches; destroy it before its handle.  gsim_labelset_sizes: sizes[l] = rows with label l,
+ * *labelled (or NULL) = rows whose label is not GSIM_LABEL_NONE, *nonempty (or NULL) = labels with at least one row.
+ * Execution: on the handle's stream under the one-call-at-a-time rule.  Several queries may share a table pass -- an execution detail:
+ * every query gets what a call with nq = 1 returns.  Per pass the table of (query, label) entries lives either in every workgroup's LDS
+ * (while one query's nlabels x 8 bytes, 12 when rows are counted under a cutoff, fit 144 KiB) or in global memory; the output is
+ * byte-identical from run to run and depends on neither the route nor launch_rows.  launch_rows: a scan launch reads at most this
+ * many rows, in whole chunks and at least one chunk; 0: sized by the row width and the queries of the pass, as gsim_db_search_group
+ * sizes its launches.  There is no environment knob.  The call leaves the search state as it found it: a gsim_db_search before and
+ * after returns identical bytes, the back-off counters and the lanes are untouched.  Device memory of a call: the queries are answered
+ * in tiles of at most 16 (fewer where 16 x nlabels exceeds 2^27), a tile takes tile x nlabels x 24 bytes, and the ranking nlabels x 8
+ * bytes plus the radix sort's scratch (about as much again); every temporary is freed on return.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / out / ls / hits / hit_labels / counts, NULL labels with a non-empty
+ * table, NULL queries with nq > 0, nlabels == 0, a label >= nlabels other than GSIM_LABEL_NONE, a label set made for another handle,
+ * an unknown metric, Tversky alpha / beta negative or not finite, rows wider than 4096 bits, a table of 2^32 rows or more.  *out is
+ * cleared on failure.  GSIM_ERR_STATE: a table not on a GPU, a folded table, a multi-shard handle.  GSIM_ERR_NOMEM: the call's device
+ * memory cannot be had; nothing leaked.  nq == 0 and an empty table: GSIM_OK. */
+typedef struct gsim_labelset gsim_labelset;
+typedef struct {
+    uint64_t queries;       /* nq                                                                                     */
+    uint64_t labels;        /* nlabels                                                                                */
+    uint64_t passes;        /* passes over the table                                                                  */
+    uint64_t passes_lds;    /* ... whose (query, label) table lived in the workgroups' LDS                            */
+    uint64_t passes_global; /* ... in global memory                                                                   */
+    uint64_t launches;      /* kernel launches: the scans', a finish per tile, a sort and an emission per query       */
+    double scan_ms;         /* HIP events: all scan launches                                                          */
+    double finish_ms;       /* ... the finish, the ranking, the emission                                              */
+    double d2h_ms;          /* ... the outputs to the host                                                            */
+    double wall_ms;         /* the whole call, host clock                                                             */
+} gsim_label_search_stats;
+int gsim_labelset_create(gsim_db* db, const uint32_t* labels /* host, one per table row */, uint32_t nlabels, gsim_labelset** out);
+int gsim_labelset_sizes(const gsim_labelset* ls, uint32_t* sizes /* nlabels */, uint64_t* labelled /* or NULL */, uint64_t* nonempty /* or NULL */);
+int gsim_labelset_destroy(gsim_labelset* ls);
+int gsim_db_search_labels(gsim_db* db, const gsim_labelset* ls, const uint32_t* queries, uint32_t nq, uint32_t k,
+                          float cutoff, int metric, float alpha, float beta,
+                          uint64_t launch_rows /* 0 = automatic */,
+                          gsim_hit* hits /* nq x k */, uint32_t* hit_labels /* nq x k */, uint32_t* counts /* nq */,
+                          uint64_t* approx /* nq, or NULL */, uint64_t* rows_kept /* nq, or NULL */,
+                          gsim_hit* label_best /* nq x nlabels, or NULL */, uint32_t* label_kept /* nq x nlabels, or NULL */,
+                          gsim_label_search_stats* stats /* or NULL */);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
