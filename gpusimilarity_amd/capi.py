@@ -207,6 +207,19 @@ class GsimLabelSearchStats(C.Structure):
                 ("d2h_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
+LINKAGE_COMPLETE = 0
+LINKAGE_AVERAGE = 1
+LINKAGE_MAX_ROWS = 65536
+LINKAGE_MERGE_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("left", np.uint32), ("right", np.uint32), ("size", np.uint32),
+                                ("score", np.float32), ("sum_q", np.uint64)])
+
+
+class GsimLinkageStats(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("merges", C.c_uint64), ("scans", C.c_uint64), ("chain_max", C.c_uint64), ("launches", C.c_uint64),
+                ("launch_steps", C.c_uint64), ("matrix_ms", C.c_double), ("chain_ms", C.c_double), ("order_ms", C.c_double),
+                ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -243,6 +256,7 @@ EXPORTS = [
     "gsim_db_assign", "gsim_db_label_counts", "gsim_label_centroids", "gsim_db_kmeans",
     "gsim_db_label_sums", "gsim_label_silhouette", "gsim_label_medoids",
     "gsim_labelset_create", "gsim_labelset_sizes", "gsim_labelset_destroy", "gsim_db_search_labels",
+    "gsim_db_linkage", "gsim_linkage",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -394,6 +408,9 @@ def load():
         "gsim_labelset_destroy": (C.c_int, [vp]),
         "gsim_db_search_labels": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, C.c_uint64,
                                             vp, u32p, u32p, u64p, u64p, vp, u32p, C.POINTER(GsimLabelSearchStats)]),
+        "gsim_db_linkage": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint32, vp, u64p,
+                                      C.POINTER(GsimLinkageStats)]),
+        "gsim_linkage": (C.c_int, [C.POINTER(C.c_float), C.c_uint64, C.c_uint64, C.c_int, vp, u64p, u64p]),
         "gsim_db_kmeans": (C.c_int, [vp, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, u32p, u32p,
                                      C.POINTER(C.c_float), u32p, C.POINTER(GsimKmeansStats)]),
         "gsim_last_error": (C.c_char_p, []),
@@ -1007,6 +1024,23 @@ class Table:
         stats = {f: getattr(st, f) for f, _ in GsimLabelSumsStats._fields_}
         return own[:n], (None if own_only else other[:n]), (None if own_only else other_q[:n]), sizes[:int(nlabels)], stats
 
+    def linkage(self, linkage, row_begin=0, row_end=None, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, launch_steps=0):
+        """gsim_db_linkage: the complete-linkage (LINKAGE_COMPLETE) or average-linkage (LINKAGE_AVERAGE) dendrogram of the rows
+        [row_begin, row_end), at most LINKAGE_MAX_ROWS of them -> (merges, stats dict); merges is a structured array
+        (LINKAGE_MERGE_DTYPE) of n - 1 entries in the order of execution: a < b the smallest rows of the two clusters (row_begin
+        and the row base added), left / right in scipy's numbering within the range, size, score (complete: the minimum; average:
+        the mean of the quantised scores) and sum_q (the exact sum of q = floor(score * 2^31) over the pairs between the two).
+        :func:`linkage_edges` makes them :func:`mst_cut`'s input, :func:`linkage_to_scipy` scipy's Z matrix."""
+        if row_end is None:
+            row_end = self.count()
+        n = max(row_end - row_begin, 0)
+        merges = np.zeros(max(n - 1, 1), dtype=LINKAGE_MERGE_DTYPE)
+        nm = C.c_uint64(0)
+        st = GsimLinkageStats()
+        check(self._L.gsim_db_linkage(self._h, row_begin, row_end, linkage, metric, alpha, beta, int(launch_steps), merges.ctypes.data,
+                                      C.byref(nm), C.byref(st)))
+        return merges[:nm.value].copy(), {f: getattr(st, f) for f, _ in GsimLinkageStats._fields_}
+
     def kmeans(self, init, max_iter=20, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0):
         """gsim_db_kmeans: Lloyd's iteration from the m centres `init` over the whole table -- assign, count, majority-vote centroid,
         until the labels repeat or `max_iter` assignments were made -> (centres uint32 [m, words], label uint32 [N], score float32
@@ -1284,6 +1318,45 @@ def mst_cut(edges, nrows, t):
     nc = C.c_uint64(0)
     check(load().gsim_mst_cut(ptr, len(edges), n, t, _u32(component_of), _u32(first_row), _u32(sizes), C.byref(nc)))
     return component_of, first_row[:nc.value].copy(), sizes[:nc.value].copy()
+
+
+def linkage(scores, kind):
+    """gsim_linkage (host code): the rule of gsim_db_linkage on a square float32 matrix of scores in [0, 1], of which only the
+    entries i < j are read -> (merges (LINKAGE_MERGE_DTYPE, rows without any offset), the chain's nearest-neighbour scans)."""
+    s = np.ascontiguousarray(scores, dtype=np.float32)
+    if s.size == 0:
+        s = s.reshape(0, 0)
+    if s.ndim != 2 or s.shape[0] != s.shape[1]:
+        raise GsimError(-1, "linkage: the scores must be a square matrix")
+    n = s.shape[0]
+    merges = np.zeros(max(n - 1, 1), dtype=LINKAGE_MERGE_DTYPE)
+    nm, scans = C.c_uint64(0), C.c_uint64(0)
+    check(load().gsim_linkage(_f32(s) if n else None, n, n, kind, merges.ctypes.data, C.byref(nm), C.byref(scans)))
+    return merges[:nm.value].copy(), scans.value
+
+
+def linkage_edges(merges, offset=0):
+    """The merges of :meth:`Table.linkage` / :func:`linkage` as MST_EDGE_DTYPE edges (a - offset, b - offset, score) in their order:
+    :func:`mst_cut` of them at t gives the flat clusters at t.  offset: row_begin plus the row base of a device call."""
+    m = np.ascontiguousarray(merges, dtype=LINKAGE_MERGE_DTYPE).reshape(-1)
+    edges = np.zeros(len(m), dtype=MST_EDGE_DTYPE)
+    edges["a"] = m["a"] - np.uint32(offset)
+    edges["b"] = m["b"] - np.uint32(offset)
+    edges["score"] = m["score"]
+    return edges
+
+
+def linkage_to_scipy(merges, n):
+    """The merges as scipy's linkage matrix Z: float64 [n - 1, 4] of (left, right, distance = 1 - score, size)."""
+    m = np.ascontiguousarray(merges, dtype=LINKAGE_MERGE_DTYPE).reshape(-1)
+    if len(m) != max(int(n) - 1, 0):
+        raise GsimError(-1, "linkage: %d merges for %d rows" % (len(m), n))
+    z = np.zeros((len(m), 4), dtype=np.float64)
+    z[:, 0] = m["left"]
+    z[:, 1] = m["right"]
+    z[:, 2] = 1.0 - m["score"].astype(np.float64)
+    z[:, 3] = m["size"]
+    return z
 
 
 def mreach_mst(indptr, indices, scores, min_pts, nrows=None):

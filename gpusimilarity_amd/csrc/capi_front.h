@@ -90,6 +90,22 @@ template <class Fn> int on_one_shard(gsim_db* db, const char* nomem_what, Fn&& c
     return rc;
 }
 
+// ---- the core of the score matrices (capi_scores.cpp), which gsim_db_linkage (capi_linkage.cpp) fills its matrix with ----
+
+struct ScoresCall {
+    uint64_t r0, nr; // the table rows [r0, r0 + nr)
+    int metric;
+    float alpha, beta;
+    float* out;      // host output (nullptr: the device call)
+    float* d_out;    // device output
+    uint64_t ld;
+    gsim_scores_stats* stats;
+};
+
+// left rows d_left[0 .. nl) (W words each, on s's device) against s's table rows [c.r0, c.r0 + c.nr): the launch plan, the
+// launches and -- with host output -- the staging slabs; waits for the stream
+int scores(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, const ScoresCall& c);
+
 // ---- the label sort of gsim_db_label_counts and gsim_db_label_sums (capi_labels.cpp; the device side is gsim_labels.hip) ----
 
 // keys = min(label, nlabels) and row numbers, one stable radix sort, the segment starts: the rows of a label become one ascending

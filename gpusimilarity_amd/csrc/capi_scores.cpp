@@ -38,15 +38,7 @@ std::vector<ScoresLaunch> plan_scores(uint64_t nl, uint64_t nr, uint32_t WP, lon
     return out;
 }
 
-struct ScoresCall {
-    uint64_t r0, nr; // the table rows [r0, r0 + nr)
-    int metric;
-    float alpha, beta;
-    float* out;      // host output (nullptr: the device call)
-    float* d_out;    // device output
-    uint64_t ld;
-    gsim_scores_stats* stats;
-};
+} // namespace
 
 // left rows d_left[0 .. nl) (W words each, on s's device) against s's table rows [c.r0, c.r0 + c.nr)
 int scores(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, const ScoresCall& c)
@@ -140,6 +132,9 @@ int scores(gsim_db* db, Shard& s, const uint32_t* d_left, uint64_t nl, const Sco
     if (c.stats) *c.stats = ss;
     return GSIM_OK;
 }
+
+namespace
+{
 
 // what every entry point checks before any device state (`handle`: the left rows are `left`'s; else the queries entry, nl = nq)
 int check_scores_args(gsim_db* db, bool handle, const gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, uint64_t rrow_begin, uint64_t rrow_end,

@@ -848,6 +848,40 @@ hipError_t launch_leader_pass(const LeaderArgs& a, const uint32_t* list, uint64_
 hipError_t launch_leader_compact(const LeaderArgs& a, void* tmp, size_t tmp_bytes, const uint32_t* list_in, uint64_t n, uint32_t* list_out,
                                  hipStream_t s);
 
+// ---- complete- and average-linkage dendrograms (gsim_linkage.hip, gsim_db_linkage) -----------------------------------------
+constexpr int kLinkBlock = 1024;      // the one workgroup of the chain kernel
+constexpr uint32_t kLinkTile = 32;    // the mirror kernel's square tile: a slab starts at a multiple of it
+constexpr uint32_t kLinkCtlWords = 16;
+constexpr uint32_t kLinkCtlLen = 0;      // ctl words: elements on the chain
+constexpr uint32_t kLinkCtlMerged = 1;   // ... merges executed
+constexpr uint32_t kLinkCtlScans = 2;    // ... nearest-neighbour scans
+constexpr uint32_t kLinkCtlChainMax = 3; // ... the longest the chain has been
+constexpr uint32_t kLinkCtlDone = 4;     // ... 1 once n - 1 merges are executed, 2: a scan found no live slot (never)
+constexpr uint32_t kLinkCtlClk = 8;      // ... the last launch's four clock words (as KnnArgs.clk)
+struct LinkRaw {                 // a merge as the chain executed it
+    uint32_t a, b;               // the slots (= smallest rows within the range), a < b
+    uint32_t size_a, size_b;
+    unsigned long long v;        // complete linkage: the bits of the minimum; average linkage: Q
+};
+struct LinkArgs {
+    void* mat;                   // n rows of ld entries: float (complete linkage) or unsigned long long (average linkage), symmetric
+    uint64_t ld;                 // a multiple of 4, >= n: every row starts on 16 bytes
+    uint32_t n;
+    int average;
+    uint32_t* size;              // ld entries: the rows of the cluster in slot z, 0 for a dead slot and for the padding
+    uint32_t* chain;             // n entries
+    LinkRaw* raw;                // n - 1 entries
+    unsigned long long* ctl;     // kLinkCtlWords
+};
+// size = 1 for z < n, 0 for the padding; ctl zeroed
+hipError_t launch_link_init(const LinkArgs& a, hipStream_t s);
+// in: `rows` rows of ld_in floats, the scores of the range's rows [first, first + rows) against its rows [col0, n), col0 <= first;
+// `first` a multiple of kLinkTile.  For i < j both mat[i][j] and mat[j][i] become s(i, j) (complete linkage, in place: in == mat, col0 == first == 0, rows == n) or
+// q(s(i, j)) (average linkage); the lower triangle of `in` is not read.
+hipError_t launch_link_mirror(const LinkArgs& a, const float* in, uint64_t ld_in, uint64_t col0, uint64_t first, uint64_t rows, hipStream_t s);
+// at most `steps` > 0 chain steps (a scan, then a push or a merge)
+hipError_t launch_link_chain(const LinkArgs& a, uint32_t steps, hipStream_t s);
+
 hipError_t launch_generate(void* rows, uint64_t seed, int kind, uint64_t first_row, uint64_t nrows,
                            uint32_t W, hipStream_t s);
 

@@ -1450,6 +1450,79 @@ int gsim_db_search_labels(gsim_db* db, const gsim_labelset* ls, const uint32_t* 
                           gsim_hit* label_best /* nq x nlabels, or NULL */, uint32_t* label_kept /* nq x nlabels, or NULL */,
                           gsim_label_search_stats* stats /* or NULL */);
 
+/* ---- complete- and average-linkage dendrograms ------------------------------------------------------------------------------------ */
+/* gsim_db_mst is single linkage, which chains.  gsim_db_linkage builds the two other dendrograms asked for on a few thousand to a few
+ * tens of thousands of rows -- cluster representatives from gsim_label_medoids, a hit list, a screening deck --: complete linkage and
+ * average linkage (UPGMA), on the dense similarity matrix, which never leaves the device.  No counterpart in the reference.
+ * gsim_db_linkage, THE RESULT RULE, on the n = row_end - row_begin rows of a single-shard, unfolded handle, n <= GSIM_LINKAGE_MAX_ROWS:
+ *   - linkages: GSIM_LINKAGE_COMPLETE, GSIM_LINKAGE_AVERAGE.  Metrics: those of gsim_db_mst -- GSIM_METRIC_TANIMOTO, or
+ *     GSIM_METRIC_TVERSKY with alpha == beta, finite and >= 0;
+ *   - leaves: s(i, j) for i < j is the score gsim_db_scores gives with the LOWER row on the left; 0 / 0 is 0.0f.  Every pair has a
+ *     score in [0, 1], so the dendrogram is always complete: exactly n - 1 merges (n >= 1);
+ *   - the similarity of two clusters, complete linkage: the MINIMUM of s over the pairs between them -- an f32, exact;
+ *   - ... average linkage: the exact fraction Q / (|A| |B|), Q the sum of q(s) over the pairs between them, q(s) = (uint32) floor(s *
+ *     2^31) as in gsim_db_label_sums.  Means are compared as exact fractions by cross-multiplication in 128 bits, never as rounded
+ *     doubles;
+ *   - a cluster is identified by its smallest row.  At every step the pair of live clusters (a < b) that comes first in ORDER L =
+ *     (similarity descending, a ascending, b ascending) is merged.  L is total, so the dendrogram is unique, ties included;
+ *   - merges[m], m = 0 .. n - 2, in the order of execution: a, b the smallest rows of the two clusters, a < b, with row_begin and the
+ *     row base added; left, right in scipy's numbering WITHIN the range, as gsim_mst_merge -- leaf i is id i, merge m creates id
+ *     n + m, `left` is the cluster of `a`; size the new cluster's rows;
+ *     score, complete linkage: the minimum, exact; sum_q = q(score);
+ *     score, average linkage: (float) (((double) sum_q / (double) pairs) * 0x1p-31) with pairs = |A| |B|, one rounding per operation;
+ *     sum_q = Q, exact.
+ * What the rule implies:
+ *   - scores never increase along the list (both linkages are reducible: a merged cluster is no closer to a third than the closer of
+ *     its halves was);
+ *   - the edges (a, b, score) given to gsim_mst_cut(t) (without the row offsets) are the flat clusters at t in gsim_components'
+ *     numbering: no cut call of its own is needed;
+ *   - the output is byte-identical from run to run and does not depend on launch_steps.
+ * Execution: the matrix-core pass of gsim_db_scores fills the matrix; ONE workgroup then runs the nearest-neighbour chain on it (a
+ * scan of one matrix row per step), at most launch_steps steps to a launch (0: sized so that a launch stays near 5 ms), and the host
+ * puts the n - 1 merges it executed into order L's sequence.  On the handle's stream under the
+ * one-call-at-a-time rule, every temporary freed, the search state left as it was found.  Device memory of a call, with n4 = n rounded
+ * up to a multiple of 4: complete linkage 4 B x n x n4 (the score matrix itself); average linkage 8 B x n x n4 (the Q matrix) plus one
+ * staging slab of f32 scores (GSIM_SCORES_STAGE_BYTES, at least 32 rows); 32 B x n of state (sizes, chain, executed merges); and what
+ * the score pass takes: popcounts and, where the width is not 256, 512, ... 4096 bits, the zero-padded copy of the rows.  n = 65 536
+ * with average linkage is 32 GiB.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / nmerges, row_begin > row_end or row_end past the count, n above
+ * GSIM_LINKAGE_MAX_ROWS, an unknown linkage or metric, Tversky alpha != beta, negative or not finite, rows wider than 4096 bits, NULL
+ * merges with n > 1.  n == 0 and n == 1: GSIM_OK, *nmerges = 0.  GSIM_ERR_STATE: a table not on a GPU, a folded table, a multi-shard
+ * handle.  GSIM_ERR_NOMEM: the call's device memory cannot be had; nothing leaked. */
+#define GSIM_LINKAGE_COMPLETE 0
+#define GSIM_LINKAGE_AVERAGE 1
+#define GSIM_LINKAGE_MAX_ROWS 65536u
+typedef struct {
+    uint32_t a, b;        /* smallest row of either cluster, a < b, row_begin and row base added */
+    uint32_t left, right; /* scipy numbering within the range, as gsim_mst_merge                 */
+    uint32_t size;
+    float score;
+    uint64_t sum_q;
+} gsim_linkage_merge; /* 32 bytes */
+typedef struct {
+    uint64_t rows;         /* n                                                                                      */
+    uint64_t merges;       /* n - 1                                                                                  */
+    uint64_t scans;        /* nearest-neighbour scans of the chain: one matrix row each                              */
+    uint64_t chain_max;    /* the deepest the chain got                                                              */
+    uint64_t launches;     /* launches of the chain kernel                                                           */
+    uint64_t launch_steps; /* chain steps to a launch: the argument, or what 0 chose                                 */
+    double matrix_ms;      /* host clock, the stream waited for: the score pass and the mirror / widening kernel     */
+    double chain_ms;       /* ... all chain launches                                                                 */
+    double order_ms;       /* ... the host's replay into order L's sequence                                          */
+    double d2h_ms;         /* ... the executed merges to the host                                                    */
+    double wall_ms;        /* the whole call                                                                         */
+    double clock_mhz;      /* as gsim_knn_stats.clock_mhz, over the chain launches                                   */
+} gsim_linkage_stats;
+int gsim_db_linkage(gsim_db* db, uint64_t row_begin, uint64_t row_end, int linkage, int metric, float alpha, float beta,
+                    uint32_t launch_steps /* 0 = automatic */, gsim_linkage_merge* merges /* n - 1 */, uint64_t* nmerges,
+                    gsim_linkage_stats* stats /* or NULL */);
+/* The same rule on a matrix in host memory (host code, no device, no handle, no row base; what gsim_mst is to gsim_db_mst): scores
+ * holds n rows of ld floats of which only the entries i < j are read (-0.0f is read as 0.0f).  *scans (or NULL) is the number of
+ * nearest-neighbour scans the chain took.  GSIM_ERR_INVALID: NULL scores with n > 1, NULL nmerges, NULL merges with n > 1, ld < n,
+ * n above GSIM_LINKAGE_MAX_ROWS, an unknown linkage, a NaN or an entry outside [0, 1] in the upper triangle. */
+int gsim_linkage(const float* scores /* n rows of ld floats, only i < j read */, uint64_t n, uint64_t ld, int linkage,
+                 gsim_linkage_merge* merges /* n - 1 */, uint64_t* nmerges, uint64_t* scans /* or NULL */);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
