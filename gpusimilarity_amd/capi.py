@@ -220,6 +220,24 @@ class GsimLinkageStats(C.Structure):
                 ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
 
 
+SNN_CLOSED = 1  # the lists count their owners (the 1973 paper's convention)
+SNN_EITHER = 2  # jarvis_patrick: one-sided pairs may link too
+SNN_MUTUAL_BIT = 0x80000000
+
+
+class GsimSnnStats(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("k", C.c_uint64), ("entries", C.c_uint64), ("mutual_entries", C.c_uint64),
+                ("links", C.c_uint64 * 8), ("unions", C.c_uint64), ("cas_failed", C.c_uint64), ("launches", C.c_uint64),
+                ("pairs", C.c_uint64), ("inserts", C.c_uint64), ("knn_ms", C.c_double), ("sort_ms", C.c_double), ("link_ms", C.c_double),
+                ("label_ms", C.c_double), ("d2h_ms", C.c_double), ("wall_ms", C.c_double), ("clock_mhz", C.c_double)]
+
+
+def _snn_stats_dict(st):
+    d = {f: getattr(st, f) for f, _ in GsimSnnStats._fields_}
+    d["links"] = list(st.links)
+    return d
+
+
 class GsimError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("gsim error %d: %s" % (code, msg))
@@ -257,6 +275,7 @@ EXPORTS = [
     "gsim_db_label_sums", "gsim_label_silhouette", "gsim_label_medoids",
     "gsim_labelset_create", "gsim_labelset_sizes", "gsim_labelset_destroy", "gsim_db_search_labels",
     "gsim_db_linkage", "gsim_linkage",
+    "gsim_db_snn", "gsim_graph_copy_shared", "gsim_graph_get_snn_stats", "gsim_db_jarvis_patrick", "gsim_snn", "gsim_jarvis_patrick",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -411,6 +430,13 @@ def load():
         "gsim_db_linkage": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint32, vp, u64p,
                                       C.POINTER(GsimLinkageStats)]),
         "gsim_linkage": (C.c_int, [C.POINTER(C.c_float), C.c_uint64, C.c_uint64, C.c_int, vp, u64p, u64p]),
+        "gsim_db_snn": (C.c_int, [vp, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, C.c_uint32, C.POINTER(vp)]),
+        "gsim_graph_copy_shared": (C.c_int, [vp, u32p]),
+        "gsim_graph_get_snn_stats": (C.c_int, [vp, C.POINTER(GsimSnnStats)]),
+        "gsim_db_jarvis_patrick": (C.c_int, [vp, C.c_uint32, u32p, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, C.c_uint32, u32p, u32p,
+                                             u32p, u32p, C.POINTER(GsimSnnStats)]),
+        "gsim_snn": (C.c_int, [u64p, u32p, C.c_uint64, C.c_uint32, u32p]),
+        "gsim_jarvis_patrick": (C.c_int, [u64p, u32p, C.c_uint64, u32p, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p]),
         "gsim_db_kmeans": (C.c_int, [vp, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, u32p, u32p,
                                      C.POINTER(C.c_float), u32p, C.POINTER(GsimKmeansStats)]),
         "gsim_last_error": (C.c_char_p, []),
@@ -856,6 +882,47 @@ class Table:
                   for l in range(nl)]
         return levels, {f: getattr(st, f) for f, _ in GsimComponentsStats._fields_}
 
+    def snn(self, k, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, closed=False, stats=None):
+        """gsim_db_snn: knn(k, cutoff)'s graph of the whole table with the shared-nearest-neighbour count of every entry
+        -> (indptr, indices, scores, shared); shared[e] = |L(i) & L(j)| for the entry e = (i, j) (`closed`: the lists count their
+        owners), with SNN_MUTUAL_BIT set where i is in list j too.  `stats`: a dict that receives the call's gsim_snn_stats."""
+        g = C.c_void_p()
+        check(self._L.gsim_db_snn(self._h, k, cutoff, metric, alpha, beta, SNN_CLOSED if closed else 0, C.byref(g)))
+        try:
+            nnz = C.c_uint64(0)
+            check(self._L.gsim_graph_shape(g, None, C.byref(nnz)))
+            shared = np.empty(nnz.value, dtype=np.uint32)
+            check(self._L.gsim_graph_copy_shared(g, _u32(shared)))
+            if stats is not None:
+                st = GsimSnnStats()
+                check(self._L.gsim_graph_get_snn_stats(g, C.byref(st)))
+                stats.update(_snn_stats_dict(st))
+        except Exception:
+            self._L.gsim_graph_destroy(g)
+            raise
+        return self._take_graph(g, None, None, None) + (shared,)
+
+    def jarvis_patrick(self, k, kmins, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, closed=False, either=False, first_row=True,
+                       sizes=True):
+        """gsim_db_jarvis_patrick: Jarvis-Patrick clustering on knn(k, cutoff)'s lists at an ascending list of kmin values, or one
+        scalar -> (levels, stats dict); levels[l] = (cluster_of uint32 [N], first_row uint32 [nclusters] (+ row base), sizes uint32
+        [nclusters]) for kmins[l], in components()'s numbering; first_row / sizes are None where not asked for.  Two rows link when
+        each is in the other's list (`either`: one of them suffices) and the lists share at least kmin rows (`closed`: the lists count
+        their owners)."""
+        km = np.ascontiguousarray(np.atleast_1d(kmins), dtype=np.uint32).reshape(-1)
+        n, nl = self.count(), len(km)
+        comp = np.empty((max(nl, 1), n), dtype=np.uint32)
+        ncomp = np.zeros(max(nl, 1), dtype=np.uint32)
+        first = np.empty((max(nl, 1), n), dtype=np.uint32) if first_row else None
+        size = np.empty((max(nl, 1), n), dtype=np.uint32) if sizes else None
+        flags = (SNN_CLOSED if closed else 0) | (SNN_EITHER if either else 0)
+        st = GsimSnnStats()
+        check(self._L.gsim_db_jarvis_patrick(self._h, k, _u32(km), nl, cutoff, metric, alpha, beta, flags, _u32(comp), _u32(ncomp),
+                                             _u32(first) if first_row else None, _u32(size) if sizes else None, C.byref(st)))
+        levels = [(comp[l].copy(), first[l, :ncomp[l]].copy() if first_row else None, size[l, :ncomp[l]].copy() if sizes else None)
+                  for l in range(nl)]
+        return levels, _snn_stats_dict(st)
+
     def mst(self, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0):
         """gsim_db_mst: the single-linkage dendrogram as its maximum-similarity spanning forest -> (edges, stats dict); edges is a
         structured array (MST_EDGE_DTYPE: a < b with the row base added, score) in order E = (score descending, a, b); the per-scan
@@ -1256,6 +1323,41 @@ def components(indptr, indices, nrows=None):
     check(load().gsim_components(indptr.ctypes.data_as(C.POINTER(C.c_uint64)), _u32(indices), n, _u32(component_of), _u32(first_row),
                                  _u32(sizes), C.byref(nc)))
     return component_of, first_row[:nc.value].copy(), sizes[:nc.value].copy()
+
+
+def snn(indptr, indices, nrows=None, closed=False):
+    """gsim_snn (host code): the shared-nearest-neighbour count of every entry of a CSR of lists (any lengths, any order) -> shared
+    uint32 [nnz]; shared[e] = |L(i) & L(j)| for e = (i, j) (`closed`: + [j in L(i)] + [i in L(j)]), with SNN_MUTUAL_BIT set where i is
+    in list j (include/gpusim_hip.h states the rule)."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.uint64)
+    indices = np.ascontiguousarray(indices, dtype=np.uint32)
+    n = len(indptr) - 1 if nrows is None else int(nrows)
+    if n < 0 or len(indptr) < n + 1:
+        raise GsimError(-1, "indptr needs nrows + 1 entries")
+    shared = np.empty(int(indptr[n]), dtype=np.uint32)
+    check(load().gsim_snn(indptr.ctypes.data_as(C.POINTER(C.c_uint64)), _u32(indices), n, SNN_CLOSED if closed else 0, _u32(shared)))
+    return shared
+
+
+def jarvis_patrick(indptr, indices, kmins, nrows=None, closed=False, either=False):
+    """gsim_jarvis_patrick (host code): Jarvis-Patrick clustering of a CSR of lists at an ascending list of kmin values, or one
+    scalar -> levels; levels[l] = (cluster_of uint32 [n], first_row uint32 [nclusters], sizes uint32 [nclusters]), clusters numbered
+    in ascending order of their smallest row (include/gpusim_hip.h states the rule)."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.uint64)
+    indices = np.ascontiguousarray(indices, dtype=np.uint32)
+    km = np.ascontiguousarray(np.atleast_1d(kmins), dtype=np.uint32).reshape(-1)
+    n = len(indptr) - 1 if nrows is None else int(nrows)
+    if n < 0 or len(indptr) < n + 1:
+        raise GsimError(-1, "indptr needs nrows + 1 entries")
+    nl = len(km)
+    comp = np.empty((max(nl, 1), n), dtype=np.uint32)
+    first = np.empty((max(nl, 1), n), dtype=np.uint32)
+    size = np.empty((max(nl, 1), n), dtype=np.uint32)
+    nc = np.zeros(max(nl, 1), dtype=np.uint32)
+    flags = (SNN_CLOSED if closed else 0) | (SNN_EITHER if either else 0)
+    check(load().gsim_jarvis_patrick(indptr.ctypes.data_as(C.POINTER(C.c_uint64)), _u32(indices), n, _u32(km), nl, flags, _u32(comp),
+                                     _u32(first), _u32(size), _u32(nc)))
+    return [(comp[l].copy(), first[l, :nc[l]].copy(), size[l, :nc[l]].copy()) for l in range(nl)]
 
 
 def _mst_edges(edges):

@@ -16,11 +16,13 @@ struct gsim_graph {
     std::vector<uint32_t> indices;
     std::vector<float> scores;
     gsim_graph_stats stats{};
-    enum class Kind : uint8_t { kNeighbors, kJoin, kKnn, kKnnJoin }; // who made it: which of the *_get_*_stats accessors answers for it
+    enum class Kind : uint8_t { kNeighbors, kJoin, kKnn, kKnnJoin, kSnn }; // who made it: which of the *_get_*_stats accessors answers for it
     Kind kind = Kind::kNeighbors;
     gsim_join_stats join{}; // kJoin (gsim_db_join / gsim_db_join_queries)
     gsim_knn_stats knn{};   // kKnn (gsim_db_knn, capi_knn.cpp)
     gsim_knn_join_stats knn_join{}; // kKnnJoin (gsim_db_knn_join / gsim_db_knn_queries, capi_knn_join.cpp)
+    gsim_snn_stats snn{};           // kSnn (gsim_db_snn, capi_snn.cpp) ...
+    std::vector<uint32_t> shared;   // ... and its count per entry (gsim_graph_copy_shared)
 };
 
 namespace gsim_host
@@ -162,7 +164,7 @@ int check_scored_csr(const uint64_t* indptr, const uint32_t* indices, const floa
 // Kruskal over the pairs a < b of `all` (sorted here into order E; repeated pairs are harmless) -> edges, in order E; their number
 uint64_t kruskal_in_e(std::vector<gsim_mst_edge>& all, uint64_t nrows, gsim_mst_edge* edges);
 
-// The fold launches of a k-NN plan (capi_knn.cpp; the core pass of capi_hdbscan.cpp runs the same): a's table, lists and cutoff as
+// The fold launches of a k-NN plan (capi_knn.cpp; the core pass of capi_hdbscan.cpp and capi_snn.cpp run the same): a's table, lists and cutoff as
 // the caller set them, every launch with its clock words, HIP events around all of them.
 gsim::KnnArgs knn_args(const PaddedRows& table, uint64_t N, uint64_t rb, uint64_t re, uint32_t WP, uint32_t k, float cutoff, int metric,
                        float alpha, float beta, gsim::KnnEntry* lists, uint32_t* len, unsigned long long* inserts);

@@ -498,6 +498,29 @@ hipError_t launch_mreach_fold(const MreachArgs& a, uint32_t ot0, uint32_t not_, 
 hipError_t launch_mreach_core(const KnnEntry* lists, const uint32_t* len, uint64_t nrows, uint32_t k, float cutoff, float* core,
                               unsigned long long* dense, hipStream_t s);
 
+// ---- shared-nearest-neighbour counts and Jarvis-Patrick links (gsim_snn.hip, gsim_db_snn / gsim_db_jarvis_patrick) -----------------
+constexpr uint32_t kSnnEntries = 0, kSnnMutual = 1, kSnnUnions = 2, kSnnCasFailed = 3, kSnnLinks = 4; // SnnArgs::counters; kSnnLinks + level
+constexpr uint32_t kSnnCounters = kSnnLinks + kCompMaxLevels;
+struct SnnArgs {
+    const KnnEntry* lists;       // nrows x k slots as the fold left them (KnnArgs::lists, all rows as owners)
+    const uint32_t* len;         // entries held per list
+    const uint32_t* nbr;         // nrows x k: every list's rows ascending, padded with 0xFFFFFFFF (launch_snn_sort)
+    uint64_t nrows;
+    uint32_t k;                  // 1 ... GSIM_KNN_MAX_K
+    uint32_t flags;              // GSIM_SNN_CLOSED | GSIM_SNN_EITHER
+    uint32_t nlevels;            // 1 ... kCompMaxLevels (with parent)
+    uint32_t kmins[kCompMaxLevels]; // ascending; [0 .. nlevels)
+    uint32_t* parent;            // nlevels forests of nrows words (gsim_components.hip's protocol), or nullptr: no links
+    uint32_t* shared;            // nrows x k: the count | GSIM_SNN_MUTUAL_BIT of every held entry, or nullptr
+    unsigned long long* counters; // kSnnCounters words, added to
+};
+hipError_t launch_snn_sort(const KnnEntry* lists, const uint32_t* len, uint64_t nrows, uint32_t k, uint32_t* nbr, hipStream_t s);
+// every entry of every list: its count, and its links into the forests (launch_comp_flatten follows)
+hipError_t launch_snn_link(const SnnArgs& a, int num_cus, hipStream_t s);
+// the counts of the held entries to their CSR places, as launch_knn_compact moves indices and scores
+hipError_t launch_snn_compact(const uint32_t* shared, const uint32_t* len, const uint64_t* indptr, uint64_t nrows, uint32_t k, uint32_t* out,
+                              hipStream_t s);
+
 // ---- per-bit column counts and weighted popcounts (gsim_profile.hip, gsim_db_bit_counts / gsim_db_overlap_sums) -------------
 constexpr int kProfileBlock = 256;
 constexpr uint32_t kProfileMaxIters = 4088; // rows one thread can add into its 12 vertical counter planes: a multiple of 8 below 2^12

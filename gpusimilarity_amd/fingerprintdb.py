@@ -197,6 +197,22 @@ class FingerprintDB:
                 members[c].append(r)
         return [(f,) + tuple(m) for f, m in zip(first, members)], noise
 
+    def jarvis_patrick(self, k: int, kmin: int, cutoff: float = 1e-45, metric: int = capi.METRIC_TANIMOTO, alpha: float = 1.0,
+                       beta: float = 1.0, closed: bool = False, either: bool = False):
+        """Jarvis-Patrick clustering (gsim_db_jarvis_patrick): two rows are joined when each is among the other's k nearest
+        neighbours (either=True: one of them suffices) and their neighbour lists share at least `kmin` rows (closed=True: a list
+        counts its owner) -> one tuple per cluster, in ascending order of its smallest row -- that row first, then the other
+        members, ascending (the shape of butina()).  The default cutoff, the smallest positive float, lists every row with a
+        non-zero score."""
+        levels, _ = self._table.jarvis_patrick(int(k), [int(kmin)], float(cutoff), metric, alpha, beta, closed, either, sizes=False)
+        cluster_of, first_row, _ = levels[0]
+        first = first_row.tolist()
+        members = [[] for _ in first]
+        for r, c in enumerate(cluster_of.tolist()):
+            if r != first[c]:
+                members[c].append(r)
+        return [(f,) + tuple(m) for f, m in zip(first, members)]
+
     def search_cpu(self, query, dbkey: str, max_return_count: int, similarity_cutoff: float
                    ) -> Tuple[List[bytes], List[bytes], List[float]]:
         """fingerprintdb_cuda.cpp:20-54 (cutoff ignored, approx not produced)."""

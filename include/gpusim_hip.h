@@ -1523,6 +1523,84 @@ int gsim_db_linkage(gsim_db* db, uint64_t row_begin, uint64_t row_end, int linka
 int gsim_linkage(const float* scores /* n rows of ld floats, only i < j read */, uint64_t n, uint64_t ld, int linkage,
                  gsim_linkage_merge* merges /* n - 1 */, uint64_t* nmerges, uint64_t* scans /* or NULL */);
 
+/* ---- Jarvis-Patrick clustering and shared-nearest-neighbour graphs --------------------------------------------------------------- */
+/* Jarvis-Patrick clustering (Jarvis & Patrick 1973) joins two rows when they are in each other's nearest-neighbour lists and those
+ * lists have enough rows in common; it needs no similarity threshold tuned to the data and works on exactly the lists gsim_db_knn
+ * builds.  Its building block, the shared-nearest-neighbour (SNN) count of two rows, is returned by gsim_db_snn for callers that want
+ * the SNN graph itself.  No counterpart in the reference.
+ * THE RULE, on a single-shard, unfolded handle with N rows:
+ *   - lists: L(i) is the set of rows in list i of gsim_db_knn(db, k, cutoff, metric, alpha, beta, 0, N) -- that call's metrics,
+ *     asymmetric Tversky included, since every list is taken from its owner's side.  i is never in L(i); an all-zero row has an empty
+ *     list and is in nobody's list;
+ *   - shared(i, j) = |L(i) & L(j)|.  With GSIM_SNN_CLOSED the lists count their owners (the 1973 paper's convention):
+ *     shared(i, j) = |L(i) & L(j)| + [j in L(i)] + [i in L(j)].  mutual(i, j): j in L(i) and i in L(j);
+ *   - links: a pair {i, j}, i != j, is a link at level l when it is mutual and shared(i, j) >= kmins[l]; with GSIM_SNN_EITHER "mutual"
+ *     is relaxed to "j in L(i) or i in L(j)".  kmins[0] < kmins[1] < ..., 1 <= nlevels <= GSIM_COMPONENTS_MAX_LEVELS, each value in
+ *     [0, k], or [0, k + 2] with GSIM_SNN_CLOSED.  kmin = 0 without GSIM_SNN_EITHER is the mutual k-NN graph.  Level 0 is the loosest;
+ *   - the partition at level l: the connected components of the graph on the N rows whose edges are the links of level l;
+ *   - numbering and outputs: exactly gsim_db_components' -- the clusters of a level are numbered in ascending order of their smallest
+ *     row; cluster_of[l * N + i], nclusters[l], first_row[l * N + c] (or NULL; + the handle's row base), sizes[l * N + c] (or NULL);
+ *     the entries at and after nclusters[l] of a first_row / sizes stripe are left untouched.
+ * Consequences: level l + 1 refines level l; a single-level call and the matching stripe of a multi-level call are byte-identical; the
+ * output is byte-identical from run to run and does not depend on GSIM_KNN_LAUNCH_PAIRS (the lists are unique because gsim_db_knn's
+ * order is total); gsim_db_jarvis_patrick equals gsim_jarvis_patrick applied to gsim_db_knn's CSR (without a row base), and
+ * gsim_db_snn's counts equal gsim_snn's on it.
+ * gsim_db_snn returns a gsim_graph whose gsim_graph_shape / _copy bytes are exactly gsim_db_knn's for the whole table, and per entry
+ * e = (i, j) of it, through gsim_graph_copy_shared: shared[e] = shared(i, j) | (mutual(i, j) ? GSIM_SNN_MUTUAL_BIT : 0).  Only
+ * GSIM_SNN_CLOSED is a flag of this call.  gsim_graph_get_stats and gsim_graph_get_snn_stats answer for it; the k-NN, join and k-NN
+ * join accessors return GSIM_ERR_INVALID, as gsim_graph_copy_shared and gsim_graph_get_snn_stats do for every other graph.
+ * gsim_db_jarvis_patrick keeps the graph on the device: the fold of gsim_db_knn leaves the lists there (8 B x N x k), one kernel writes
+ * each list's rows in ascending order (4 B x N x k), one kernel intersects, for every entry (i, j), the two sorted lists and feeds the
+ * links to one union-find forest per level (4 B x N each), and gsim_db_components' labelling numbers the trees (its outputs on the
+ * device and 8 B x N of scratch plus the scan's); beside that, what gsim_db_knn takes for popcounts and padded rows.  All of it is
+ * freed by the call.
+ * The stats: rows, k, entries (of all lists), mutual_entries (entries with the mutual bit: twice the mutual pairs) and links[l]
+ * (entries (i, j) with [mutual or GSIM_SNN_EITHER] and shared >= kmins[l]; gsim_db_snn: none) and unions (successful hooks = the sum
+ * over the levels of N - nclusters[l]) are reproducible; cas_failed is a diagnostic and is not.
+ * GSIM_ERR_INVALID, checked before any device state and in this order: NULL db (and NULL out), gsim_db_knn's checks of k, cutoff and
+ * metric, unknown flag bits, NULL kmins / cluster_of / nclusters, nlevels outside [1, 8], kmins not strictly ascending or out of range,
+ * rows wider than 4096 bits, N >= 2^32.  GSIM_ERR_STATE as gsim_db_knn.  N == 0: GSIM_OK, nclusters[l] = 0 (an empty graph); N == 1:
+ * one singleton.  Execution: on the handle's stream under the one-call-at-a-time rule; the search state is left as it was found. */
+#define GSIM_SNN_CLOSED 1u /* the lists count their owners */
+#define GSIM_SNN_EITHER 2u /* gsim_db_jarvis_patrick / gsim_jarvis_patrick: one-sided pairs may link too */
+#define GSIM_SNN_MUTUAL_BIT 0x80000000u
+typedef struct {
+    uint64_t rows;           /* N                                                                                   */
+    uint64_t k;
+    uint64_t entries;        /* entries of all lists (gsim_db_knn's nnz)                                            */
+    uint64_t mutual_entries; /* entries (i, j) with i in L(j)                                                       */
+    uint64_t links[8];       /* entries meeting level l's condition; [nlevels ..) zero                              */
+    uint64_t unions;         /* successful hooks = sum over levels of (N - nclusters[l])                            */
+    uint64_t cas_failed;     /* diagnostic, NOT reproducible: compare-and-swaps that lost a race                    */
+    uint64_t launches;       /* launches of the fold kernel, as gsim_knn_stats                                      */
+    uint64_t pairs;          /* owner x candidate pairs scored                                                      */
+    uint64_t inserts;        /* list insertions made                                                                */
+    double knn_ms;           /* HIP events on the handle's stream: all fold launches                                */
+    double sort_ms;          /* ... the kernel that sorts every list's rows                                         */
+    double link_ms;          /* ... the intersection kernel (and the flatten that follows it)                       */
+    double label_ms;         /* ... numbering and outputs (gsim_db_snn: offsets and compaction)                     */
+    double d2h_ms;           /* outputs to the host                                                                 */
+    double wall_ms;          /* the whole call, host clock                                                          */
+    double clock_mhz;        /* as gsim_knn_stats.clock_mhz                                                         */
+} gsim_snn_stats;
+int gsim_db_snn(gsim_db* db, uint32_t k, float cutoff, int metric, float alpha, float beta, uint32_t flags, gsim_graph** out);
+int gsim_graph_copy_shared(const gsim_graph* g, uint32_t* shared /* nnz */);
+int gsim_graph_get_snn_stats(const gsim_graph* g, gsim_snn_stats* out);
+int gsim_db_jarvis_patrick(gsim_db* db, uint32_t k, const uint32_t* kmins, uint32_t nlevels, float cutoff, int metric, float alpha,
+                           float beta, uint32_t flags, uint32_t* cluster_of /* nlevels x N */, uint32_t* nclusters /* nlevels */,
+                           uint32_t* first_row /* nlevels x N, or NULL */, uint32_t* sizes /* nlevels x N, or NULL */,
+                           gsim_snn_stats* stats /* or NULL */);
+/* The same rule on any CSR of lists (host code, no device, no handle, no row base): list r is indices[indptr[r] .. indptr[r + 1]), of
+ * any length and in any order.  gsim_snn: shared[e] for every entry e, as gsim_graph_copy_shared gives it (flags: GSIM_SNN_CLOSED).
+ * gsim_jarvis_patrick: cluster_of [nlevels x nrows], nclusters [nlevels], first_row / sizes (or NULL) [nlevels x nrows], entries at
+ * and after nclusters[l] untouched; kmins only has to ascend strictly.  GSIM_ERR_INVALID: NULL arguments, unknown flag bits, nlevels
+ * outside [1, 8], kmins not strictly ascending, a malformed graph (gsim_butina's checks), a list that names its own row or names a row
+ * twice.  nrows == 0 is legal. */
+int gsim_snn(const uint64_t* indptr, const uint32_t* indices, uint64_t nrows, uint32_t flags, uint32_t* shared /* nnz */);
+int gsim_jarvis_patrick(const uint64_t* indptr, const uint32_t* indices, uint64_t nrows, const uint32_t* kmins, uint32_t nlevels,
+                        uint32_t flags, uint32_t* cluster_of, uint32_t* first_row /* or NULL */, uint32_t* sizes /* or NULL */,
+                        uint32_t* nclusters /* nlevels */);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
