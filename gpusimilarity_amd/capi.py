@@ -150,6 +150,24 @@ class GsimHdbscanStats(C.Structure):
                 ("wall_ms", C.c_double)]
 
 
+def _stats_dict(st):
+    """every field of a stats struct"""
+    return {f: getattr(st, f) for f, _ in st._fields_}
+
+
+def _level_buffers(n, nl, first_row=True, sizes=True):
+    """The outputs of a call with levels: labels [nl, n], counts [nl], first_row and sizes [nl, n] (None where not asked for)"""
+    shape = (max(nl, 1), n)
+    return (np.empty(shape, dtype=np.uint32), np.zeros(shape[0], dtype=np.uint32), np.empty(shape, dtype=np.uint32) if first_row else None,
+            np.empty(shape, dtype=np.uint32) if sizes else None)
+
+
+def _levels(nl, comp, ncomp, first, size):
+    """levels[l] = (labels [n], first_row [count], sizes [count]) from _level_buffers' arrays once the call has filled them"""
+    return [(comp[l].copy(), first[l, :ncomp[l]].copy() if first is not None else None, size[l, :ncomp[l]].copy() if size is not None else None)
+            for l in range(nl)]
+
+
 def _mst_stats_dict(st):
     stats = {f: getattr(st, f) for f, _ in GsimMstStats._fields_[:-2]}
     stats["scan_owners"] = list(st.scan_owners)[:st.scans]
@@ -233,7 +251,7 @@ class GsimSnnStats(C.Structure):
 
 
 def _snn_stats_dict(st):
-    d = {f: getattr(st, f) for f, _ in GsimSnnStats._fields_}
+    d = _stats_dict(st)
     d["links"] = list(st.links)
     return d
 
@@ -718,7 +736,7 @@ class Table:
             if stats is not None:
                 st = stats_type()
                 check(get_stats(g, C.byref(st)))
-                stats.update({f: getattr(st, f) for f, _ in stats_type._fields_})
+                stats.update(_stats_dict(st))
         finally:
             self._L.gsim_graph_destroy(g)
         return indptr, indices, scores
@@ -779,7 +797,7 @@ class Table:
             check(self._L.gsim_db_histogram_queries(self._h, _u32(q) if nl else None, nl, ep, len(e), metric, alpha, beta, hp, tp,
                                                     C.byref(st)))
         if stats is not None:
-            stats.update({f: getattr(st, f) for f, _ in GsimHistStats._fields_})
+            stats.update(_stats_dict(st))
         return hist, tot
 
     def scores(self, left, row_begin=0, row_end=None, col_begin=0, col_end=None, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0,
@@ -820,7 +838,7 @@ class Table:
             check(self._L.gsim_db_scores_queries(self._h, _u32(q) if len(q) else None, len(q), col_begin, col_end, metric, alpha, beta,
                                                  out.ctypes.data_as(fp), nr, C.byref(st)))
         if stats is not None:
-            stats.update({f: getattr(st, f) for f, _ in GsimScoresStats._fields_})
+            stats.update(_stats_dict(st))
         return out
 
     def maxmin(self, npicks, seeds=(), metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, max_score=1.0, assign=False, stats=None):
@@ -842,7 +860,7 @@ class Table:
                                      row_score.ctypes.data_as(fp) if assign else None, _u32(nearest) if assign else None,
                                      C.byref(st)))
         if stats is not None:
-            stats.update({f: getattr(st, f) for f, _ in GsimMaxMinStats._fields_})
+            stats.update(_stats_dict(st))
         out = (picks[:n.value].copy(), scores[:n.value].copy())
         return out + (row_score, nearest) if assign else out
 
@@ -863,7 +881,7 @@ class Table:
         check(self._L.gsim_db_leader(self._h, cutoff, _u32(sd) if len(sd) else None, len(sd), cap, metric, alpha, beta, _u32(leaders),
                                      C.byref(nl), _u32(leader_of) if assign else None,
                                      row_score.ctypes.data_as(C.POINTER(C.c_float)) if assign else None, C.byref(st)))
-        return leaders[:nl.value].copy(), leader_of, row_score, {f: getattr(st, f) for f, _ in GsimLeaderStats._fields_}
+        return leaders[:nl.value].copy(), leader_of, row_score, _stats_dict(st)
 
     def components(self, cutoffs, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, first_row=True, sizes=True):
         """gsim_db_components: single-linkage clustering (connected components of "score >= cutoff") at an ascending list of cutoffs,
@@ -871,16 +889,11 @@ class Table:
         base), sizes uint32 [ncomponents]) for cutoffs[l]; first_row / sizes are None where not asked for."""
         cut = np.ascontiguousarray(np.atleast_1d(cutoffs), dtype=np.float32).reshape(-1)
         n, nl = self.count(), len(cut)
-        comp = np.empty((max(nl, 1), n), dtype=np.uint32)
-        ncomp = np.zeros(max(nl, 1), dtype=np.uint32)
-        first = np.empty((max(nl, 1), n), dtype=np.uint32) if first_row else None
-        size = np.empty((max(nl, 1), n), dtype=np.uint32) if sizes else None
+        comp, ncomp, first, size = _level_buffers(n, nl, first_row, sizes)
         st = GsimComponentsStats()
         check(self._L.gsim_db_components(self._h, cut.ctypes.data_as(C.POINTER(C.c_float)), nl, metric, alpha, beta, _u32(comp), _u32(ncomp),
                                          _u32(first) if first_row else None, _u32(size) if sizes else None, C.byref(st)))
-        levels = [(comp[l].copy(), first[l, :ncomp[l]].copy() if first_row else None, size[l, :ncomp[l]].copy() if sizes else None)
-                  for l in range(nl)]
-        return levels, {f: getattr(st, f) for f, _ in GsimComponentsStats._fields_}
+        return _levels(nl, comp, ncomp, first, size), _stats_dict(st)
 
     def snn(self, k, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, closed=False, stats=None):
         """gsim_db_snn: knn(k, cutoff)'s graph of the whole table with the shared-nearest-neighbour count of every entry
@@ -911,17 +924,12 @@ class Table:
         their owners)."""
         km = np.ascontiguousarray(np.atleast_1d(kmins), dtype=np.uint32).reshape(-1)
         n, nl = self.count(), len(km)
-        comp = np.empty((max(nl, 1), n), dtype=np.uint32)
-        ncomp = np.zeros(max(nl, 1), dtype=np.uint32)
-        first = np.empty((max(nl, 1), n), dtype=np.uint32) if first_row else None
-        size = np.empty((max(nl, 1), n), dtype=np.uint32) if sizes else None
+        comp, ncomp, first, size = _level_buffers(n, nl, first_row, sizes)
         flags = (SNN_CLOSED if closed else 0) | (SNN_EITHER if either else 0)
         st = GsimSnnStats()
         check(self._L.gsim_db_jarvis_patrick(self._h, k, _u32(km), nl, cutoff, metric, alpha, beta, flags, _u32(comp), _u32(ncomp),
                                              _u32(first) if first_row else None, _u32(size) if sizes else None, C.byref(st)))
-        levels = [(comp[l].copy(), first[l, :ncomp[l]].copy() if first_row else None, size[l, :ncomp[l]].copy() if sizes else None)
-                  for l in range(nl)]
-        return levels, _snn_stats_dict(st)
+        return _levels(nl, comp, ncomp, first, size), _snn_stats_dict(st)
 
     def mst(self, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0):
         """gsim_db_mst: the single-linkage dendrogram as its maximum-similarity spanning forest -> (edges, stats dict); edges is a
@@ -951,7 +959,7 @@ class Table:
                                      _u32(anc) if anchor else None, _u32(first) if first_row else None, _u32(size) if sizes else None,
                                      C.byref(st)))
         return (label_of, deg, anc, first[:ncl.value].copy() if first_row else None, size[:ncl.value].copy() if sizes else None,
-                {f: getattr(st, f) for f, _ in GsimDbscanStats._fields_})
+                _stats_dict(st))
 
     def core_scores(self, min_pts, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0):
         """gsim_db_core_scores: every row's HDBSCAN core score -> (core float32 [N], stats dict: gsim_knn_stats of the core pass).
@@ -960,7 +968,7 @@ class Table:
         core = np.empty(self.count(), dtype=np.float32)
         st = GsimKnnStats()
         check(self._L.gsim_db_core_scores(self._h, min_pts, cutoff, metric, alpha, beta, _f32(core), C.byref(st)))
-        return core, {f: getattr(st, f) for f, _ in GsimKnnStats._fields_}
+        return core, _stats_dict(st)
 
     def mreach_mst(self, min_pts, cutoff, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0):
         """gsim_db_mreach_mst: the mutual-reachability forest -> (edges, core float32 [N], stats dict).  gsim_db_mst's rule with
@@ -1003,7 +1011,7 @@ class Table:
         check(self._L.gsim_db_bit_counts(self._h, rowset._h if rowset is not None else None, row_begin, row_end,
                                          counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(counted), C.byref(st)))
         if stats is not None:
-            stats.update({f: getattr(st, f) for f, _ in GsimProfileStats._fields_})
+            stats.update(_stats_dict(st))
         return counts, counted.value
 
     def overlap_sums(self, weights, row_begin=0, row_end=None, popc=False, stats=None):
@@ -1020,7 +1028,7 @@ class Table:
         check(self._L.gsim_db_overlap_sums(self._h, _u32(w), row_begin, row_end, sums.ctypes.data_as(C.POINTER(C.c_uint64)),
                                            _u32(pc) if popc else None, C.byref(st)))
         if stats is not None:
-            stats.update({f: getattr(st, f) for f, _ in GsimProfileStats._fields_})
+            stats.update(_stats_dict(st))
         return (sums[:n], pc[:n]) if popc else sums[:n]
 
     def _centres(self, centres):
@@ -1042,7 +1050,7 @@ class Table:
         check(self._L.gsim_db_assign(self._h, cp, len(c), row_begin, row_end, metric, alpha, beta, _u32(label),
                                      score.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st)))
         if stats is not None:
-            stats.update({f: getattr(st, f) for f, _ in GsimAssignStats._fields_})
+            stats.update(_stats_dict(st))
         return label[:n], score[:n]
 
     def label_counts(self, labels, nlabels, row_begin=0, row_end=None, stats=None):
@@ -1062,7 +1070,7 @@ class Table:
         check(self._L.gsim_db_label_counts(self._h, _u32(lab) if len(lab) else None, nlabels, row_begin, row_end, _u32(counts), _u32(sizes),
                                            C.byref(st)))
         if stats is not None:
-            stats.update({f: getattr(st, f) for f, _ in GsimLabelStats._fields_})
+            stats.update(_stats_dict(st))
         return counts, sizes
 
     def label_sums(self, labels, nlabels, row_begin=0, row_end=None, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, own_only=False, launch_pairs=0):
@@ -1088,7 +1096,7 @@ class Table:
                                          LABEL_SUMS_OWN_ONLY if own_only else 0, int(launch_pairs), own.ctypes.data_as(u64p),
                                          None if own_only else _u32(other), None if own_only else other_q.ctypes.data_as(u64p), _u32(sizes),
                                          C.byref(st)))
-        stats = {f: getattr(st, f) for f, _ in GsimLabelSumsStats._fields_}
+        stats = _stats_dict(st)
         return own[:n], (None if own_only else other[:n]), (None if own_only else other_q[:n]), sizes[:int(nlabels)], stats
 
     def linkage(self, linkage, row_begin=0, row_end=None, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, launch_steps=0):
@@ -1106,7 +1114,7 @@ class Table:
         st = GsimLinkageStats()
         check(self._L.gsim_db_linkage(self._h, row_begin, row_end, linkage, metric, alpha, beta, int(launch_steps), merges.ctypes.data,
                                       C.byref(nm), C.byref(st)))
-        return merges[:nm.value].copy(), {f: getattr(st, f) for f, _ in GsimLinkageStats._fields_}
+        return merges[:nm.value].copy(), _stats_dict(st)
 
     def kmeans(self, init, max_iter=20, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0):
         """gsim_db_kmeans: Lloyd's iteration from the m centres `init` over the whole table -- assign, count, majority-vote centroid,
@@ -1122,7 +1130,7 @@ class Table:
         st = GsimKmeansStats()
         check(self._L.gsim_db_kmeans(self._h, cp, len(c), max_iter, metric, alpha, beta, _u32(centres) if len(c) else None, _u32(label),
                                      score.ctypes.data_as(C.POINTER(C.c_float)), _u32(sizes), C.byref(st)))
-        return centres, label[:n], score[:n], sizes[:len(c)], {f: getattr(st, f) for f, _ in GsimKmeansStats._fields_}
+        return centres, label[:n], score[:n], sizes[:len(c)], _stats_dict(st)
 
     def rowset(self, rows=None, bitmap=None, exclude=False) -> RowSet:
         """gsim_rowset_from_rows / _from_bitmap: `rows` are row indices including the row base (gsim_hit.row values), any order,
@@ -1156,7 +1164,7 @@ class Table:
                                           approx.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(st)))
         out = [hits[i, :counts[i]].copy() for i in range(nq)], approx
         if stats:
-            out += ({f: getattr(st, f) for f, _ in GsimRowsetStats._fields_},)
+            out += (_stats_dict(st),)
         return out
 
     def labelset(self, labels, nlabels) -> LabelSet:
@@ -1192,7 +1200,7 @@ class Table:
                                             out["label_best"].ctypes.data_as(C.c_void_p) if per_label else None,
                                             _u32(out["label_kept"]) if per_label else None, C.byref(st)))
         if stats:
-            out["stats"] = {f: getattr(st, f) for f, _ in GsimLabelSearchStats._fields_}
+            out["stats"] = _stats_dict(st)
         return out
 
     def search_group(self, queries, k, mode=GROUP_MAX, cutoff=0.0, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, stats=False):
@@ -1207,7 +1215,7 @@ class Table:
                                            hits.ctypes.data_as(C.c_void_p), C.byref(count), C.byref(approx), C.byref(st)))
         out = hits[:count.value].copy(), approx.value
         if stats:
-            out += ({f: getattr(st, f) for f, _ in GsimGroupStats._fields_},)
+            out += (_stats_dict(st),)
         return out
 
     def make_search_buffers(self, nq, k):
@@ -1279,7 +1287,7 @@ class Table:
     def timing(self) -> dict:
         t = GsimTiming()
         check(self._L.gsim_db_get_timing(self._h, C.byref(t)))
-        return {f: getattr(t, f) for f, _ in GsimTiming._fields_}
+        return _stats_dict(t)
 
     def query_flags(self, n: int) -> np.ndarray:
         """One byte per query of the last search call made with timing enabled (gsim_debug_query_flags): 1 handed back by its own
@@ -1350,14 +1358,11 @@ def jarvis_patrick(indptr, indices, kmins, nrows=None, closed=False, either=Fals
     if n < 0 or len(indptr) < n + 1:
         raise GsimError(-1, "indptr needs nrows + 1 entries")
     nl = len(km)
-    comp = np.empty((max(nl, 1), n), dtype=np.uint32)
-    first = np.empty((max(nl, 1), n), dtype=np.uint32)
-    size = np.empty((max(nl, 1), n), dtype=np.uint32)
-    nc = np.zeros(max(nl, 1), dtype=np.uint32)
+    comp, nc, first, size = _level_buffers(n, nl)
     flags = (SNN_CLOSED if closed else 0) | (SNN_EITHER if either else 0)
     check(load().gsim_jarvis_patrick(indptr.ctypes.data_as(C.POINTER(C.c_uint64)), _u32(indices), n, _u32(km), nl, flags, _u32(comp),
                                      _u32(first), _u32(size), _u32(nc)))
-    return [(comp[l].copy(), first[l, :nc[l]].copy(), size[l, :nc[l]].copy()) for l in range(nl)]
+    return _levels(nl, comp, nc, first, size)
 
 
 def _mst_edges(edges):

@@ -1,6 +1,6 @@
 // capi_components.cpp -- gsim_db_components (single-linkage clustering: the connected components of the threshold graph at up to
-// eight cutoffs, in one pass over the pairs) and gsim_components (the same rule on a symmetric CSR graph, host code).  The argument
-// checks and the launch sequence of a call; the device side is gsim_components.hip.  The rule is stated in include/gpusim_hip.h.
+// eight cutoffs, in one pass over the pairs; the labelling tail is ForestLabels, capi_front.h) and gsim_components (the same rule on a
+// symmetric CSR graph, host code).  The device side is gsim_components.hip.  The rule is stated in include/gpusim_hip.h.
 #include "capi_front.h"
 
 #include <cmath>
@@ -25,18 +25,13 @@ int components(gsim_db* db, Shard& s, const float* cutoffs, uint32_t nlevels, in
     size_t tmp_bytes = 0;
     GSIM_HIP(gsim::comp_scan_bytes(N, &tmp_bytes));
     PaddedRows table;
-    DevBuf<uint32_t> parent, d_comp, d_first, d_sizes, d_ncomp, d_flag, d_num;
+    DevBuf<uint32_t> parent;
+    ForestLabels labels;
     DevBuf<unsigned long long> ctl; // the counters, then 4 clock stamps per launch
     DevBuf<> tmp;
-    const size_t stripe = static_cast<size_t>(N) * 4, all = stripe * nlevels;
     if (const int rc = table.alloc(N, s.W, WP, "components (popcounts)", "components (the padded rows)")) return rc;
-    GSIM_ALLOC(parent, all, "components (the forests)");
-    GSIM_ALLOC(d_comp, all, "components (component_of)");
-    if (first_row) GSIM_ALLOC(d_first, all, "components (first_row)");
-    if (sizes) GSIM_ALLOC(d_sizes, all, "components (sizes)");
-    GSIM_ALLOC(d_ncomp, gsim::kCompMaxLevels * 4, "components (the counts)");
-    GSIM_ALLOC(d_flag, stripe, "components (label scratch)");
-    GSIM_ALLOC(d_num, stripe, "components (label scratch)");
+    GSIM_ALLOC(parent, static_cast<size_t>(N) * 4 * nlevels, "components (the forests)");
+    if (const int rc = labels.alloc(N, nlevels, first_row, sizes, "components", "component_of")) return rc;
     GSIM_ALLOC(ctl, (gsim::kCompCounters + 4 * plan.size()) * 8, "components (control block)");
     GSIM_ALLOC(tmp, tmp_bytes, "components (scan scratch)");
     LaunchClocks clocks;
@@ -53,10 +48,8 @@ int components(gsim_db* db, Shard& s, const float* cutoffs, uint32_t nlevels, in
     a.parent = parent;
     a.counters = ctl;
 
-    EventPair ev_kernel, ev_label, ev_d2h;
+    EventPair ev_kernel;
     GSIM_HIP(ev_kernel.create());
-    GSIM_HIP(ev_label.create());
-    GSIM_HIP(ev_d2h.create());
     GSIM_HIP(hipMemsetAsync(ctl, 0, (gsim::kCompCounters + 4 * plan.size()) * 8, stream));
     if (const int rc = table.prepare(s.d_rows, N, stream)) return rc;
     a.rows = table.rows();
@@ -72,44 +65,24 @@ int components(gsim_db* db, Shard& s, const float* cutoffs, uint32_t nlevels, in
         GSIM_HIP(gsim::launch_comp_flatten(parent, N, nlevels, stream));
     }
     GSIM_HIP(hipEventRecord(ev_kernel.b, stream));
-    // labels, on the device, a level at a time
-    GSIM_HIP(hipEventRecord(ev_label.a, stream));
-    if (sizes) GSIM_HIP(hipMemsetAsync(d_sizes, 0, all, stream));
-    for (uint32_t l = 0; l < nlevels; l++)
-        GSIM_HIP(gsim::launch_comp_label(tmp, tmp_bytes, parent + l * N, N, db->row_base, d_flag, d_num, d_comp + l * N,
-                                         first_row ? d_first + l * N : nullptr, sizes ? d_sizes + l * N : nullptr, d_ncomp + l, stream));
-    GSIM_HIP(hipEventRecord(ev_label.b, stream));
-    std::vector<unsigned long long> h_ctl(gsim::kCompCounters + 4 * plan.size());
-    uint32_t h_ncomp[gsim::kCompMaxLevels] = {};
-    GSIM_HIP(hipEventRecord(ev_d2h.a, stream));
-    GSIM_HIP(hipMemcpyAsync(h_ncomp, d_ncomp, nlevels * 4, hipMemcpyDeviceToHost, stream));
-    GSIM_HIP(hipMemcpyAsync(h_ctl.data(), ctl, h_ctl.size() * 8, hipMemcpyDeviceToHost, stream));
-    GSIM_HIP(hipMemcpyAsync(component_of, d_comp, all, hipMemcpyDeviceToHost, stream));
-    GSIM_HIP(hipStreamSynchronize(stream));
-    uint64_t unions = 0;
-    for (uint32_t l = 0; l < nlevels; l++) {
-        if (h_ncomp[l] < 1 || h_ncomp[l] > N) return fail(GSIM_ERR_STATE, "components: the device reported an impossible count");
-        unions += N - h_ncomp[l];
-        // (entries at and after ncomponents[l] of a stripe are left untouched)
-        if (first_row) GSIM_HIP(hipMemcpyAsync(first_row + l * N, d_first + l * N, static_cast<size_t>(h_ncomp[l]) * 4, hipMemcpyDeviceToHost, stream));
-        if (sizes) GSIM_HIP(hipMemcpyAsync(sizes + l * N, d_sizes + l * N, static_cast<size_t>(h_ncomp[l]) * 4, hipMemcpyDeviceToHost, stream));
-    }
-    GSIM_HIP(hipEventRecord(ev_d2h.b, stream));
-    GSIM_HIP(hipStreamSynchronize(stream));
-    if (h_ctl[gsim::kCompUnions] != unions) return fail(GSIM_ERR_STATE, "components: the hooks and the component counts do not add up");
-    for (uint32_t l = 0; l < nlevels; l++) ncomponents[l] = h_ncomp[l];
+    if (const int rc = labels.run(parent, N, nlevels, db->row_base, tmp, tmp_bytes, ctl, gsim::kCompCounters + 4 * plan.size(), component_of,
+                                  first_row, sizes, stream, "components"))
+        return rc;
+    const unsigned long long* h_ctl = labels.ctl.data();
+    if (h_ctl[gsim::kCompUnions] != labels.unions) return fail(GSIM_ERR_STATE, "components: the hooks and the component counts do not add up");
+    for (uint32_t l = 0; l < nlevels; l++) ncomponents[l] = labels.ncomp[l];
     if (st) {
         st->rows = N;
         st->levels = nlevels;
         st->launches = plan.size();
         st->pairs = N * (N - 1) / 2;
         st->kept = h_ctl[gsim::kCompKept];
-        st->unions = unions;
+        st->unions = labels.unions;
         st->cas_failed = h_ctl[gsim::kCompCasFailed];
         st->kernel_ms = ev_kernel.ms();
-        st->label_ms = ev_label.ms();
-        st->d2h_ms = ev_d2h.ms();
-        clocks.add(h_ctl.data() + gsim::kCompCounters, plan.size()); // (read with the counters, in one copy)
+        st->label_ms = labels.ev_label.ms();
+        st->d2h_ms = labels.ev_d2h.ms();
+        clocks.add(h_ctl + gsim::kCompCounters, plan.size()); // (read with the counters, in one copy)
         st->clock_mhz = clocks.mhz();
         st->wall_ms = ms_since(t0);
     }
@@ -134,9 +107,8 @@ int gsim_db_components(gsim_db* db, const float* cutoffs, uint32_t nlevels, int 
         if (l && !(cutoffs[l - 1] < cutoffs[l])) return fail(GSIM_ERR_INVALID, "components: the cutoffs must be strictly ascending");
     }
     if (const int rc = check_symmetric_metric("components need", "components", metric, alpha, beta)) return rc;
-    if (db->fp_bits > 4096 || gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, "components: rows wider than 4096 bits");
+    if (const int rc = check_tile_table(db, "components")) return rc;
     const uint64_t N = db->nrows;
-    if (N > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "components: tables of 2^32 rows or more");
     for (uint32_t l = 0; l < nlevels; l++) ncomponents[l] = 0;
     if (N == 0) return GSIM_OK;
     if (const int rc = check_table_state(db, "components", true)) return rc;

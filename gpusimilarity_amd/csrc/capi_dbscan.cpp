@@ -157,12 +157,11 @@ int gsim_db_dbscan(gsim_db* db, float cutoff, uint32_t min_pts, int metric, floa
     if (stats) *stats = gsim_dbscan_stats{};
     if (nclusters) *nclusters = 0;
     if (!db || !label_of || !nclusters) return fail(GSIM_ERR_INVALID, "NULL argument");
-    if (!(cutoff > 0.0f && cutoff <= 1.0f)) return fail(GSIM_ERR_INVALID, "dbscan: the cutoff must be in (0, 1]");
+    if (const int rc = check_cutoff("dbscan", cutoff)) return rc;
     if (min_pts == 0) return fail(GSIM_ERR_INVALID, "dbscan: min_pts must be at least 1");
     if (const int rc = check_symmetric_metric("dbscan needs", "dbscan", metric, alpha, beta)) return rc;
-    if (db->fp_bits > 4096 || gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, "dbscan: rows wider than 4096 bits");
+    if (const int rc = check_tile_table(db, "dbscan")) return rc;
     const uint64_t N = db->nrows;
-    if (N > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "dbscan: tables of 2^32 rows or more");
     if (N == 0) return GSIM_OK;
     if (const int rc = check_table_state(db, "dbscan", false)) return rc;
     return on_one_shard(db, "host memory for dbscan", [&](Shard& s) {

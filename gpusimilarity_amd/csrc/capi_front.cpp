@@ -95,6 +95,66 @@ int check_row_range(const gsim_db* db, uint64_t row_begin, uint64_t row_end)
     return GSIM_OK;
 }
 
+int check_tile_table(const gsim_db* db, const char* name)
+{
+    if (db->fp_bits > 4096 || gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, std::string(name) + ": rows wider than 4096 bits");
+    if (db->nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, std::string(name) + ": tables of 2^32 rows or more");
+    return GSIM_OK;
+}
+
+int check_cutoff(const char* name, float cutoff)
+{
+    if (!(cutoff > 0.0f && cutoff <= 1.0f)) return fail(GSIM_ERR_INVALID, std::string(name) + ": the cutoff must be in (0, 1]");
+    return GSIM_OK;
+}
+
+int check_k_cutoff(const char* name, uint32_t k, float cutoff)
+{
+    if (k < 1 || k > GSIM_KNN_MAX_K) return fail(GSIM_ERR_INVALID, std::string(name) + ": k must be in [1, GSIM_KNN_MAX_K = 128]");
+    return check_cutoff(name, cutoff);
+}
+
+int ForestLabels::alloc(uint64_t N, uint32_t nlevels, bool first_row, bool sizes, const char* prefix, const char* of)
+{
+    const std::string w = std::string("device memory for ") + prefix;
+    const size_t stripe = static_cast<size_t>(N) * 4, all = stripe * nlevels;
+    if (d_comp.grow(all) != hipSuccess) return fail(GSIM_ERR_NOMEM, w + " (" + of + ")");
+    if (first_row && d_first.grow(all) != hipSuccess) return fail(GSIM_ERR_NOMEM, w + " (first_row)");
+    if (sizes && d_sizes.grow(all) != hipSuccess) return fail(GSIM_ERR_NOMEM, w + " (sizes)");
+    if (d_ncomp.grow(gsim::kCompMaxLevels * 4) != hipSuccess) return fail(GSIM_ERR_NOMEM, w + " (the counts)");
+    if (d_flag.grow(stripe) != hipSuccess || d_num.grow(stripe) != hipSuccess) return fail(GSIM_ERR_NOMEM, w + " (label scratch)");
+    return GSIM_OK;
+}
+
+int ForestLabels::run(const uint32_t* parent, uint64_t N, uint32_t nlevels, uint32_t row_base, void* tmp, size_t tmp_bytes, const void* d_ctl,
+                      size_t ctl_words, uint32_t* labels, uint32_t* first_row, uint32_t* sizes, hipStream_t st, const char* prefix)
+{
+    const size_t all = static_cast<size_t>(N) * 4 * nlevels;
+    GSIM_HIP(ev_label.create());
+    GSIM_HIP(ev_d2h.create());
+    GSIM_HIP(hipEventRecord(ev_label.a, st));
+    if (sizes) GSIM_HIP(hipMemsetAsync(d_sizes, 0, all, st));
+    for (uint32_t l = 0; l < nlevels; l++)
+        GSIM_HIP(gsim::launch_comp_label(tmp, tmp_bytes, parent + l * N, N, row_base, d_flag, d_num, d_comp + l * N,
+                                         first_row ? d_first + l * N : nullptr, sizes ? d_sizes + l * N : nullptr, d_ncomp + l, st));
+    GSIM_HIP(hipEventRecord(ev_label.b, st));
+    ctl.assign(ctl_words, 0);
+    GSIM_HIP(hipEventRecord(ev_d2h.a, st));
+    GSIM_HIP(hipMemcpyAsync(ncomp, d_ncomp, nlevels * 4, hipMemcpyDeviceToHost, st));
+    GSIM_HIP(hipMemcpyAsync(ctl.data(), d_ctl, ctl_words * 8, hipMemcpyDeviceToHost, st));
+    GSIM_HIP(hipMemcpyAsync(labels, d_comp, all, hipMemcpyDeviceToHost, st));
+    GSIM_HIP(hipStreamSynchronize(st));
+    for (uint32_t l = 0; l < nlevels; l++) {
+        if (ncomp[l] < 1 || ncomp[l] > N) return fail(GSIM_ERR_STATE, std::string(prefix) + ": the device reported an impossible count");
+        unions += N - ncomp[l];
+        if (first_row) GSIM_HIP(hipMemcpyAsync(first_row + l * N, d_first + l * N, static_cast<size_t>(ncomp[l]) * 4, hipMemcpyDeviceToHost, st));
+        if (sizes) GSIM_HIP(hipMemcpyAsync(sizes + l * N, d_sizes + l * N, static_cast<size_t>(ncomp[l]) * 4, hipMemcpyDeviceToHost, st));
+    }
+    GSIM_HIP(hipEventRecord(ev_d2h.b, st));
+    GSIM_HIP(hipStreamSynchronize(st));
+    return GSIM_OK;
+}
+
 int check_seeds(const gsim_db* db, const uint32_t* seeds, uint32_t nseeds, const char* nomem_what)
 {
     if (nseeds && !seeds) return fail(GSIM_ERR_INVALID, "NULL seeds");

@@ -1,8 +1,8 @@
 // capi_front.h -- what a call does before and after its launches, where several entry points had each carried a copy: the metric
-// check, the state check and the left side of the two-table families (threshold joins, k-NN joins, histograms, score matrices:
-// capi_join / capi_knn_join / capi_hist / capi_scores.cpp), the wrapper of the graph-returning calls, and the checks and the runner
-// of the calls on one table.  Each family keeps its own argument checks.  Implemented in capi_front.cpp; DESIGN.md sections 24 and
-// 25.  Internal.
+// check, the state check and the left side of the two-table families (threshold joins, k-NN joins, histograms, score matrices), the
+// wrapper of the graph-returning calls, the checks and the runner of the calls on one table, and the labelling tail of the forest
+// calls.  Each family keeps the argument checks that are its own.  Implemented in capi_front.cpp (the score core: capi_scores.cpp;
+// the label sort: capi_labels.cpp); DESIGN.md sections 24, 25 and 33.  Internal.
 #pragma once
 
 #include "capi_pairs.h"
@@ -73,6 +73,12 @@ int check_row_range(const gsim_db* db, uint64_t row_begin, uint64_t row_end);
 // INVALID "NULL seeds", then per seed "seed row outside the table" and "repeated seed row"; NOMEM `nomem_what`
 int check_seeds(const gsim_db* db, const uint32_t* seeds, uint32_t nseeds, const char* nomem_what);
 
+// INVALID "<name>: rows wider than 4096 bits" (wider than the tile kernels hold), then "<name>: tables of 2^32 rows or more"
+int check_tile_table(const gsim_db* db, const char* name);
+// INVALID "<name>: the cutoff must be in (0, 1]"; with k, "<name>: k must be in [1, GSIM_KNN_MAX_K = 128]" in front of it
+int check_cutoff(const char* name, float cutoff);
+int check_k_cutoff(const char* name, uint32_t k, float cutoff);
+
 // The call on the handle's one shard, which check_table_state has passed: one call at a time per handle; NOMEM `nomem_what` when
 // core(shard) runs out of host memory; a failed core may have stopped between its launches, so the shard is marked and the next
 // enqueue re-zeroes the search state (rezero_dirty_state).
@@ -89,6 +95,24 @@ template <class Fn> int on_one_shard(gsim_db* db, const char* nomem_what, Fn&& c
     if (rc != GSIM_OK) s.state_dirty = true;
     return rc;
 }
+
+// ---- the labelling tail of gsim_db_components and gsim_db_jarvis_patrick: nlevels flattened forests of N rows -> the outputs ----
+
+struct ForestLabels {
+    DevBuf<uint32_t> d_comp, d_first, d_sizes, d_ncomp, d_flag, d_num;
+    uint32_t ncomp[gsim::kCompMaxLevels] = {}; // trees per level
+    uint64_t unions = 0;                       // N - ncomp[l], summed: what the caller's hook counter must say
+    std::vector<unsigned long long> ctl;       // the caller's control block, read back with the counts
+    EventPair ev_label, ev_d2h;                // around the label launches; around the copies
+
+    // NOMEM "device memory for <prefix> (<of>)", "(first_row)", "(sizes)" -- the two where asked for --, "(the counts)", "(label scratch)"
+    int alloc(uint64_t N, uint32_t nlevels, bool first_row, bool sizes, const char* prefix, const char* of);
+    // The sizes' memset and the label launches (scratch `tmp`: comp_scan_bytes(N)); the copies of the counts, of d_ctl's ctl_words
+    // words and of the labels; the wait; STATE "<prefix>: the device reported an impossible count"; the first ncomp[l] entries of
+    // first_row and sizes per level (the rest of a stripe is left untouched); the second wait.
+    int run(const uint32_t* parent, uint64_t N, uint32_t nlevels, uint32_t row_base, void* tmp, size_t tmp_bytes, const void* d_ctl,
+            size_t ctl_words, uint32_t* labels, uint32_t* first_row, uint32_t* sizes, hipStream_t st, const char* prefix);
+};
 
 // ---- the core of the score matrices (capi_scores.cpp), which gsim_db_linkage (capi_linkage.cpp) fills its matrix with ----
 

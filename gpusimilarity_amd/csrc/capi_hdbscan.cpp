@@ -1,5 +1,5 @@
-// capi_hdbscan.cpp -- HDBSCAN on a resident table: gsim_db_core_scores (the core pass: gsim_db_knn's fold over all rows and a tail
-// kernel that reads the lists' last entries), gsim_db_mreach_mst (the core pass, then gsim_db_mst's round loop -- boruvka_forest,
+// capi_hdbscan.cpp -- HDBSCAN on a resident table: gsim_db_core_scores (the core pass: KnnListPass over all rows and a tail kernel
+// that reads the lists' last entries), gsim_db_mreach_mst (the core pass, then gsim_db_mst's round loop -- boruvka_forest,
 // capi_mst.cpp -- with the mutual-reachability fold kernel), gsim_db_hdbscan (that forest, then the selection), and the host
 // companions gsim_mreach_mst (the forest's rule on a scored CSR graph) and gsim_mst_hdbscan (the condensed tree and the selection
 // of clusters from any forest in order E).  The device side is gsim_mreach.hip.  The rule is stated in include/gpusim_hip.h.
@@ -20,47 +20,35 @@ struct CorePass {
     double kernel_ms = 0.0, tail_ms = 0.0, clock_mhz = 0.0;
 };
 
-// d_core[0 .. N) on the device from the prepared table: the k-NN fold of all N owners with k = min_pts - 1 (capi_knn.cpp's plan
-// and launches; not for min_pts == 1) and the tail kernel.  The lists live here only: they are freed on return, and the stream
+// d_core[0 .. N) on the device from the prepared table: the k-NN list pass of all N owners with k = min_pts - 1 (KnnListPass,
+// capi_knn.cpp; no lists for min_pts == 1) and the tail kernel.  The lists live here only: they are freed on return, and the stream
 // has been waited for.
 int core_pass(gsim_db* db, const PaddedRows& table, uint64_t N, uint32_t WP, uint32_t min_pts, float cutoff, int metric, float alpha,
               float beta, float* d_core, hipStream_t st, CorePass* out)
 {
     const uint32_t k = min_pts - 1;
-    const std::vector<KnnLaunch> plan = k && N >= 2 ? plan_knn(N, N, WP, db->knobs.knn_launch_pairs) : std::vector<KnnLaunch>();
-    // [0] the insert counter, [1] the rows with core >= cutoff, then 4 clock stamps per launch
-    const size_t ctl_words = 2 + LaunchClocks::kWords * plan.size();
-    DevBuf<gsim::KnnEntry> lists;
-    DevBuf<uint32_t> len;
-    DevBuf<unsigned long long> ctl;
-    if (k) {
-        GSIM_ALLOC(lists, N * k * sizeof(gsim::KnnEntry), "the core scores (the k-nearest-neighbour lists)");
-        GSIM_ALLOC(len, N * 4, "the core scores (the lists' lengths)");
-        GSIM_HIP(hipMemsetAsync(len, 0, N * 4, st));
-    }
-    GSIM_ALLOC(ctl, ctl_words * 8, "the core scores (control block)");
-    GSIM_HIP(hipMemsetAsync(ctl, 0, ctl_words * 8, st));
-    LaunchClocks clocks;
-    clocks.view(ctl + 2);
-    EventPair ev_fold, ev_tail;
+    // [0] the insert counter, [1] the rows with core >= cutoff, then 4 clock stamps per launch; min_pts == 1: no lists, the tail alone
+    KnnListPass pass;
+    if (const int rc = pass.alloc(db, N, WP, 0, N, k, 2, 0, false, {"the core scores (the k-nearest-neighbour lists)",
+                                  "the core scores (the lists' lengths)", "the core scores (control block)"}, st))
+        return rc;
+    EventPair ev_tail;
     GSIM_HIP(ev_tail.create());
-    if (k)
-        if (const int rc = run_knn_fold(knn_args(table, N, 0, N, WP, k, cutoff, metric, alpha, beta, lists, len, ctl), plan, clocks, ev_fold, st))
-            return rc;
+    if (const int rc = pass.fold(table, cutoff, metric, alpha, beta, st)) return rc;
     GSIM_HIP(hipEventRecord(ev_tail.a, st));
-    GSIM_HIP(gsim::launch_mreach_core(lists, len, N, k, cutoff, d_core, ctl + 1, st));
+    GSIM_HIP(gsim::launch_mreach_core(pass.lists, pass.len, N, k, cutoff, d_core, pass.word(1), st));
     GSIM_HIP(hipEventRecord(ev_tail.b, st));
-    std::vector<unsigned long long> h_ctl(ctl_words);
-    GSIM_HIP(hipMemcpyAsync(h_ctl.data(), ctl, ctl_words * 8, hipMemcpyDeviceToHost, st));
+    std::vector<unsigned long long> h_ctl(pass.ctl_words);
+    GSIM_HIP(hipMemcpyAsync(h_ctl.data(), pass.ctl, pass.ctl_words * 8, hipMemcpyDeviceToHost, st));
     GSIM_HIP(hipStreamSynchronize(st));
     if (h_ctl[1] > N) return fail(GSIM_ERR_STATE, "core scores: the device reported an impossible count");
-    clocks.add(h_ctl.data() + 2, plan.size());
-    out->launches = plan.size();
+    pass.add_clocks(h_ctl.data());
+    out->launches = pass.plan.size();
     out->inserts = h_ctl[0];
     out->dense = h_ctl[1];
-    out->kernel_ms = k ? ev_fold.ms() : 0.0;
+    out->kernel_ms = k ? pass.ev_fold.ms() : 0.0;
     out->tail_ms = ev_tail.ms();
-    out->clock_mhz = clocks.mhz();
+    out->clock_mhz = pass.clocks.mhz();
     return GSIM_OK;
 }
 
@@ -351,11 +339,9 @@ int check_call(const gsim_db* db, const char* name, uint32_t min_pts, float cuto
 {
     const std::string n(name);
     if (min_pts < 1 || min_pts > GSIM_KNN_MAX_K + 1) return fail(GSIM_ERR_INVALID, n + ": min_pts must be in [1, GSIM_KNN_MAX_K + 1 = 129]");
-    if (!(cutoff > 0.0f && cutoff <= 1.0f)) return fail(GSIM_ERR_INVALID, n + ": the cutoff must be in (0, 1]");
+    if (const int rc = check_cutoff(name, cutoff)) return rc;
     if (const int rc = check_symmetric_metric((n + " needs").c_str(), name, metric, alpha, beta)) return rc;
-    if (db->fp_bits > 4096 || gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, n + ": rows wider than 4096 bits");
-    if (db->nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, n + ": tables of 2^32 rows or more");
-    return GSIM_OK;
+    return check_tile_table(db, name);
 }
 
 } // namespace

@@ -193,14 +193,11 @@ int check_knn_join_args(gsim_db* db, gsim_graph** out, uint64_t nl, const KnnJoi
 {
     if (out) *out = nullptr;
     if (!db || !out) return fail(GSIM_ERR_INVALID, "NULL argument");
-    if (c.k < 1 || c.k > GSIM_KNN_MAX_K) return fail(GSIM_ERR_INVALID, "knn join: k must be in [1, GSIM_KNN_MAX_K = 128]");
-    if (!(c.cutoff > 0.0f && c.cutoff <= 1.0f)) return fail(GSIM_ERR_INVALID, "knn join: the cutoff must be in (0, 1]");
+    if (const int rc = check_k_cutoff("knn join", c.k, c.cutoff)) return rc;
     if (const int rc = check_metric("knn join", c.metric, c.alpha, c.beta)) return rc;
     if (flags & ~GSIM_KNN_EXCLUDE_SELF) return fail(GSIM_ERR_INVALID, "knn join: unknown flag bits");
     if (nl > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "knn join: 2^32 left rows or more");
-    if (db->nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "knn join: tables of 2^32 rows or more");
-    if (db->fp_bits > 4096 || gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, "knn join: rows wider than 4096 bits");
-    return GSIM_OK;
+    return check_tile_table(db, "knn join"); // (width first: the shared order)
 }
 
 int run_knn_join(gsim_db* db, const LeftSide& left, const KnnJoinCall& c, gsim_graph** out)

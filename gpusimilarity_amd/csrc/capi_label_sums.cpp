@@ -207,8 +207,7 @@ int gsim_db_label_sums(gsim_db* db, const uint32_t* labels, uint32_t nlabels, ui
     if (nlabels == 0) return fail(GSIM_ERR_INVALID, "label sums: nlabels == 0");
     if (const int rc = check_row_range(db, row_begin, row_end)) return rc;
     if (const int rc = check_metric("label sums", metric, alpha, beta)) return rc;
-    if (db->nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "label sums: tables of 2^32 rows or more");
-    if (db->fp_bits > 4096 || gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, "label sums: rows wider than 4096 bits");
+    if (const int rc = check_tile_table(db, "label sums")) return rc; // (width first: the shared order)
     const uint64_t n = row_end - row_begin;
     if (n && !labels) return fail(GSIM_ERR_INVALID, "label sums: NULL labels");
     for (uint64_t i = 0; i < n; i++)

@@ -186,7 +186,7 @@ int gsim_db_leader(gsim_db* db, float cutoff, const uint32_t* seeds, uint32_t ns
     if (stats) *stats = gsim_leader_stats{};
     if (!db || !leaders || !nleaders) return fail(GSIM_ERR_INVALID, "NULL argument");
     *nleaders = 0;
-    if (!(cutoff > 0.0f && cutoff <= 1.0f)) return fail(GSIM_ERR_INVALID, "leader: the cutoff must be in (0, 1]");
+    if (const int rc = check_cutoff("leader", cutoff)) return rc;
     if (const int rc = check_symmetric_metric("leader needs", "leader", metric, alpha, beta)) return rc;
     const uint64_t N = db->nrows;
     if (N > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "leader: tables of 2^32 rows or more");

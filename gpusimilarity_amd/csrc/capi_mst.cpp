@@ -223,11 +223,10 @@ int gsim_db_mst(gsim_db* db, float cutoff, int metric, float alpha, float beta, 
     if (stats) *stats = gsim_mst_stats{};
     if (nedges) *nedges = 0;
     if (!db || !nedges) return fail(GSIM_ERR_INVALID, "NULL argument");
-    if (!(cutoff > 0.0f && cutoff <= 1.0f)) return fail(GSIM_ERR_INVALID, "mst: the cutoff must be in (0, 1]");
+    if (const int rc = check_cutoff("mst", cutoff)) return rc;
     if (const int rc = check_symmetric_metric("mst needs", "mst", metric, alpha, beta)) return rc;
-    if (db->fp_bits > 4096 || gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, "mst: rows wider than 4096 bits");
+    if (const int rc = check_tile_table(db, "mst")) return rc;
     const uint64_t N = db->nrows;
-    if (N > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, "mst: tables of 2^32 rows or more");
     if (N > 1 && !edges) return fail(GSIM_ERR_INVALID, "NULL edges");
     if (N == 0) return GSIM_OK;
     if (const int rc = check_table_state(db, "mst", false)) return rc;

@@ -1,10 +1,8 @@
-// capi_pairs.h -- what gsim_db_neighbors (capi_neighbors.cpp) and the threshold joins (capi_join.cpp) share: the result
-// object, the handle's pair buffer with its overflow / exact-regrow protocol, the tile kernel's launch plan, and the CSR
-// build; and what the k-NN calls (capi_knn.cpp, capi_knn_join.cpp, capi_mst.cpp) share: the fold launches' plan and the CSR
-// build of their lists; and what the host functions on a caller's graph share: the CSR checks, the union-find forest and the
-// numbering of its trees; and what the two spanning forests share (capi_mst.cpp, capi_hdbscan.cpp): the round loop, order E, the
-// edge checks, Kruskal on a list of pairs, and the k-NN fold launches of a plan.  Implemented in capi_pairs.cpp (the k-NN plan:
-// capi_knn_join.cpp; the forests' part: capi_mst.cpp and capi_knn.cpp).  Internal.
+// capi_pairs.h -- the units more than one call runs, by section: the result object; the pair buffer, tile plan and CSR build of
+// gsim_db_neighbors and the threshold joins (capi_pairs.cpp); the fold plans and the CSR build of the k-NN lists (capi_knn_join.cpp,
+// capi_pairs.cpp); the CSR checks, forest and numbering of the host functions (capi_pairs.cpp); the round loop, order E and edge
+// checks of the two spanning forests (capi_mst.cpp); the k-NN list pass of gsim_db_knn, the shared-neighbour calls and the core
+// scores (capi_knn.cpp).  Internal.
 #pragma once
 
 #include "capi_internal.h"
@@ -164,10 +162,33 @@ int check_scored_csr(const uint64_t* indptr, const uint32_t* indices, const floa
 // Kruskal over the pairs a < b of `all` (sorted here into order E; repeated pairs are harmless) -> edges, in order E; their number
 uint64_t kruskal_in_e(std::vector<gsim_mst_edge>& all, uint64_t nrows, gsim_mst_edge* edges);
 
-// The fold launches of a k-NN plan (capi_knn.cpp; the core pass of capi_hdbscan.cpp and capi_snn.cpp run the same): a's table, lists and cutoff as
-// the caller set them, every launch with its clock words, HIP events around all of them.
-gsim::KnnArgs knn_args(const PaddedRows& table, uint64_t N, uint64_t rb, uint64_t re, uint32_t WP, uint32_t k, float cutoff, int metric,
-                       float alpha, float beta, gsim::KnnEntry* lists, uint32_t* len, unsigned long long* inserts);
-int run_knn_fold(gsim::KnnArgs a, const std::vector<KnnLaunch>& plan, const LaunchClocks& clocks, EventPair& ev_fold, hipStream_t st);
+// ---- the k-NN list pass: gsim_db_knn, the shared-neighbour pass (capi_snn.cpp), the core pass (capi_hdbscan.cpp) ----
+
+// The lists of the owner rows [rb, re) of a table of N rows, k slots each, with their lengths, the plan and the control block:
+// `front` words of counters ([0] the fold's inserts, the rest the caller's), 4 clock stamps per fold launch, `back` words more of
+// the caller's.  k == 0 is a list of no slots: nothing but the control block is allocated, nothing launched.
+struct KnnListPass {
+    struct Names {
+        const char *lists, *len, *ctl; // of the three allocations, after "device memory for "
+    };
+    DevBuf<gsim::KnnEntry> lists;
+    DevBuf<uint32_t> len;
+    DevBuf<> ctl;
+    std::vector<KnnLaunch> plan;
+    LaunchClocks clocks;
+    EventPair ev_fold;
+    size_t front = 1, ctl_words = 0;
+    gsim::KnnArgs args{};                      // what alloc knows of the fold's arguments
+
+    unsigned long long* word(size_t w) const { return ctl.as<unsigned long long>() + w; }
+    size_t back_at() const { return front + LaunchClocks::kWords * plan.size(); } // where the caller's `back` words begin
+
+    // the plan; the three allocations, by these names; lengths (`total`: one more, which build_knn_csr's scan makes the total) and block zeroed
+    int alloc(const gsim_db* db, uint64_t N, uint32_t WP, uint64_t rb, uint64_t re, uint32_t k, size_t front, size_t back, bool total,
+              const Names& names, hipStream_t st);
+    // the plan's fold launches on the prepared table, every launch with its clock words, HIP events (ev_fold) around all of them
+    int fold(const PaddedRows& table, float cutoff, int metric, float alpha, float beta, hipStream_t st);
+    void add_clocks(const unsigned long long* h_ctl) { clocks.add(h_ctl + front, plan.size()); } // from a host copy of the block
+};
 
 } // namespace gsim_host

@@ -1,8 +1,8 @@
 // capi_snn.cpp -- gsim_db_snn (gsim_db_knn's graph with the shared-nearest-neighbour count of every entry) and gsim_db_jarvis_patrick
 // (Jarvis-Patrick clustering at up to eight kmin levels; the graph never leaves the device).  The argument checks and the launch
-// sequence of a call: gsim_db_knn's fold over all rows (knn_args, run_knn_fold: capi_knn.cpp), the sort and link kernels of
-// gsim_snn.hip, then either the k-NN calls' CSR tail (build_knn_csr) or gsim_db_components' flatten and labelling.  The rule is
-// stated in include/gpusim_hip.h; the host functions of the same rule are in capi_snn_host.cpp.
+// sequence of a call: gsim_db_knn's list pass over all rows (KnnListPass, capi_pairs.h), the sort and link kernels of gsim_snn.hip,
+// then either the k-NN calls' CSR tail (build_knn_csr) or gsim_db_components' flatten and labelling (ForestLabels, capi_front.h).
+// The rule is stated in include/gpusim_hip.h; the host functions of the same rule are in capi_snn_host.cpp.
 #include "capi_front.h"
 
 namespace gsim_host
@@ -10,19 +10,14 @@ namespace gsim_host
 namespace
 {
 
-// What both calls do first: the lists of all N >= 2 rows, their rows sorted, and the link pass.  The control block: [0] the fold's
-// insert counter, 4 clock stamps per fold launch, then the link kernel's kSnnCounters.
+// What both calls do first: the lists of all N >= 2 rows (KnnListPass: behind its clock stamps, the link kernel's kSnnCounters), their
+// rows sorted, and the link pass.
 struct SnnPass {
     PaddedRows table;
-    DevBuf<> ctl, tmp;
-    DevBuf<gsim::KnnEntry> lists;
-    DevBuf<uint32_t> len, nbr;
-    std::vector<KnnLaunch> plan;
-    LaunchClocks clocks;
-    EventPair ev_fold, ev_sort, ev_link;
-    size_t ctl_words = 0, tmp_bytes = 0;
-
-    size_t counters_at() const { return 1 + LaunchClocks::kWords * plan.size(); }
+    KnnListPass knn;
+    DevBuf<> tmp;
+    DevBuf<uint32_t> nbr;
+    EventPair ev_sort, ev_link;
 
     // `parent`: nlevels initialised forests, flattened here after the link launch (or nullptr); `shared`: N x k words (or nullptr)
     int run(gsim_db* db, Shard& s, uint32_t k, float cutoff, int metric, float alpha, float beta, uint32_t flags, const uint32_t* kmins,
@@ -31,30 +26,22 @@ struct SnnPass {
         const uint64_t N = s.nrows;
         const uint32_t WP = gsim::nbr_padded_words(s.W);
         const hipStream_t st = s.stream;
-        plan = plan_knn(N, N, WP, db->knobs.knn_launch_pairs);
-        ctl_words = counters_at() + gsim::kSnnCounters;
-        tmp_bytes = scan_bytes;
         if (const int rc = table.alloc(N, s.W, WP, "the shared-neighbour pass (popcounts)", "the shared-neighbour pass (padded rows)")) return rc;
-        GSIM_ALLOC(lists, N * k * sizeof(gsim::KnnEntry), "the shared-neighbour pass (the k-nearest-neighbour lists)");
-        GSIM_ALLOC(len, (N + 1) * 4, "the shared-neighbour pass (the lists' lengths)");
-        GSIM_ALLOC(nbr, N * k * 4, "the shared-neighbour pass (the sorted lists)");
-        GSIM_ALLOC(ctl, ctl_words * 8, "the shared-neighbour pass (control block)");
-        GSIM_ALLOC(tmp, tmp_bytes, "the shared-neighbour pass (scan scratch)");
-        unsigned long long* d_ctl = ctl.as<unsigned long long>();
-        clocks.view(d_ctl + 1);
-        GSIM_HIP(hipMemsetAsync(len, 0, (N + 1) * 4, st));
-        GSIM_HIP(hipMemsetAsync(ctl, 0, ctl_words * 8, st));
-        if (const int rc = table.prepare(s.d_rows, N, st)) return rc;
-        if (const int rc = run_knn_fold(knn_args(table, N, 0, N, WP, k, cutoff, metric, alpha, beta, lists, len, d_ctl), plan, clocks, ev_fold, st))
+        if (const int rc = knn.alloc(db, N, WP, 0, N, k, 1, gsim::kSnnCounters, true, {"the shared-neighbour pass (the k-nearest-neighbour lists)",
+                                     "the shared-neighbour pass (the lists' lengths)", "the shared-neighbour pass (control block)"}, st))
             return rc;
+        GSIM_ALLOC(nbr, N * k * 4, "the shared-neighbour pass (the sorted lists)");
+        GSIM_ALLOC(tmp, scan_bytes, "the shared-neighbour pass (scan scratch)");
+        if (const int rc = table.prepare(s.d_rows, N, st)) return rc;
+        if (const int rc = knn.fold(table, cutoff, metric, alpha, beta, st)) return rc;
         GSIM_HIP(ev_sort.create());
         GSIM_HIP(ev_link.create());
         GSIM_HIP(hipEventRecord(ev_sort.a, st));
-        GSIM_HIP(gsim::launch_snn_sort(lists, len, N, k, nbr, st));
+        GSIM_HIP(gsim::launch_snn_sort(knn.lists, knn.len, N, k, nbr, st));
         GSIM_HIP(hipEventRecord(ev_sort.b, st));
         gsim::SnnArgs a{};
-        a.lists = lists;
-        a.len = len;
+        a.lists = knn.lists;
+        a.len = knn.len;
         a.nbr = nbr;
         a.nrows = N;
         a.k = k;
@@ -63,7 +50,7 @@ struct SnnPass {
         for (uint32_t l = 0; l < nlevels; l++) a.kmins[l] = kmins[l];
         a.parent = parent;
         a.shared = shared;
-        a.counters = d_ctl + counters_at();
+        a.counters = knn.word(knn.back_at());
         GSIM_HIP(hipEventRecord(ev_link.a, st));
         GSIM_HIP(gsim::launch_snn_link(a, s.num_cus / std::max(s.cu_share, 1), st));
         if (parent) GSIM_HIP(gsim::launch_comp_flatten(parent, N, nlevels, st));
@@ -74,7 +61,7 @@ struct SnnPass {
     // the stats both calls fill from the control block (read back by the caller, the stream waited for)
     void fill(const unsigned long long* h_ctl, uint64_t N, uint32_t k, uint32_t nlevels, gsim_snn_stats* st)
     {
-        const unsigned long long* c = h_ctl + counters_at();
+        const unsigned long long* c = h_ctl + knn.back_at();
         st->rows = N;
         st->k = k;
         st->entries = c[gsim::kSnnEntries];
@@ -82,14 +69,14 @@ struct SnnPass {
         for (uint32_t l = 0; l < nlevels; l++) st->links[l] = c[gsim::kSnnLinks + l];
         st->unions = c[gsim::kSnnUnions];
         st->cas_failed = c[gsim::kSnnCasFailed];
-        st->launches = plan.size();
+        st->launches = knn.plan.size();
         st->pairs = N * N;
         st->inserts = h_ctl[0];
-        st->knn_ms = ev_fold.ms();
+        st->knn_ms = knn.ev_fold.ms();
         st->sort_ms = ev_sort.ms();
         st->link_ms = ev_link.ms();
-        clocks.add(h_ctl + 1, plan.size());
-        st->clock_mhz = clocks.mhz();
+        knn.add_clocks(h_ctl);
+        st->clock_mhz = knn.clocks.mhz();
     }
 };
 
@@ -117,14 +104,14 @@ int snn(gsim_db* db, Shard& s, uint32_t k, float cutoff, int metric, float alpha
     if (const int rc = pass.run(db, s, k, cutoff, metric, alpha, beta, flags, nullptr, 0, nullptr, d_shared, scan_bytes)) return rc;
 
     KnnCsr csr;
-    if (const int rc = build_knn_csr(db, s, pass.lists, pass.len, N, k, pass.tmp, d_indptr, pass.ctl, "the shared-neighbour CSR", "snn", g, &csr))
+    if (const int rc = build_knn_csr(db, s, pass.knn.lists, pass.knn.len, N, k, pass.tmp, d_indptr, pass.knn.ctl, "the shared-neighbour CSR", "snn", g, &csr))
         return rc;
     // the counts by the same offsets
     EventPair ev_d2h;
     GSIM_HIP(ev_d2h.create());
     GSIM_ALLOC(d_out, csr.total * 4, "the shared-neighbour CSR (counts)");
     g->shared.resize(csr.total);
-    GSIM_HIP(gsim::launch_snn_compact(d_shared, pass.len, d_indptr, N, k, d_out, st));
+    GSIM_HIP(gsim::launch_snn_compact(d_shared, pass.knn.len, d_indptr, N, k, d_out, st));
     GSIM_HIP(hipEventRecord(ev_d2h.a, st));
     if (csr.total) GSIM_HIP(hipMemcpyAsync(g->shared.data(), d_out, csr.total * 4, hipMemcpyDeviceToHost, st));
     GSIM_HIP(hipEventRecord(ev_d2h.b, st));
@@ -169,75 +156,28 @@ int jarvis_patrick(gsim_db* db, Shard& s, uint32_t k, const uint32_t* kmins, uin
     GSIM_HIP(set_device(s.device));
     const hipStream_t st = s.stream;
     SnnPass pass;
-    DevBuf<uint32_t> parent, d_comp, d_first, d_sizes, d_ncomp, d_flag, d_num;
-    const size_t stripe = static_cast<size_t>(N) * 4, all = stripe * nlevels;
+    DevBuf<uint32_t> parent;
+    ForestLabels labels;
     size_t scan_bytes = 0;
     GSIM_HIP(gsim::comp_scan_bytes(N, &scan_bytes));
-    GSIM_ALLOC(parent, all, "jarvis-patrick (the forests)");
-    GSIM_ALLOC(d_comp, all, "jarvis-patrick (cluster_of)");
-    if (first_row) GSIM_ALLOC(d_first, all, "jarvis-patrick (first_row)");
-    if (sizes) GSIM_ALLOC(d_sizes, all, "jarvis-patrick (sizes)");
-    GSIM_ALLOC(d_ncomp, gsim::kCompMaxLevels * 4, "jarvis-patrick (the counts)");
-    GSIM_ALLOC(d_flag, stripe, "jarvis-patrick (label scratch)");
-    GSIM_ALLOC(d_num, stripe, "jarvis-patrick (label scratch)");
+    GSIM_ALLOC(parent, static_cast<size_t>(N) * 4 * nlevels, "jarvis-patrick (the forests)");
+    if (const int rc = labels.alloc(N, nlevels, first_row, sizes, "jarvis-patrick", "cluster_of")) return rc;
     GSIM_HIP(gsim::launch_comp_init(parent, N, nlevels, st));
     if (const int rc = pass.run(db, s, k, cutoff, metric, alpha, beta, flags, kmins, nlevels, parent, nullptr, scan_bytes)) return rc;
 
-    // labels, on the device, a level at a time; then the outputs, as gsim_db_components
-    EventPair ev_label, ev_d2h;
-    GSIM_HIP(ev_label.create());
-    GSIM_HIP(ev_d2h.create());
-    GSIM_HIP(hipEventRecord(ev_label.a, st));
-    if (sizes) GSIM_HIP(hipMemsetAsync(d_sizes, 0, all, st));
-    for (uint32_t l = 0; l < nlevels; l++)
-        GSIM_HIP(gsim::launch_comp_label(pass.tmp, pass.tmp_bytes, parent + l * N, N, db->row_base, d_flag, d_num, d_comp + l * N,
-                                         first_row ? d_first + l * N : nullptr, sizes ? d_sizes + l * N : nullptr, d_ncomp + l, st));
-    GSIM_HIP(hipEventRecord(ev_label.b, st));
-    std::vector<unsigned long long> h_ctl(pass.ctl_words);
-    uint32_t h_ncomp[gsim::kCompMaxLevels] = {};
-    GSIM_HIP(hipEventRecord(ev_d2h.a, st));
-    GSIM_HIP(hipMemcpyAsync(h_ncomp, d_ncomp, nlevels * 4, hipMemcpyDeviceToHost, st));
-    GSIM_HIP(hipMemcpyAsync(h_ctl.data(), pass.ctl, h_ctl.size() * 8, hipMemcpyDeviceToHost, st));
-    GSIM_HIP(hipMemcpyAsync(cluster_of, d_comp, all, hipMemcpyDeviceToHost, st));
-    GSIM_HIP(hipStreamSynchronize(st));
-    uint64_t unions = 0;
-    for (uint32_t l = 0; l < nlevels; l++) {
-        if (h_ncomp[l] < 1 || h_ncomp[l] > N) return fail(GSIM_ERR_STATE, "jarvis-patrick: the device reported an impossible count");
-        unions += N - h_ncomp[l];
-        // (entries at and after nclusters[l] of a stripe are left untouched)
-        if (first_row) GSIM_HIP(hipMemcpyAsync(first_row + l * N, d_first + l * N, static_cast<size_t>(h_ncomp[l]) * 4, hipMemcpyDeviceToHost, st));
-        if (sizes) GSIM_HIP(hipMemcpyAsync(sizes + l * N, d_sizes + l * N, static_cast<size_t>(h_ncomp[l]) * 4, hipMemcpyDeviceToHost, st));
-    }
-    GSIM_HIP(hipEventRecord(ev_d2h.b, st));
-    GSIM_HIP(hipStreamSynchronize(st));
-    if (h_ctl[pass.counters_at() + gsim::kSnnUnions] != unions)
+    // labels and outputs, as gsim_db_components
+    if (const int rc = labels.run(parent, N, nlevels, db->row_base, pass.tmp, scan_bytes, pass.knn.ctl, pass.knn.ctl_words, cluster_of,
+                                  first_row, sizes, st, "jarvis-patrick"))
+        return rc;
+    if (labels.ctl[pass.knn.back_at() + gsim::kSnnUnions] != labels.unions)
         return fail(GSIM_ERR_STATE, "jarvis-patrick: the hooks and the cluster counts do not add up");
-    for (uint32_t l = 0; l < nlevels; l++) nclusters[l] = h_ncomp[l];
+    for (uint32_t l = 0; l < nlevels; l++) nclusters[l] = labels.ncomp[l];
     if (stats) {
-        pass.fill(h_ctl.data(), N, k, nlevels, stats);
-        stats->label_ms = ev_label.ms();
-        stats->d2h_ms = ev_d2h.ms();
+        pass.fill(labels.ctl.data(), N, k, nlevels, stats);
+        stats->label_ms = labels.ev_label.ms();
+        stats->d2h_ms = labels.ev_d2h.ms();
         stats->wall_ms = ms_since(t0);
     }
-    return GSIM_OK;
-}
-
-// gsim_db_knn's checks of k, cutoff and metric, then the flags
-int check_lists(const char* name, uint32_t k, float cutoff, int metric, float alpha, float beta, uint32_t flags, uint32_t known)
-{
-    const std::string n(name);
-    if (k < 1 || k > GSIM_KNN_MAX_K) return fail(GSIM_ERR_INVALID, n + ": k must be in [1, GSIM_KNN_MAX_K = 128]");
-    if (!(cutoff > 0.0f && cutoff <= 1.0f)) return fail(GSIM_ERR_INVALID, n + ": the cutoff must be in (0, 1]");
-    if (const int rc = check_metric(name, metric, alpha, beta)) return rc;
-    if (flags & ~known) return fail(GSIM_ERR_INVALID, n + ": unknown flags");
-    return GSIM_OK;
-}
-
-int check_table(const gsim_db* db, const char* name)
-{
-    const std::string n(name);
-    if (db->fp_bits > 4096 || gsim::nbr_padded_words(db->W) == 0) return fail(GSIM_ERR_INVALID, n + ": rows wider than 4096 bits");
-    if (db->nrows > 0xFFFFFFFFull) return fail(GSIM_ERR_INVALID, n + ": tables of 2^32 rows or more");
     return GSIM_OK;
 }
 
@@ -252,8 +192,10 @@ int gsim_db_snn(gsim_db* db, uint32_t k, float cutoff, int metric, float alpha, 
 {
     if (out) *out = nullptr;
     if (!db || !out) return fail(GSIM_ERR_INVALID, "NULL argument");
-    if (const int rc = check_lists("snn", k, cutoff, metric, alpha, beta, flags, GSIM_SNN_CLOSED)) return rc;
-    if (const int rc = check_table(db, "snn")) return rc;
+    if (const int rc = check_k_cutoff("snn", k, cutoff)) return rc;
+    if (const int rc = check_metric("snn", metric, alpha, beta)) return rc;
+    if (flags & ~GSIM_SNN_CLOSED) return fail(GSIM_ERR_INVALID, "snn: unknown flags");
+    if (const int rc = check_tile_table(db, "snn")) return rc;
     if (const int rc = check_table_state(db, "snn", false)) return rc;
     const char* nomem = "host memory for the shared-neighbour graph";
     return on_one_shard(db, nomem, [&](Shard& s) {
@@ -283,7 +225,9 @@ int gsim_db_jarvis_patrick(gsim_db* db, uint32_t k, const uint32_t* kmins, uint3
 {
     if (stats) *stats = gsim_snn_stats{};
     if (!db) return fail(GSIM_ERR_INVALID, "NULL argument");
-    if (const int rc = check_lists("jarvis-patrick", k, cutoff, metric, alpha, beta, flags, GSIM_SNN_CLOSED | GSIM_SNN_EITHER)) return rc;
+    if (const int rc = check_k_cutoff("jarvis-patrick", k, cutoff)) return rc;
+    if (const int rc = check_metric("jarvis-patrick", metric, alpha, beta)) return rc;
+    if (flags & ~(GSIM_SNN_CLOSED | GSIM_SNN_EITHER)) return fail(GSIM_ERR_INVALID, "jarvis-patrick: unknown flags");
     if (!kmins || !nclusters || (db->nrows && !cluster_of)) return fail(GSIM_ERR_INVALID, "NULL argument");
     if (nlevels < 1 || nlevels > GSIM_COMPONENTS_MAX_LEVELS) return fail(GSIM_ERR_INVALID, "jarvis-patrick: between 1 and 8 levels");
     const uint32_t kmax = k + ((flags & GSIM_SNN_CLOSED) ? 2u : 0u);
@@ -291,7 +235,7 @@ int gsim_db_jarvis_patrick(gsim_db* db, uint32_t k, const uint32_t* kmins, uint3
         if (kmins[l] > kmax) return fail(GSIM_ERR_INVALID, "jarvis-patrick: every kmin must be in [0, k], or [0, k + 2] with GSIM_SNN_CLOSED");
         if (l && !(kmins[l - 1] < kmins[l])) return fail(GSIM_ERR_INVALID, "jarvis-patrick: kmins must be strictly ascending");
     }
-    if (const int rc = check_table(db, "jarvis-patrick")) return rc;
+    if (const int rc = check_tile_table(db, "jarvis-patrick")) return rc;
     for (uint32_t l = 0; l < nlevels; l++) nclusters[l] = 0;
     if (db->nrows == 0) return GSIM_OK;
     if (const int rc = check_table_state(db, "jarvis-patrick", false)) return rc;
