@@ -34,6 +34,7 @@ KNN_MAX_K = 128
 KNN_EXCLUDE_SELF = 1
 HIST_MAX_EDGES = 128
 HIST_EXCLUDE_SELF = 1
+POPINDEX_ROWS = 1
 
 HIT_DTYPE = np.dtype([("row", "<u4"), ("score", "<f4"), ("common", "<u2"), ("popc_db", "<u2")])
 GROUP_HIT_DTYPE = np.dtype([("row", "<u4"), ("score", "<f4"), ("which", "<u2"), ("popc_db", "<u2")])
@@ -69,6 +70,12 @@ class GsimMaxMinStats(C.Structure):
 
 class GsimRowsetStats(C.Structure):
     _fields_ = [("selected", C.c_uint64), ("queries_gather", C.c_uint64), ("queries_stream", C.c_uint64), ("launches", C.c_uint64),
+                ("kernel_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+class GsimPopindexStats(C.Structure):
+    _fields_ = [("rows_scanned", C.c_uint64), ("rows_window", C.c_uint64), ("queries_one_stage", C.c_uint64),
+                ("queries_two_stage", C.c_uint64), ("queries_plain", C.c_uint64), ("launches", C.c_uint64), ("bounds_ms", C.c_double),
                 ("kernel_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
@@ -294,6 +301,7 @@ EXPORTS = [
     "gsim_labelset_create", "gsim_labelset_sizes", "gsim_labelset_destroy", "gsim_db_search_labels",
     "gsim_db_linkage", "gsim_linkage",
     "gsim_db_snn", "gsim_graph_copy_shared", "gsim_graph_get_snn_stats", "gsim_db_jarvis_patrick", "gsim_snn", "gsim_jarvis_patrick",
+    "gsim_popindex_create", "gsim_popindex_first", "gsim_popindex_order", "gsim_popindex_destroy", "gsim_popcount_bounds", "gsim_db_search_bounded",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -457,6 +465,13 @@ def load():
         "gsim_jarvis_patrick": (C.c_int, [u64p, u32p, C.c_uint64, u32p, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p]),
         "gsim_db_kmeans": (C.c_int, [vp, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, u32p, u32p,
                                      C.POINTER(C.c_float), u32p, C.POINTER(GsimKmeansStats)]),
+        "gsim_popindex_create": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
+        "gsim_popindex_first": (C.c_int, [vp, u64p]),
+        "gsim_popindex_order": (C.c_int, [vp, u32p]),
+        "gsim_popindex_destroy": (C.c_int, [vp]),
+        "gsim_popcount_bounds": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float)]),
+        "gsim_db_search_bounded": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, vp, u32p, u64p,
+                                             C.POINTER(GsimPopindexStats)]),
         "gsim_last_error": (C.c_char_p, []),
         "gsim_version": (C.c_char_p, []),
     }
@@ -554,6 +569,56 @@ class RowSet:
             self.close()
         except Exception:
             pass
+
+
+class PopIndex:
+    """``gsim_popindex``: the rows of one :class:`Table` ordered by popcount (Table.popindex makes it, Table.search_bounded searches
+    through it).  It lives in the table's device memory: close it (or drop it) before the table."""
+
+    def __init__(self, table, handle, flags):
+        self._L = table._L
+        self._h = handle
+        self._table = table  # (keeps the handle it belongs to alive)
+        self.flags = int(flags)
+        self.fp_bits = table.W * 32
+        self.nrows = table.count()
+
+    def first(self) -> np.ndarray:
+        """first[b], b = 0 .. fp_bits + 1: the number of rows with a popcount below b (uint64)."""
+        out = np.zeros(self.fp_bits + 2, dtype=np.uint64)
+        check(self._L.gsim_popindex_first(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def order(self) -> np.ndarray:
+        """The table's rows sorted by (popcount, row), row base included (uint32)."""
+        out = np.empty(self.nrows, dtype=np.uint32)
+        check(self._L.gsim_popindex_order(self._h, _u32(out) if len(out) else None))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.gsim_popindex_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def popcount_bounds(fp_bits, popc_query, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0) -> np.ndarray:
+    """gsim_popcount_bounds (host): ub[b], b = 0 .. fp_bits -- the largest score a row with b bits set can have against a query with
+    `popc_query` bits set, exact in f32."""
+    ub = np.empty(fp_bits + 1 if 0 < fp_bits <= 32768 else 1, dtype=np.float32)
+    check(load().gsim_popcount_bounds(fp_bits, popc_query, metric, alpha, beta, _f32(ub)))
+    return ub
 
 
 class LabelSet:
@@ -1163,6 +1228,32 @@ class Table:
                                           hits.ctypes.data_as(C.c_void_p), _u32(counts),
                                           approx.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(st)))
         out = [hits[i, :counts[i]].copy() for i in range(nq)], approx
+        if stats:
+            out += (_stats_dict(st),)
+        return out
+
+    def popindex(self, rows=False) -> PopIndex:
+        """gsim_popindex_create: the popcount index of this table; rows=True (GSIM_POPINDEX_ROWS) also keeps a popcount-ordered copy
+        of the rows, so that windows stream instead of gathering."""
+        flags = POPINDEX_ROWS if rows else 0
+        h = C.c_void_p()
+        check(self._L.gsim_popindex_create(self._h, flags, C.byref(h)))
+        return PopIndex(self, h, flags)
+
+    def search_bounded(self, popindex, queries, k, cutoff=0.0, metric=METRIC_TANIMOTO, alpha=1.0, beta=1.0, approx=True, stats=False):
+        """gsim_db_search_bounded: what :meth:`search` returns (list of HIT_DTYPE arrays, approx), read from a window of the popcount
+        order; approx=False passes NULL for it (None is returned in its place), which lets a query with a cutoff narrow to its top
+        k; with stats=True a third item, the call's gsim_popindex_stats as a dict."""
+        q = np.ascontiguousarray(queries, dtype=np.uint32).reshape(-1, self.W)
+        nq = q.shape[0]
+        hits = np.zeros((nq, max(k, 1)), dtype=HIT_DTYPE)
+        counts = np.zeros(nq, dtype=np.uint32)
+        ap = np.zeros(nq, dtype=np.uint64) if approx else None
+        st = GsimPopindexStats()
+        check(self._L.gsim_db_search_bounded(self._h, popindex._h, _u32(q), nq, k, cutoff, metric, alpha, beta,
+                                             hits.ctypes.data_as(C.c_void_p), _u32(counts),
+                                             ap.ctypes.data_as(C.POINTER(C.c_uint64)) if approx else None, C.byref(st)))
+        out = [hits[i, :counts[i]].copy() for i in range(nq)], ap
         if stats:
             out += (_stats_dict(st),)
         return out

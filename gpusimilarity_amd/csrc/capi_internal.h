@@ -157,6 +157,9 @@ struct Shard {
     DevBuf<unsigned long long> d_dbg; // GSIM_FUSED_DEBUG: per-workgroup phase timestamps
     DevBuf<uint32_t> d_gqueries; // gsim_db_search_group: the call's queries and, behind them, their popcounts (grown, never shrunk)
     HostBuf<uint32_t> h_gqpop{kHostPinned}; // ... the popcounts' pinned staging
+    DevBuf<uint32_t> d_pqueries; // gsim_db_search_bounded: the call's queries (grown, never shrunk: a screening loop pays no allocation per call)
+    DevBuf<float> d_pbounds;     // ... the bound table of one query popcount, fp_bits + 1 floats
+    HostBuf<float> h_pbounds{kHostPinned}; // ... and its pinned copy
     DevBuf<> d_result;
     // pinned host staging; queries go through a ring so that back-to-back
     // asynchronous searches never overwrite a query whose upload is still queued
@@ -239,6 +242,23 @@ struct gsim_labelset {
     uint64_t nonempty = 0;       // labels with at least one row
     std::vector<uint32_t> sizes; // nlabels, counted on the host
     gsim_host::DevBuf<uint32_t> d_labels; // nrows labels
+};
+
+// A popcount index (gsim_popindex_*, capi_popindex.cpp): device memory of the handle it was made for, immutable.
+// tests/popindex_front_errors_cases.py hands the fronts a stand-in (FakePopindex: zeroed memory that begins as this struct does, with
+// `owner`, `device`, `nrows`, `fp_bits`, `row_base`, `flags` set) to reach the checks that read an index before any device state.  That
+// holds while those six fields stay first, in this order, and while gsim_db_search_bounded reads nothing behind them ahead of
+// check_table_state: move a field, or read `first` earlier, and change the stand-in with it.
+struct gsim_popindex {
+    gsim_db* owner = nullptr;
+    int device = 0;
+    uint64_t nrows = 0;          // rows of the owner's table when the index was made
+    uint32_t fp_bits = 0;
+    uint32_t row_base = 0;       // ... and its row base then (what gsim_popindex_order adds)
+    uint32_t flags = 0;
+    std::vector<uint64_t> first; // fp_bits + 2: rows with a popcount below b
+    gsim_host::DevBuf<uint32_t> d_order; // nrows rows in (popcount, row) order, without the row base
+    gsim_host::DevBuf<uint32_t> d_rows;  // GSIM_POPINDEX_ROWS: the rows in that order
 };
 
 struct gsim_db {

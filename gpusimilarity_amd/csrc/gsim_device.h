@@ -776,6 +776,25 @@ ScanGeometry subset_gather_geometry(uint64_t nsel, uint32_t W, int num_cus); // 
 hipError_t launch_subset_scan(const ScanArgs& a, const ScanGeometry& g, const uint32_t* bits, hipStream_t s);
 hipError_t launch_subset_gather(const ScanArgs& a, const ScanGeometry& g, const uint32_t* list, uint32_t nsel, hipStream_t s);
 
+// ---- popcount indexes (gsim_popindex.hip, gsim_popindex_* / gsim_db_search_bounded) ---------------------------------------------
+// bins of the popcount histogram a workgroup keeps in LDS (rows up to 4096 bits; wider rows add to the global bins directly)
+constexpr uint32_t kPopcLdsBins = 4097;
+// popc[r] = popc(row r) for the nrows rows of W words, hist[b] += rows with popcount b (hist: W x 32 + 1 bins, zeroed by the caller)
+hipError_t launch_popindex_popc(const void* rows, uint64_t nrows, uint32_t W, uint16_t* popc, uint32_t* hist, int num_cus, hipStream_t s);
+// order[0 .. n) = the rows 0 .. n - 1 sorted stably by popc (its low end_bit bits hold every value): (popcount, row) ascending
+hipError_t popindex_sort_bytes(uint64_t n, uint32_t end_bit, size_t* bytes);
+hipError_t launch_popindex_sort(void* tmp, size_t tmp_bytes, const uint16_t* popc, uint16_t* popc_sorted, uint32_t* order, uint64_t n,
+                                uint32_t end_bit, hipStream_t s);
+// first[0 .. n) = exclusive prefix sums of hist[0 .. n) (n = bins + 1 with hist[bins] = 0: first[bins] is the row count)
+hipError_t popindex_scan_bytes(uint64_t n, size_t* bytes);
+hipError_t launch_popindex_first(void* tmp, size_t tmp_bytes, const uint32_t* hist, uint32_t* first, uint64_t n, hipStream_t s);
+// ub[b], b <= fp_bits: the largest score_of(metric, alpha, beta, qpop, b, c) over c in [max(0, qpop + b - fp_bits), min(qpop, b)], NaN as 0
+hipError_t launch_popindex_bounds(uint32_t fp_bits, uint32_t qpop, int metric, float alpha, float beta, float* ub, hipStream_t s);
+// The window scan: slots [lo, lo + n) of the popcount-ordered copy `a.rows` (n >= 1), slot i offered as row order[i]; leaves what
+// launch_scan leaves (candidate segments of g.seg_cap slots per wave, seg_count, QueryState) for launch_compact and the tail behind it.
+ScanGeometry popindex_scan_geometry(uint64_t n, uint32_t W, int num_cus);
+hipError_t launch_popindex_scan(const ScanArgs& a, const ScanGeometry& g, const uint32_t* order, uint64_t lo, uint32_t n, hipStream_t s);
+
 // ---- group queries (gsim_group.hip, gsim_db_search_group) --------------------------------------------------------------------------
 struct GroupArgs {
     const uint32_t* queries; // device, nq x W words

@@ -1601,6 +1601,77 @@ int gsim_jarvis_patrick(const uint64_t* indptr, const uint32_t* indices, uint64_
                         uint32_t flags, uint32_t* cluster_of, uint32_t* first_row /* or NULL */, uint32_t* sizes /* or NULL */,
                         uint32_t* nclusters /* nlevels */);
 
+/* ---- popcount-bounded search: a query reads only the rows whose popcount lets them matter ----------------------------------------- */
+/* A query with a bits set and a row with b bits set share at most min(a, b) bits, so their Tanimoto score is at most
+ * min(a, b) / max(a, b): at a cutoff of 0.7 only the rows with 0.7 a <= b <= a / 0.7 can pass, and a top-k query needs only the
+ * popcounts whose bound reaches the k-th best score (Swamidass and Baldi's bound; chemfp, FPSim2 and Arthor search this way).  A
+ * gsim_popindex is the table's rows ordered by popcount; gsim_db_search_bounded answers gsim_db_search's question and reads only a
+ * window of that order.  Opt-in: no other call looks at an index.  No counterpart in the reference.
+ * The index of a table of N rows: `order` (gsim_popindex_order) is the permutation of the rows sorted by (popcount ascending, row
+ * ascending), row base included; first[b] (gsim_popindex_first, b = 0 .. fp_bits + 1) is the number of rows with a popcount below b,
+ * so first[fp_bits + 1] = N and the rows with popcount b are order[first[b] .. first[b + 1]).  With GSIM_POPINDEX_ROWS the index also
+ * keeps a copy of the rows in that order.
+ * The bound: for a query popcount a and a row popcount b,
+ *     ub[b] = max over c in [max(0, a + b - fp_bits), min(a, b)] of s(a, b, c),
+ * s the f32 score gsim_db_search computes from the three counts, NaN (0 / 0) taken as 0.  The maximum is found by enumerating c, not
+ * from a closed form, so it is exact -- f32 roundings included -- for Tanimoto and for Tversky with any alpha and beta: no row with
+ * popcount b scores above ub[b], and some pair of fingerprints attains it.  gsim_popcount_bounds computes the same table on the host
+ * (no device, no handle; ub holds fp_bits + 1 floats); for Tanimoto ub[b] = (float) min(a, b) / (float) max(a, b), 0 for a = b = 0.
+ * gsim_db_search_bounded, THE RESULT RULE: for every query, hits, counts and approx are byte for byte what gsim_db_search returns on
+ * the same handle with the same arguments -- whatever the index's flags, the route and the number of stages, from run to run, and for
+ * cutoff <= 0 as well (approx = N).  k is the stride of `hits` and k == 0 is legal, as there.
+ * Execution (fixed here, so that `stats` can be checked).  Per query, with k clamped to N:
+ *   - cutoff window (cutoff > 0): B = {b : ub[b] >= cutoff}; the window is the hull [min B, max B], its rows are
+ *     order[first[min B] .. first[max B + 1]).  B empty: zero hits, approx 0, no launch.  cutoff <= 0: the window is the whole order;
+ *   - top-k narrowing, when cutoff <= 0 or approx == NULL (the hits of a narrowed scan are exact, its count of rows above the cutoff
+ *     is not), k >= 1, the window holds more than T = max(4 k, 4096) rows, and the metric is Tanimoto or Tversky with finite
+ *     alpha >= 0, beta >= 0, alpha + beta >= 1 (gsim_db_search_group's condition: scores within [0, 1]).  Stage 1 scans the smallest
+ *     hull of the window's buckets, taken in descending ub with ties to the lower b, that holds at least T rows.  It is final when
+ *     that hull is the window, or when it returns k hits and every bucket of the window outside it has ub < s_k, the last hit's
+ *     score -- strictly: an outside row with an equal score and a lower row number would displace a hit.  Otherwise stage 2 scans,
+ *     in full, the hull of {b in the window : ub[b] >= s_k}, or the whole window when stage 1 returned fewer than k hits, and its
+ *     result is the answer;
+ *   - the route of a scan of n rows: with GSIM_POPINDEX_ROWS the slots of the copy are STREAMED while 4 n <= 3 N; without the copy
+ *     the rows are GATHERED through `order` while gsim_db_search_rows would gather a set of n rows (GSIM_SUBSET_GATHER_MAX_PERMILLE).
+ *     Past that the query is answered by a PLAIN scan of the whole table (the four-kernel pipeline of the ordinary search), whichever
+ *     stage asked.  Both limits are estimates.
+ * stats: rows_scanned sums the rows of every scan (N for a plain one), rows_window the cutoff windows; every query is counted once,
+ * in queries_plain if a plain scan answered it, else in queries_one_stage or queries_two_stage (a query without narrowing, or with
+ * an empty window, is a one-stage query).
+ * The call runs on the handle's stream under the one-call-at-a-time rule, answers the queries one after another and leaves the
+ * search state as it found it: a gsim_db_search before and after returns identical bytes; the back-off counters, the lanes and the
+ * pipeline slots are untouched.  The bound table of a query popcount is computed on the device once per call and popcount.
+ * Lifetime: an index belongs to ONE single-shard, unfolded, finalized handle of fewer than 2^32 rows -- made by gsim_db_finalize,
+ * gsim_db_generate or gsim_db_attach_device_rows: it is built from the rows on the device --, lives in that handle's device memory
+ * (4 bytes per row; with GSIM_POPINDEX_ROWS N x row bytes more; the build takes 4 bytes per row of popcounts -- two 16-bit arrays,
+ * before and behind the sort -- and the radix sort's scratch, about 6 bytes per row, besides; both are freed on return), is immutable
+ * and serves any number of searches; destroy it before its handle.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / out / ix / first / order / ub / queries / hits / counts, unknown
+ * flag bits, a table of 2^32 rows or more, an index made for another handle, an unknown metric; gsim_popcount_bounds: fp_bits not a
+ * positive multiple of 32 up to 32768, popc_query above fp_bits.  *out is cleared on failure.  GSIM_ERR_STATE: a table not on a GPU,
+ * a multi-shard handle, a folded table, a table that changed after the index was made.  GSIM_ERR_NOMEM as elsewhere. */
+typedef struct gsim_popindex gsim_popindex;
+#define GSIM_POPINDEX_ROWS 1u  /* also keep a popcount-ordered COPY of the rows (N x row bytes more HBM): windows stream instead of gathering */
+typedef struct {
+    uint64_t rows_scanned;      /* rows offered to the filter, summed over queries and stages                             */
+    uint64_t rows_window;       /* rows of the cutoff window (N when cutoff <= 0), summed over queries                    */
+    uint64_t queries_one_stage; /* queries answered by one window scan (or by none: an empty window)                      */
+    uint64_t queries_two_stage; /* ... by two                                                                             */
+    uint64_t queries_plain;     /* ... by a plain scan of the whole table                                                 */
+    uint64_t launches;          /* kernel launches: a bound table per distinct popcount; per scan the scan, the compaction and the select (k > 8192: three for it) */
+    double bounds_ms;           /* HIP events around the bound tables and their copies                                    */
+    double kernel_ms;           /* ... around every scan and its tail, summed                                             */
+    double wall_ms;             /* the whole call, host clock                                                             */
+} gsim_popindex_stats;
+int gsim_popindex_create(gsim_db* db, uint32_t flags, gsim_popindex** out);
+int gsim_popindex_first(const gsim_popindex* ix, uint64_t* first /* fp_bits + 2 */);
+int gsim_popindex_order(const gsim_popindex* ix, uint32_t* order /* N entries, row base included */);
+int gsim_popindex_destroy(gsim_popindex* ix);
+int gsim_popcount_bounds(uint32_t fp_bits, uint32_t popc_query, int metric, float alpha, float beta, float* ub /* fp_bits + 1 */); /* host */
+int gsim_db_search_bounded(gsim_db* db, const gsim_popindex* ix, const uint32_t* queries, uint32_t nq, uint32_t k, float cutoff,
+                           int metric, float alpha, float beta, gsim_hit* hits, uint32_t* counts, uint64_t* approx,
+                           gsim_popindex_stats* stats /* or NULL */);
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
