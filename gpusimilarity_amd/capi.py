@@ -35,6 +35,8 @@ KNN_EXCLUDE_SELF = 1
 HIST_MAX_EDGES = 128
 HIST_EXCLUDE_SELF = 1
 POPINDEX_ROWS = 1
+ROW_NONE = 0xFFFFFFFF
+ROWHASH_REPEATS = 1
 
 HIT_DTYPE = np.dtype([("row", "<u4"), ("score", "<f4"), ("common", "<u2"), ("popc_db", "<u2")])
 GROUP_HIT_DTYPE = np.dtype([("row", "<u4"), ("score", "<f4"), ("which", "<u2"), ("popc_db", "<u2")])
@@ -77,6 +79,11 @@ class GsimPopindexStats(C.Structure):
     _fields_ = [("rows_scanned", C.c_uint64), ("rows_window", C.c_uint64), ("queries_one_stage", C.c_uint64),
                 ("queries_two_stage", C.c_uint64), ("queries_plain", C.c_uint64), ("launches", C.c_uint64), ("bounds_ms", C.c_double),
                 ("kernel_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+class GsimRowhashStats(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("groups", C.c_uint64), ("repeated_groups", C.c_uint64), ("largest_group", C.c_uint64),
+                ("slots", C.c_uint64), ("launches", C.c_uint64), ("kernel_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
 class GsimGroupStats(C.Structure):
@@ -302,6 +309,8 @@ EXPORTS = [
     "gsim_db_linkage", "gsim_linkage",
     "gsim_db_snn", "gsim_graph_copy_shared", "gsim_graph_get_snn_stats", "gsim_db_jarvis_patrick", "gsim_snn", "gsim_jarvis_patrick",
     "gsim_popindex_create", "gsim_popindex_first", "gsim_popindex_order", "gsim_popindex_destroy", "gsim_popcount_bounds", "gsim_db_search_bounded",
+    "gsim_rowhash_create", "gsim_rowhash_get_stats", "gsim_rowhash_groups", "gsim_rowhash_rowset", "gsim_rowhash_find", "gsim_rowhash_find_db",
+    "gsim_rowhash_destroy", "gsim_row_hash", "gsim_duplicates",
     "gsim_db_get_timing", "gsim_debug_query_flags", "gsim_debug_litmus", "gsim_debug_score_table", "gsim_debug_prefilter_constants", "gsim_debug_sort_desc", "gsim_last_error", "gsim_version",
 ]
 
@@ -472,6 +481,15 @@ def load():
         "gsim_popcount_bounds": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float)]),
         "gsim_db_search_bounded": (C.c_int, [vp, vp, u32p, C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_float, C.c_float, vp, u32p, u64p,
                                              C.POINTER(GsimPopindexStats)]),
+        "gsim_rowhash_create": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
+        "gsim_rowhash_get_stats": (C.c_int, [vp, C.POINTER(GsimRowhashStats)]),
+        "gsim_rowhash_groups": (C.c_int, [vp, u32p, u32p]),
+        "gsim_rowhash_rowset": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
+        "gsim_rowhash_find": (C.c_int, [vp, u32p, C.c_uint64, u32p, u32p]),
+        "gsim_rowhash_find_db": (C.c_int, [vp, vp, C.c_uint64, C.c_uint64, u32p, u32p]),
+        "gsim_rowhash_destroy": (C.c_int, [vp]),
+        "gsim_row_hash": (C.c_int, [u32p, C.c_uint64, C.c_uint32, u64p]),
+        "gsim_duplicates": (C.c_int, [u32p, C.c_uint64, C.c_uint32, u32p, u32p, u64p]),
         "gsim_last_error": (C.c_char_p, []),
         "gsim_version": (C.c_char_p, []),
     }
@@ -619,6 +637,95 @@ def popcount_bounds(fp_bits, popc_query, metric=METRIC_TANIMOTO, alpha=1.0, beta
     ub = np.empty(fp_bits + 1 if 0 < fp_bits <= 32768 else 1, dtype=np.float32)
     check(load().gsim_popcount_bounds(fp_bits, popc_query, metric, alpha, beta, _f32(ub)))
     return ub
+
+
+class RowHash:
+    """``gsim_rowhash``: the hash table over the rows of one :class:`Table` (Table.rowhash makes it): which rows are the same
+    fingerprint, and where a given fingerprint is.  It lives in the table's device memory: close it (or drop it) before the table."""
+
+    def __init__(self, table, handle):
+        self._L = table._L
+        self._h = handle
+        self._table = table  # (keeps the handle it belongs to alive)
+        self.nrows = table.count()
+
+    def stats(self) -> dict:
+        """The build's gsim_rowhash_stats: rows, groups, repeated_groups, largest_group, slots, launches, kernel_ms, wall_ms."""
+        st = GsimRowhashStats()
+        check(self._L.gsim_rowhash_get_stats(self._h, C.byref(st)))
+        return _stats_dict(st)
+
+    def groups(self):
+        """(first, size), uint32 [N]: the lowest row identical to row i (row base included) and the number of rows identical to it."""
+        first, size = np.empty(self.nrows, np.uint32), np.empty(self.nrows, np.uint32)
+        check(self._L.gsim_rowhash_groups(self._h, _u32(first), _u32(size)))
+        return first, size
+
+    def rowset(self, repeats=False) -> RowSet:
+        """The rows that are their group's first -- one per distinct fingerprint -- as a :class:`RowSet` of the table;
+        repeats=True (GSIM_ROWHASH_REPEATS): every other row."""
+        h = C.c_void_p()
+        check(self._L.gsim_rowhash_rowset(self._h, ROWHASH_REPEATS if repeats else 0, C.byref(h)))
+        return RowSet(self._table, h)
+
+    def find(self, queries, size=True):
+        """gsim_rowhash_find: (row, size), uint32 [nq] -- the lowest table row identical to each query (row base included; ROW_NONE
+        where there is none) and the size of its group; size=False passes NULL for it (None in its place)."""
+        q = np.ascontiguousarray(queries, dtype=np.uint32).reshape(-1, self._table.W)
+        row = np.empty(len(q), np.uint32)
+        sz = np.empty(len(q), np.uint32) if size else None
+        check(self._L.gsim_rowhash_find(self._h, _u32(q) if len(q) else None, len(q), _u32(row), _u32(sz) if size else None))
+        return row, sz
+
+    def find_db(self, table, begin=0, end=None):
+        """gsim_rowhash_find_db: :meth:`find` for the rows [begin, end) of another :class:`Table` on the same device (or of this one)."""
+        if end is None:
+            end = table.count()
+        n = max(end - begin, 0)
+        row, sz = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        check(self._L.gsim_rowhash_find_db(self._h, table._h, begin, end, _u32(row), _u32(sz)))
+        return row, sz
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.gsim_rowhash_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _host_rows(rows):
+    r = np.ascontiguousarray(rows, dtype=np.uint32)
+    if r.ndim != 2 or r.shape[1] == 0:
+        raise ValueError("rows: an (n, fp_bits / 32) uint32 array")
+    return r
+
+
+def row_hash(rows) -> np.ndarray:
+    """gsim_row_hash (host): the library's 64-bit hash of every row of an (n, W) uint32 array."""
+    r = _host_rows(rows)
+    out = np.empty(len(r), np.uint64)
+    check(load().gsim_row_hash(_u32(r), len(r), r.shape[1] * 32, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return out
+
+
+def duplicates(rows):
+    """gsim_duplicates (host): (first, size, ngroups) of an (n, W) uint32 array -- the lowest row identical to row i, the number of
+    rows identical to it, the number of distinct rows."""
+    r = _host_rows(rows)
+    first, size, n = np.empty(len(r), np.uint32), np.empty(len(r), np.uint32), C.c_uint64(0)
+    check(load().gsim_duplicates(_u32(r), len(r), r.shape[1] * 32, _u32(first), _u32(size), C.byref(n)))
+    return first, size, n.value
 
 
 class LabelSet:
@@ -1257,6 +1364,12 @@ class Table:
         if stats:
             out += (_stats_dict(st),)
         return out
+
+    def rowhash(self) -> RowHash:
+        """gsim_rowhash_create: the hash table over this table's rows (duplicate groups, exact-row lookup)."""
+        h = C.c_void_p()
+        check(self._L.gsim_rowhash_create(self._h, 0, C.byref(h)))
+        return RowHash(self, h)
 
     def labelset(self, labels, nlabels) -> LabelSet:
         """gsim_labelset_create: labels[r] is the label of table row r (without the row base): below `nlabels`, or LABEL_NONE for a

@@ -261,6 +261,24 @@ struct gsim_popindex {
     gsim_host::DevBuf<uint32_t> d_rows;  // GSIM_POPINDEX_ROWS: the rows in that order
 };
 
+// A row-hash index (gsim_rowhash_*, capi_rowhash.cpp): device memory of the handle it was made for, immutable.
+// tests/rowhash_front_errors_cases.py hands the fronts a stand-in (FakeRowhash: zeroed memory that begins as this struct does, with
+// `owner`, `device`, `nrows`, `fp_bits`, `row_base` set) to reach the checks that read an index before any device state.  That holds
+// while those fields stay first, in this order, and while the fronts read nothing behind `stats` ahead of their state checks.
+struct gsim_rowhash {
+    gsim_db* owner = nullptr;
+    int device = 0;
+    uint64_t nrows = 0;          // rows of the owner's table when the index was made
+    uint32_t fp_bits = 0;
+    uint32_t row_base = 0;       // ... and its row base then (what the outputs add)
+    uint32_t flags = 0;
+    gsim_rowhash_stats stats{};  // of the build
+    uint64_t nslots = 0;
+    std::vector<uint32_t> bits;  // rowset_words(nrows): bit r says row r is its group's first
+    gsim_host::DevBuf<uint32_t> d_slots;            // 2 x nslots words: {row, count}
+    gsim_host::DevBuf<unsigned long long> d_groups; // nrows: first | size << 32, without the row base
+};
+
 struct gsim_db {
     uint32_t fp_bits = 0;
     uint32_t W = 0;

@@ -795,6 +795,27 @@ hipError_t launch_popindex_bounds(uint32_t fp_bits, uint32_t qpop, int metric, f
 ScanGeometry popindex_scan_geometry(uint64_t n, uint32_t W, int num_cus);
 hipError_t launch_popindex_scan(const ScanArgs& a, const ScanGeometry& g, const uint32_t* order, uint64_t lo, uint32_t n, hipStream_t s);
 
+// ---- row-hash indexes (gsim_rowhash.hip, gsim_rowhash_*) -------------------------------------------------------------------------
+// The table: 2 x nslots words, slot s = {row, count} at words 2 s and 2 s + 1; nslots = rowhash_slots(nrows) (gsim_rowhash_hash.h).
+// A workgroup is kRowhashBlock threads; a wave's chunk is kRowhashUnroll x 64 / (W / 4) rows where W / 4 is a power of two up to 64,
+// 64 rows for other rows of fewer than 32 words, else one row; the finishing pass takes 64 rows per wave.
+constexpr int kRowhashBlock = 256;
+constexpr int kRowhashUnroll = 4;
+// every slot {GSIM_ROW_NONE, 0}
+hipError_t launch_rowhash_init(uint32_t* slots, uint64_t nslots, int num_cus, hipStream_t s);
+// the table's rows [r0, r1) of W words enter the slots; slot_of[row] = the slot whose group the row joined; *flag |= 1 if a probe
+// went round the whole table (flag: zeroed by the caller)
+hipError_t launch_rowhash_insert(const void* rows, uint64_t r0, uint64_t r1, uint32_t W, uint32_t* slots, uint64_t nslots, uint32_t* flag,
+                                 unsigned long long* slot_of, int num_cus, hipStream_t s);
+// rec[row]: the row's slot -> first | size << 32 of its group (no row base); bits: rowset_words(n) words, bit `row` set where the row
+// is its group's first; counters[4] (zeroed by the caller): groups, groups of two rows or more, the largest size, the sizes summed;
+// *flag |= 2 on a slot that cannot be
+hipError_t launch_rowhash_finish(unsigned long long* rec, uint64_t n, uint32_t* slots, uint64_t nslots, uint32_t* flag, uint32_t* bits,
+                                 uint64_t nbitwords, unsigned long long* counters, int num_cus, hipStream_t s);
+// found[q] = row | size << 32 of the group of the table's rows identical to left row q of nl (GSIM_ROW_NONE and 0: none); read-only
+hipError_t launch_rowhash_find(const void* left, uint64_t nl, const void* rows, uint32_t W, const uint32_t* slots, uint64_t nslots, uint32_t* flag,
+                               unsigned long long* found, int num_cus, hipStream_t s);
+
 // ---- group queries (gsim_group.hip, gsim_db_search_group) --------------------------------------------------------------------------
 struct GroupArgs {
     const uint32_t* queries; // device, nq x W words

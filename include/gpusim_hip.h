@@ -1672,6 +1672,81 @@ int gsim_db_search_bounded(gsim_db* db, const gsim_popindex* ix, const uint32_t*
                            int metric, float alpha, float beta, gsim_hit* hits, uint32_t* counts, uint64_t* approx,
                            gsim_popindex_stats* stats /* or NULL */);
 
+/* ---- exact duplicates and exact-row lookup: a hash table over the rows -------------------------------------------------------------- */
+/* Which rows of a table are the same fingerprint, and is this fingerprint in the table and where: O(N) to build and O(1) per lookup
+ * with a hash table over the rows, where gsim_db_components at cutoff 1.0 is O(N^2) and a scan at cutoff 1.0 reads the table per
+ * query -- and neither finds an all-zero row, whose score is NaN.  Opt-in: no other call looks at an index.  No counterpart in the
+ * reference.
+ * Two rows are IDENTICAL when all their fp_bits / 32 words are equal.  Nothing else defines the groups: all-zero rows are identical
+ * to one another and form an ordinary group.
+ * THE RESULT RULE.  gsim_rowhash_groups: first[i] is the lowest-numbered row identical to row i, the handle's row base included;
+ * size[i] is the number of rows identical to row i, itself included (either array may be NULL, not both).  stats: rows = N, groups =
+ * the number of distinct rows, repeated_groups = the groups of size >= 2, largest_group = the largest size, slots as below,
+ * launches = the kernel launches of the build; for N = 0 every count is 0 and no launch is made.  gsim_rowhash_rowset returns the
+ * row set {i : first[i] == i + row_base} of the index's handle -- one representative per group, gsim_rowset_count = groups -- or,
+ * with GSIM_ROWHASH_REPEATS, its complement: an ordinary gsim_rowset for gsim_db_search_rows, gsim_db_bit_counts and every other
+ * consumer, destroyed with gsim_rowset_destroy and independent of the index afterwards.  gsim_rowhash_find: per query, row[q] = the
+ * lowest table row identical to query q, row base included, and size[q] (size may be NULL) = the size of that row's group; when no
+ * row is identical, row[q] = GSIM_ROW_NONE and size[q] = 0.  gsim_rowhash_find_db: the same for the rows [lrow_begin, lrow_end) of
+ * another finalized, single-shard, unfolded handle with the same fp_bits on the same device (the left-handle convention of the
+ * joins); `left` may be the index's own handle, and then row[] is first[] of that range.  gsim_duplicates (host, no device, no
+ * handle): the same first / size (either or both may be NULL) and *ngroups (or NULL) = the number of distinct rows, on host rows,
+ * without a base.  Every output is byte-identical from run to run: none depends on the order in which the rows reached the table.
+ * THE HASH.  gsim_row_hash is the library's 64-bit hash of a row of W = fp_bits / 32 words w[0 .. W); the device computes the same
+ * values.  All arithmetic is on uint32_t (mod 2^32), >> is a logical shift, rotl16 swaps the halves of a word:
+ *     k(i) = (i + 1) * 0x9E3779B9
+ *     a(i) = (w[i] ^ k(i)) * 0x85EBCA6B;            a(i) ^= a(i) >> 15;          A = the sum of a(i) over i
+ *     b(i) = (rotl16(w[i]) + k(i)) * 0xC2B2AE35;    b(i) ^= b(i) >> 13;          B = the sum of b(i) over i
+ *     m1(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16
+ *     m2(x): x ^= x >> 15; x *= 0x2C1B3C6D; x ^= x >> 12; x *= 0x297A2D39; x ^= x >> 15
+ *     lo = m1(A ^ m2(B));   hi = m2(B ^ lo);   hash = (uint64_t) hi << 32 | lo
+ * A word's contribution depends on its position, the contributions are summed, and one avalanche (a bijection of (A, B)) ends it.
+ * The table of N rows has slots(N) = 0 slots for N = 0, else the smallest power of two >= 2 N, at least 1024 (stats.slots); a row's
+ * first slot is hash & (slots - 1), and a probe goes on to the next slot, wrapping at the end.  Correctness never rests on the
+ * hash: rows are compared word by word, equal hashes only cost probes.
+ * Execution: the build streams the table once (launches of at most 32 GiB of rows), every row entering the table by atomic
+ * operations on its slot alone -- no workgroup waits for another --, then a second pass gives every row its group's first row and
+ * size; a lookup hashes, probes and compares, read-only.  The calls run on the handle's stream under the one-call-at-a-time rule
+ * and leave the search state as they found it: a gsim_db_search before and after returns identical bytes.
+ * Lifetime: an index belongs to ONE single-shard, unfolded, finalized handle -- made by gsim_db_finalize, gsim_db_generate or
+ * gsim_db_attach_device_rows: it is built from the rows on the device --, lives in that handle's device memory (8 bytes per slot,
+ * i.e. 16 to 32 bytes per row and at least 8 KiB, plus 8 bytes per row for first and size; N / 8 bytes of host memory for the
+ * representatives' bitmap), is immutable and serves any number of lookups; destroy it before its handle.
+ * GSIM_ERR_INVALID, checked before any device state: NULL db / out / ix / row / queries with nq > 0, both first and size NULL,
+ * unknown flag bits, a table whose last row number with its base would be GSIM_ROW_NONE or beyond, the left handle's errors (NULL,
+ * a range past its rows or with its begin past its end, other fp_bits); gsim_row_hash and gsim_duplicates: fp_bits not a positive
+ * multiple of 32 up to 32768, NULL rows with nrows > 0, NULL hash, 2^32 - 1 rows or more.  *out is cleared on failure.
+ * GSIM_ERR_STATE: a table not on a GPU, a multi-shard handle, a folded table, a table that changed after the index was made (its
+ * row count or its row base; gsim_rowhash_get_stats and gsim_rowhash_groups read the index alone and still answer), the left
+ * table's states and "different devices".  GSIM_ERR_NOMEM as elsewhere. */
+typedef struct gsim_rowhash gsim_rowhash;
+#define GSIM_ROW_NONE 0xFFFFFFFFu
+#define GSIM_ROWHASH_REPEATS 1u   /* gsim_rowhash_rowset: the rows that are NOT their group's first row */
+#pragma push_macro("slots")       /* (a translation unit that includes Qt has `slots` as a keyword macro) */
+#undef slots
+typedef struct {
+    uint64_t rows;            /* N                                                                                            */
+    uint64_t groups;          /* distinct rows                                                                                */
+    uint64_t repeated_groups; /* groups of two rows or more                                                                   */
+    uint64_t largest_group;   /* the largest size (0 for N = 0)                                                               */
+    uint64_t slots;           /* slots(N)                                                                                     */
+    uint64_t launches;        /* kernel launches of the build: the slots' initialisation, the inserting passes, the finish    */
+    double kernel_ms;         /* HIP events around the inserting passes (insert_ms) and the finish, summed                    */
+    double wall_ms;           /* the whole build, host clock                                                                  */
+} gsim_rowhash_stats;
+#pragma pop_macro("slots")
+int gsim_rowhash_create(gsim_db* db, uint32_t flags /* 0 */, gsim_rowhash** out);
+int gsim_rowhash_get_stats(const gsim_rowhash* ix, gsim_rowhash_stats* out);
+int gsim_rowhash_groups(const gsim_rowhash* ix, uint32_t* first /* N or NULL */, uint32_t* size /* N or NULL */);
+int gsim_rowhash_rowset(const gsim_rowhash* ix, uint32_t flags, gsim_rowset** out);
+int gsim_rowhash_find(const gsim_rowhash* ix, const uint32_t* queries, uint64_t nq, uint32_t* row, uint32_t* size /* or NULL */);
+int gsim_rowhash_find_db(const gsim_rowhash* ix, gsim_db* left, uint64_t lrow_begin, uint64_t lrow_end, uint32_t* row,
+                         uint32_t* size /* or NULL */);
+int gsim_rowhash_destroy(gsim_rowhash* ix);
+int gsim_row_hash(const uint32_t* rows, uint64_t nrows, uint32_t fp_bits, uint64_t* hash /* nrows */); /* host */
+int gsim_duplicates(const uint32_t* rows, uint64_t nrows, uint32_t fp_bits, uint32_t* first /* nrows or NULL */,
+                    uint32_t* size /* nrows or NULL */, uint64_t* ngroups /* or NULL */); /* host */
+
 /* ---- instrumentation ------------------------------------------------------ */
 int gsim_db_enable_timing(gsim_db* db, int enable); /* resets the accumulators */
 int gsim_db_get_timing(gsim_db* db, gsim_timing* out); /* synchronises the stream */
