@@ -23,7 +23,7 @@ int components(gsim_db* db, Shard& s, const float* cutoffs, uint32_t nlevels, in
     const std::vector<NbrLaunch> plan =
         N < 2 ? std::vector<NbrLaunch>() : plan_launches(nt, nt, true, WP, static_cast<uint64_t>(db->knobs.components_launch_pairs));
     size_t tmp_bytes = 0;
-    GSIM_HIP(gsim::comp_scan_bytes(N, &tmp_bytes));
+    GSIM_HIP(gsim::scan_u32_bytes(N, &tmp_bytes));
     PaddedRows table;
     DevBuf<uint32_t> parent;
     ForestLabels labels;

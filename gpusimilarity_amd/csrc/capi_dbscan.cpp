@@ -30,7 +30,7 @@ int dbscan(gsim_db* db, Shard& s, float cutoff, uint32_t min_pts, int metric, fl
         N < 2 ? std::vector<NbrLaunch>() : plan_launches(nt, nt, true, WP, static_cast<uint64_t>(db->knobs.dbscan_launch_pairs));
     const size_t np = plan.size(), ctl_words = gsim::kDbscanCounters + LaunchClocks::kWords * 2 * np;
     size_t tmp_bytes = 0;
-    GSIM_HIP(gsim::comp_scan_bytes(N, &tmp_bytes));
+    GSIM_HIP(gsim::scan_u32_bytes(N, &tmp_bytes));
     PaddedRows table;
     DevBuf<uint32_t> d_degree, parent, d_label, d_anchor, d_first, d_sizes, d_ncl, d_flag, d_num;
     DevBuf<unsigned long long> best, ctl; // the counters, then 4 clock stamps per launch: the degree pass's, then the link pass's

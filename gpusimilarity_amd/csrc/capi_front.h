@@ -107,7 +107,7 @@ struct ForestLabels {
 
     // NOMEM "device memory for <prefix> (<of>)", "(first_row)", "(sizes)" -- the two where asked for --, "(the counts)", "(label scratch)"
     int alloc(uint64_t N, uint32_t nlevels, bool first_row, bool sizes, const char* prefix, const char* of);
-    // The sizes' memset and the label launches (scratch `tmp`: comp_scan_bytes(N)); the copies of the counts, of d_ctl's ctl_words
+    // The sizes' memset and the label launches (scratch `tmp`: scan_u32_bytes(N)); the copies of the counts, of d_ctl's ctl_words
     // words and of the labels; the wait; STATE "<prefix>: the device reported an impossible count"; the first ncomp[l] entries of
     // first_row and sizes per level (the rest of a stripe is left untouched); the second wait.
     int run(const uint32_t* parent, uint64_t N, uint32_t nlevels, uint32_t row_base, void* tmp, size_t tmp_bytes, const void* d_ctl,

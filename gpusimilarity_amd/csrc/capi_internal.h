@@ -447,6 +447,28 @@ int enqueue_scan_tail(gsim_db* db, Shard& s, const gsim::ScanArgs& a, const gsim
                       void* out);
 // capi_subset.cpp: the candidate scratch for a scan of geometry g behind which enqueue_scan_tail runs (row sets, group queries)
 int ensure_subset_scratch(Shard& s, const gsim::ScanGeometry& g);
+// ... one such scan for a query (row sets, bounded searches) and the wait for its block in s.h_result.  `a`: the query's scan_args,
+// at most a.k hits wanted; `enqueue(a, launches)` launches the scan of geometry g on s.stream, adds what it launched to `launches` and
+// may adjust `a` for the tail; all_rows: what the tail reports as approx without a cutoff; ev: timed, or null.  The scratch and
+// result-capacity checks, the events, the tail and the wait are the two halves in capi_subset.cpp; the kernel time and the launches
+// are added to *cost.
+struct ScanStepCost {
+    double kernel_ms = 0.0;
+    uint32_t launches = 0;
+};
+int begin_restricted_scan(Shard& s, gsim::ScanArgs& a, const gsim::ScanGeometry& g, EventPair* ev);
+int finish_restricted_scan(gsim_db* db, Shard& s, const gsim::ScanArgs& a, const gsim::ScanGeometry& g, uint64_t all_rows, EventPair* ev,
+                           ScanStepCost* cost);
+template <class Enqueue>
+int run_restricted_scan(gsim_db* db, Shard& s, gsim::ScanArgs a, const gsim::ScanGeometry& g, uint64_t all_rows, EventPair* ev, Enqueue&& enqueue,
+                        ScanStepCost* cost)
+{
+    int rc = begin_restricted_scan(s, a, g, ev);
+    if (rc == GSIM_OK) rc = enqueue(a, cost->launches);
+    return rc == GSIM_OK ? finish_restricted_scan(db, s, a, g, all_rows, ev, cost) : rc;
+}
+// ... and the answer it left there: at most k hits, their number, the header's approx (or null).  Returns the number of hits.
+uint32_t take_scan_result(const Shard& s, uint32_t k, gsim_hit* hits, uint32_t* count, uint64_t* approx);
 // ... and its route rule (GSIM_SUBSET_GATHER_MAX_PERMILLE): gather a set of `selected` rows through its list, or stream under its bitmap?
 bool subset_gather_applies(const gsim_db* db, const Shard& s, uint64_t selected);
 // capi_batch.cpp: multi-query passes

@@ -46,11 +46,11 @@ int build_popindex(gsim_db* db, uint32_t flags, gsim_popindex* ix)
     const uint32_t key_bits = popcount_key_bits(db->fp_bits);
     size_t sort_bytes = 0, scan_bytes = 0;
     GSIM_HIP(gsim::popindex_sort_bytes(N, key_bits, &sort_bytes));
-    GSIM_HIP(gsim::popindex_scan_bytes(static_cast<uint64_t>(nbins) + 1, &scan_bytes));
+    GSIM_HIP(gsim::scan_u32_bytes(static_cast<uint64_t>(nbins) + 1, &scan_bytes));
     GSIM_ALLOC(d_tmp, std::max(sort_bytes, scan_bytes), "the popcount index's sort");
     GSIM_HIP(hipMemsetAsync(d_hist, 0, (static_cast<size_t>(nbins) + 1) * 4, st));
     GSIM_HIP(gsim::launch_popindex_popc(s.d_rows, N, s.W, d_popc, d_hist, s.num_cus, st));
-    GSIM_HIP(gsim::launch_popindex_first(d_tmp, scan_bytes, d_hist, d_first, static_cast<uint64_t>(nbins) + 1, st));
+    GSIM_HIP(gsim::launch_scan_u32(d_tmp, scan_bytes, d_hist, d_first, static_cast<uint64_t>(nbins) + 1, st));
     std::vector<uint32_t> h_first(static_cast<size_t>(nbins) + 1);
     GSIM_HIP(hipMemcpyAsync(h_first.data(), d_first, h_first.size() * 4, hipMemcpyDeviceToHost, st));
     GSIM_HIP(gsim::launch_popindex_sort(d_tmp, sort_bytes, d_popc, d_popc2, ix->d_order, N, key_bits, st));
@@ -136,35 +136,33 @@ struct BoundedCall {
     int scan(ScanRoute r, const uint32_t* query, uint32_t* dq, uint64_t lo, uint64_t n)
     {
         const hipStream_t stream = s.stream;
-        const uint32_t row_base = db->row_base + static_cast<uint32_t>(s.first_row);
         const uint32_t kk = static_cast<uint32_t>(std::min<uint64_t>(k, r == ScanRoute::kPlain ? s.nrows : n)); // (never more hits than rows offered)
         const gsim::ScanGeometry g = r == ScanRoute::kPlain    ? s.geo
                                      : r == ScanRoute::kStream ? gsim::popindex_scan_geometry(n, s.W, s.num_cus)
                                                                : gsim::subset_gather_geometry(n, s.W, s.num_cus);
-        int rc = ensure_subset_scratch(s, g);
-        if (rc == GSIM_OK) rc = ensure_result_capacity(s, kk);
-        if (rc != GSIM_OK) return rc;
-        gsim::ScanArgs a = scan_args(s, query, dq, dq, kk, cutoff, metric, alpha, beta); // (the tail reads the same copy of the query)
-        if (st) GSIM_HIP(hipEventRecord(ev.a, stream));
-        bool sampled = false;
-        if (r == ScanRoute::kPlain) { // the four-kernel pipeline as the ordinary search enqueues it, seed included
-            GSIM_HIP(gsim::launch_sample(a, g, 4, stream, &sampled));
-            GSIM_HIP(gsim::launch_scan(a, g, stream));
-        } else if (r == ScanRoute::kStream) { // no seed: gtau starts at 0
-            gsim::ScanArgs w = a;
-            w.rows = ix->d_rows;
-            GSIM_HIP(gsim::launch_popindex_scan(w, g, ix->d_order, lo, static_cast<uint32_t>(n), stream));
-        } else {
-            GSIM_HIP(gsim::launch_subset_gather(a, g, ix->d_order + lo, static_cast<uint32_t>(n), stream));
-        }
-        rc = enqueue_scan_tail(db, s, a, g, row_base, s.nrows, s.h_result); // (a.rows, a.nrows: the table -- the tail rebuilds hits from it)
-        if (rc != GSIM_OK) return rc;
-        if (st) GSIM_HIP(hipEventRecord(ev.b, stream));
-        rc = wait_stream(stream);
+        // (a.rows, a.nrows stay the table's: the tail rebuilds hits from it)
+        const auto enqueue = [&](gsim::ScanArgs& a, uint32_t& launches) {
+            bool sampled = false;
+            if (r == ScanRoute::kPlain) { // the four-kernel pipeline as the ordinary search enqueues it, seed included
+                GSIM_HIP(gsim::launch_sample(a, g, 4, stream, &sampled));
+                GSIM_HIP(gsim::launch_scan(a, g, stream));
+            } else if (r == ScanRoute::kStream) { // no seed: gtau starts at 0
+                gsim::ScanArgs w = a;
+                w.rows = ix->d_rows;
+                GSIM_HIP(gsim::launch_popindex_scan(w, g, ix->d_order, lo, static_cast<uint32_t>(n), stream));
+            } else {
+                GSIM_HIP(gsim::launch_subset_gather(a, g, ix->d_order + lo, static_cast<uint32_t>(n), stream));
+            }
+            launches += sampled ? 2u : 1u;
+            return static_cast<int>(GSIM_OK);
+        };
+        ScanStepCost cost;
+        // (the tail reads the same copy of the query)
+        const int rc = run_restricted_scan(db, s, scan_args(s, query, dq, dq, kk, cutoff, metric, alpha, beta), g, s.nrows, st ? &ev : nullptr, enqueue, &cost);
         if (rc != GSIM_OK) return rc;
         if (st) {
-            st->kernel_ms += ev.ms();
-            st->launches += (sampled ? 1u : 0u) + 3 + (kk > static_cast<uint32_t>(gsim::kSelectCap) ? 2 : 0);
+            st->kernel_ms += cost.kernel_ms;
+            st->launches += cost.launches;
             st->rows_scanned += r == ScanRoute::kPlain ? s.nrows : n;
         }
         return GSIM_OK;
@@ -232,11 +230,8 @@ int search_bounded(gsim_db* db, Shard& s, const gsim_popindex* ix, const uint32_
         gsim_hit* out = hits + static_cast<size_t>(q) * kout;
         // what a scan left in the pinned block becomes the query's answer
         auto take = [&]() {
-            const gsim_result_header* h = s.h_result.as<const gsim_result_header>();
-            const uint32_t n = std::min(h->count, call.k);
-            std::memcpy(out, h + 1, sizeof(gsim_hit) * n);
-            counts[q] = n;
-            if (approx) approx[q] = cutoff > 0.0f ? h->approx : N; // (the tail reports the rows it was told of: the table's)
+            const uint32_t n = take_scan_result(s, call.k, out, &counts[q], approx ? &approx[q] : nullptr);
+            if (approx && !(cutoff > 0.0f)) approx[q] = N; // (the tail reports the rows it was told of: the table's)
             return n;
         };
         if (w.rows(window) == 0) { // no row can reach the cutoff (or none has such a popcount): zero hits, approx 0, no launch

@@ -159,7 +159,7 @@ int jarvis_patrick(gsim_db* db, Shard& s, uint32_t k, const uint32_t* kmins, uin
     DevBuf<uint32_t> parent;
     ForestLabels labels;
     size_t scan_bytes = 0;
-    GSIM_HIP(gsim::comp_scan_bytes(N, &scan_bytes));
+    GSIM_HIP(gsim::scan_u32_bytes(N, &scan_bytes));
     GSIM_ALLOC(parent, static_cast<size_t>(N) * 4 * nlevels, "jarvis-patrick (the forests)");
     if (const int rc = labels.alloc(N, nlevels, first_row, sizes, "jarvis-patrick", "cluster_of")) return rc;
     GSIM_HIP(gsim::launch_comp_init(parent, N, nlevels, st));

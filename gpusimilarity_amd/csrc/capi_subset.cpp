@@ -49,9 +49,9 @@ int build_rowset(gsim_db* db, const uint32_t* rows, uint64_t n, const uint32_t* 
     GSIM_HIP(gsim::launch_rowset_finish(d_bits, bits ? d_in.as<uint32_t>() : nullptr, N, nalloc, exclude ? 1 : 0,
                                         d_popc, st));
     size_t tmp_bytes = 0;
-    GSIM_HIP(gsim::rowset_scan_bytes(nwords + 1, &tmp_bytes));
+    GSIM_HIP(gsim::scan_u32_bytes(nwords + 1, &tmp_bytes));
     GSIM_ALLOC(d_tmp, tmp_bytes, "the row set's prefix sums");
-    GSIM_HIP(gsim::launch_rowset_offsets(d_tmp, tmp_bytes, d_popc, d_offs, nwords + 1, st));
+    GSIM_HIP(gsim::launch_scan_u32(d_tmp, tmp_bytes, d_popc, d_offs, nwords + 1, st));
     uint32_t count = 0;
     GSIM_HIP(hipMemcpyAsync(&count, d_offs + nwords, 4, hipMemcpyDeviceToHost, st));
     GSIM_HIP(hipStreamSynchronize(st));
@@ -105,6 +105,42 @@ int ensure_subset_scratch(Shard& s, const gsim::ScanGeometry& g)
     return GSIM_OK;
 }
 
+// The two halves of run_restricted_scan (capi_internal.h) around the caller's scan.  In front: the scratch and the result block for
+// geometry g and a.k hits, a's scratch pointers (the checks may have moved them), the first event.
+int begin_restricted_scan(Shard& s, gsim::ScanArgs& a, const gsim::ScanGeometry& g, EventPair* ev)
+{
+    int rc = ensure_subset_scratch(s, g);
+    if (rc == GSIM_OK) rc = ensure_result_capacity(s, a.k);
+    if (rc != GSIM_OK) return rc;
+    a.cand = s.d_cand, a.cand_cb = s.d_cand_cb, a.seg_count = s.d_seg_count;
+    if (ev) GSIM_HIP(hipEventRecord(ev->a, s.stream));
+    return GSIM_OK;
+}
+
+// Behind: the pipeline's tail into s.h_result, the second event, the wait; the kernel time and the tail's launches are added to *cost.
+int finish_restricted_scan(gsim_db* db, Shard& s, const gsim::ScanArgs& a, const gsim::ScanGeometry& g, uint64_t all_rows, EventPair* ev,
+                           ScanStepCost* cost)
+{
+    int rc = enqueue_scan_tail(db, s, a, g, db->row_base + static_cast<uint32_t>(s.first_row), all_rows, s.h_result);
+    if (rc != GSIM_OK) return rc;
+    if (ev) GSIM_HIP(hipEventRecord(ev->b, s.stream));
+    rc = wait_stream(s.stream);
+    if (rc != GSIM_OK) return rc;
+    if (ev) cost->kernel_ms += ev->ms();
+    cost->launches += 2 + (a.k > static_cast<uint32_t>(gsim::kSelectCap) ? 2 : 0); // compaction, select -- or the large-k select and the sort's two
+    return GSIM_OK;
+}
+
+uint32_t take_scan_result(const Shard& s, uint32_t k, gsim_hit* hits, uint32_t* count, uint64_t* approx)
+{
+    const gsim_result_header* h = s.h_result.as<const gsim_result_header>();
+    const uint32_t n = std::min(h->count, k);
+    std::memcpy(hits, h + 1, sizeof(gsim_hit) * n);
+    *count = n;
+    if (approx) *approx = h->approx;
+    return n;
+}
+
 // gather when selected x max(row bytes, 128) x 1000 <= permille x N x row bytes (gsim_db_bit_counts decides by the same rule)
 bool subset_gather_applies(const gsim_db* db, const Shard& s, uint64_t selected)
 {
@@ -137,39 +173,32 @@ int search_rows(gsim_db* db, Shard& s, const gsim_rowset* rs, const uint32_t* qu
     const hipStream_t stream = s.stream;
     const bool gather = subset_gather_applies(db, s, sel);
     const gsim::ScanGeometry g = gather ? gsim::subset_gather_geometry(sel, s.W, s.num_cus) : gsim::subset_scan_geometry(s.nrows, s.W, s.num_cus);
-    int rc = ensure_subset_scratch(s, g);
-    if (rc == GSIM_OK) rc = ensure_result_capacity(s, k);
-    if (rc == GSIM_OK) rc = rezero_dirty_state(s);
+    int rc = rezero_dirty_state(s);
     if (rc != GSIM_OK) return rc;
     DevBuf<uint32_t> d_q; // the call's queries (16-byte aligned rows when W % 4 == 0)
     GSIM_ALLOC(d_q, static_cast<size_t>(nq) * s.W * 4, "the queries of a row-set search");
     GSIM_HIP(hipMemcpyAsync(d_q, queries, static_cast<size_t>(nq) * s.W * 4, hipMemcpyHostToDevice, stream));
     EventPair ev;
     if (st) GSIM_HIP(ev.create());
-    const uint32_t row_base = db->row_base + static_cast<uint32_t>(s.first_row);
-    for (uint32_t q = 0; q < nq; q++) {
-        const uint32_t* query = queries + static_cast<size_t>(q) * s.W;
-        uint32_t* dq = d_q + static_cast<size_t>(q) * s.W; // (the tail reads the same copy: nothing to write)
-        gsim::ScanArgs a = scan_args(s, query, dq, dq, k, cutoff, metric, alpha, beta);
-        if (st) GSIM_HIP(hipEventRecord(ev.a, stream));
-        // No seed: sample_kernel's threshold counts rows of the whole table and may lie above the set's k-th best (DESIGN.md
-        // section 12); both scans start from gtau = 0 and raise it through the histogram of SELECTED rows.
+    // No seed: sample_kernel's threshold counts rows of the whole table and may lie above the set's k-th best (DESIGN.md
+    // section 12); both scans start from gtau = 0 and raise it through the histogram of SELECTED rows.
+    const auto enqueue = [&](gsim::ScanArgs& a, uint32_t& launches) {
         if (gather) GSIM_HIP(gsim::launch_subset_gather(a, g, rs->d_list, static_cast<uint32_t>(sel), stream));
         else GSIM_HIP(gsim::launch_subset_scan(a, g, rs->d_bits, stream));
         a.nrows = sel; // (the tail's "all rows" -- approx without a cutoff -- is the set)
-        rc = enqueue_scan_tail(db, s, a, g, row_base, sel, s.h_result);
+        launches += 1;
+        return static_cast<int>(GSIM_OK);
+    };
+    for (uint32_t q = 0; q < nq; q++) {
+        const uint32_t* query = queries + static_cast<size_t>(q) * s.W;
+        uint32_t* dq = d_q + static_cast<size_t>(q) * s.W; // (the tail reads the same copy: nothing to write)
+        ScanStepCost cost;
+        rc = run_restricted_scan(db, s, scan_args(s, query, dq, dq, k, cutoff, metric, alpha, beta), g, sel, st ? &ev : nullptr, enqueue, &cost);
         if (rc != GSIM_OK) return rc;
-        if (st) GSIM_HIP(hipEventRecord(ev.b, stream));
-        rc = wait_stream(stream);
-        if (rc != GSIM_OK) return rc;
-        const gsim_result_header* h = s.h_result.as<const gsim_result_header>();
-        const uint32_t n = std::min(h->count, k);
-        std::memcpy(hits + static_cast<size_t>(q) * kout, h + 1, sizeof(gsim_hit) * n);
-        counts[q] = n;
-        if (approx) approx[q] = h->approx;
+        take_scan_result(s, k, hits + static_cast<size_t>(q) * kout, &counts[q], approx ? &approx[q] : nullptr);
         if (st) {
-            st->kernel_ms += ev.ms();
-            st->launches += 3 + (k > static_cast<uint32_t>(gsim::kSelectCap) ? 2 : 0); // scan, compaction, select -- or the large-k select and the sort's two
+            st->kernel_ms += cost.kernel_ms;
+            st->launches += cost.launches;
             (gather ? st->queries_gather : st->queries_stream) += 1;
         }
     }

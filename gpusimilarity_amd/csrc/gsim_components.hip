@@ -41,8 +41,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "../../include/gpusim_hip.h"
 #include "gsim_device_common.h"
 #include "gsim_forest.h"
@@ -238,13 +236,6 @@ hipError_t launch_comp_flatten(uint32_t* parent, uint64_t nrows, uint32_t nlevel
     return hipGetLastError();
 }
 
-hipError_t comp_scan_bytes(uint64_t nrows, size_t* bytes)
-{
-    *bytes = 0;
-    return rocprim::exclusive_scan(nullptr, *bytes, static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), 0u,
-                                   static_cast<size_t>(nrows), rocprim::plus<uint32_t>());
-}
-
 hipError_t launch_comp_label(void* tmp, size_t tmp_bytes, const uint32_t* parent, uint64_t nrows, uint32_t row_base, uint32_t* flag,
                              uint32_t* num, uint32_t* component_of, uint32_t* first_row, uint32_t* sizes, uint32_t* ncomponents,
                              hipStream_t s)
@@ -254,8 +245,7 @@ hipError_t launch_comp_label(void* tmp, size_t tmp_bytes, const uint32_t* parent
     hipLaunchKernelGGL(comp_flag_kernel, grid, block, 0, s, parent, static_cast<u64>(nrows), flag);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    size_t bytes = tmp_bytes;
-    e = rocprim::exclusive_scan(tmp, bytes, static_cast<const uint32_t*>(flag), num, 0u, static_cast<size_t>(nrows), rocprim::plus<uint32_t>(), s);
+    e = launch_scan_u32(tmp, tmp_bytes, flag, num, nrows, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(comp_label_kernel, grid, block, 0, s, parent, static_cast<const uint32_t*>(num), static_cast<u64>(nrows), row_base,
                        component_of, first_row, sizes, ncomponents);

@@ -39,8 +39,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "../../include/gpusim_hip.h"
 #include "gsim_device_common.h"
 #include "gsim_forest.h"
@@ -310,8 +308,7 @@ hipError_t launch_dbscan_label(void* tmp, size_t tmp_bytes, const DbscanArgs& a,
                        a.min_pts, static_cast<u64>(a.nrows), flag);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    size_t bytes = tmp_bytes;
-    e = rocprim::exclusive_scan(tmp, bytes, static_cast<const uint32_t*>(flag), num, 0u, static_cast<size_t>(a.nrows), rocprim::plus<uint32_t>(), s);
+    e = launch_scan_u32(tmp, tmp_bytes, flag, num, a.nrows, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(dbscan_label_kernel, grid, block, 0, s, static_cast<const uint32_t*>(a.parent), static_cast<const uint32_t*>(num),
                        static_cast<const uint32_t*>(flag), static_cast<const uint32_t*>(a.degree), reinterpret_cast<const u64*>(a.best), a.min_pts,

@@ -148,6 +148,13 @@ bool fused_supported(const ScanGeometry& g);
 uint32_t fused_summary_keys(uint32_t nwaves, uint32_t k, uint32_t max_m = 16);
 uint32_t fused_final_keys(uint32_t nwg, uint32_t k);
 
+// ScanGeometry::lanes_per_row of rows of W words: W / 4 where that is a whole power of two up to 64 (the kernels with a group of
+// lanes per row), else 0
+inline uint32_t pow2_lanes_per_row(uint32_t W)
+{
+    const uint32_t l = W / 4;
+    return (W % 4 == 0 && l != 0 && (l & (l - 1)) == 0 && l <= 64) ? l : 0;
+}
 // Geometry of the scan grid for a table (host side, no device work).
 ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll);
 // ... of the single launch where it differs from the four-kernel pipeline's: rows of 3, 5, 7, 9, 11 or twice that many WORDS
@@ -312,6 +319,11 @@ hipError_t launch_nbr_csr(void* tmp, size_t tmp_bytes, const unsigned long long*
                           float* vals_sorted, uint64_t n, uint32_t end_bit, uint64_t nrows_out, uint32_t row_base, uint64_t* indptr,
                           uint32_t* indices, hipStream_t s);
 
+// ---- primitives (gsim_prims.hip) ------------------------------------------------------------------------------------------
+// out[0 .. n) = the exclusive prefix sums of in[0 .. n), 32-bit words (tmp: scan_u32_bytes(n) bytes)
+hipError_t scan_u32_bytes(uint64_t n, size_t* bytes);
+hipError_t launch_scan_u32(void* tmp, size_t tmp_bytes, const uint32_t* in, uint32_t* out, uint64_t n, hipStream_t s);
+
 // ---- single-linkage clustering: connected components of the threshold graph (gsim_components.hip, gsim_db_components) -----
 constexpr uint32_t kCompMaxLevels = 8; // GSIM_COMPONENTS_MAX_LEVELS
 constexpr uint32_t kCompKept = 0, kCompUnions = 1, kCompCasFailed = 2, kCompCounters = 3; // CompArgs::counters
@@ -332,9 +344,8 @@ hipError_t launch_comp_init(uint32_t* parent, uint64_t nrows, uint32_t nlevels, 
 // tiles (rt0 .. rt0+nrt-1) x (ct0 .. ct0+nct-1) of the upper triangle, as launch_nbr_tiles with tri = 1
 hipError_t launch_comp_tiles(const CompArgs& a, uint32_t rt0, uint32_t nrt, uint32_t ct0, uint32_t nct, hipStream_t s);
 hipError_t launch_comp_flatten(uint32_t* parent, uint64_t nrows, uint32_t nlevels, hipStream_t s);
-hipError_t comp_scan_bytes(uint64_t nrows, size_t* bytes);
 // one flattened forest -> component_of[nrows], *ncomponents, first_row / sizes (or nullptr; sizes zeroed before) -- flag, num: nrows
-// words of scratch each
+// words of scratch each, tmp: scan_u32_bytes(nrows)
 hipError_t launch_comp_label(void* tmp, size_t tmp_bytes, const uint32_t* parent, uint64_t nrows, uint32_t row_base, uint32_t* flag,
                              uint32_t* num, uint32_t* component_of, uint32_t* first_row, uint32_t* sizes, uint32_t* ncomponents,
                              hipStream_t s);
@@ -363,7 +374,7 @@ struct DbscanArgs {
 hipError_t launch_dbscan_count(const DbscanArgs& a, uint32_t rt0, uint32_t nrt, uint32_t ct0, uint32_t nct, hipStream_t s);
 hipError_t launch_dbscan_link(const DbscanArgs& a, uint32_t rt0, uint32_t nrt, uint32_t ct0, uint32_t nct, hipStream_t s);
 // the flattened forest, the degrees and best[] -> label_of[nrows], *nclusters, the census in a.counters, anchor / first_row / sizes (or
-// nullptr; sizes zeroed before) -- flag, num: nrows words of scratch each, tmp: comp_scan_bytes
+// nullptr; sizes zeroed before) -- flag, num: nrows words of scratch each, tmp: scan_u32_bytes(nrows)
 hipError_t launch_dbscan_label(void* tmp, size_t tmp_bytes, const DbscanArgs& a, uint32_t row_base, uint32_t* flag, uint32_t* num,
                                uint32_t* label_of, uint32_t* anchor, uint32_t* first_row, uint32_t* sizes, uint32_t* nclusters, hipStream_t s);
 
@@ -764,10 +775,8 @@ hipError_t launch_rowset_mark(const uint32_t* d_rows, uint64_t n, uint32_t row_b
 // the bitmap finished in place (src: the caller's words instead of the marks; invert: an exclusion set; zero past the last row and in
 // the padding -- nalloc = words + padding) and popc[0 .. words] = its words' popcounts (popc[words] = 0)
 hipError_t launch_rowset_finish(uint32_t* bits, const uint32_t* src, uint64_t nrows, uint64_t nalloc, int invert, uint32_t* popc, hipStream_t s);
-// offs[0 .. n) = exclusive prefix sums of popc[0 .. n) (n = words + 1: offs[words] is the set's size)
-hipError_t rowset_scan_bytes(uint64_t n, size_t* bytes);
-hipError_t launch_rowset_offsets(void* tmp, size_t tmp_bytes, const uint32_t* popc, uint32_t* offs, uint64_t n, hipStream_t s);
-// list[offs[t] ..] = the rows of word t, ascending
+// list[offs[t] ..] = the rows of word t, ascending; offs[0 .. words] = the exclusive prefix sums of popc[0 .. words]
+// (launch_scan_u32: offs[words] is the set's size)
 hipError_t launch_rowset_list(const uint32_t* bits, const uint32_t* offs, uint64_t nwords, uint32_t* list, hipStream_t s);
 // The two scans of gsim_db_search_rows; both leave what launch_scan leaves (candidate segments of g.seg_cap slots per wave,
 // seg_count, QueryState) for launch_compact and the tail behind it.
@@ -785,9 +794,7 @@ hipError_t launch_popindex_popc(const void* rows, uint64_t nrows, uint32_t W, ui
 hipError_t popindex_sort_bytes(uint64_t n, uint32_t end_bit, size_t* bytes);
 hipError_t launch_popindex_sort(void* tmp, size_t tmp_bytes, const uint16_t* popc, uint16_t* popc_sorted, uint32_t* order, uint64_t n,
                                 uint32_t end_bit, hipStream_t s);
-// first[0 .. n) = exclusive prefix sums of hist[0 .. n) (n = bins + 1 with hist[bins] = 0: first[bins] is the row count)
-hipError_t popindex_scan_bytes(uint64_t n, size_t* bytes);
-hipError_t launch_popindex_first(void* tmp, size_t tmp_bytes, const uint32_t* hist, uint32_t* first, uint64_t n, hipStream_t s);
+// (the buckets' first positions: launch_scan_u32 over hist[0 .. bins] with hist[bins] = 0 -- first[bins] is the row count)
 // ub[b], b <= fp_bits: the largest score_of(metric, alpha, beta, qpop, b, c) over c in [max(0, qpop + b - fp_bits), min(qpop, b)], NaN as 0
 hipError_t launch_popindex_bounds(uint32_t fp_bits, uint32_t qpop, int metric, float alpha, float beta, float* ub, hipStream_t s);
 // The window scan: slots [lo, lo + n) of the popcount-ordered copy `a.rows` (n >= 1), slot i offered as row order[i]; leaves what

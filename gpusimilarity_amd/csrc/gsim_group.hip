@@ -28,6 +28,7 @@
 #include "../../include/gpusim_hip.h"
 #include "gsim_device_common.h"
 #include "gsim_filter_inl.h"
+#include "gsim_row_units.h"
 
 namespace gsim
 {
@@ -64,15 +65,6 @@ template <int MODE> struct GroupAcc {
     }
     __device__ __forceinline__ float result(uint32_t nq) const { return MODE == GSIM_GROUP_MEAN ? __fdiv_rn(g, static_cast<float>(nq)) : g; }
 };
-
-// the threshold poll of scan_rows (gsim_scan_inl.h): one wave of the workgroup per period reads gtau
-template <typename Filter> __device__ __forceinline__ void poll_threshold(Filter& f, uint32_t& gt, uint32_t& trip, uint32_t wib, int lane)
-{
-    f.refresh(gt, lane);
-    const uint32_t period = trip < 64u ? 8u : (trip < 512u ? 32u : 128u);
-    if ((trip & (period - 1u)) == 0 && ((trip / period) & (kScanBlock / 64 - 1)) == wib) gt = f.load_gtau();
-    trip++;
-}
 
 // the first chunk of wave w at or after c0 (chunk c belongs to wave c % nwaves in every launch of the pass)
 __device__ __forceinline__ u64 first_chunk(u64 c0, uint32_t w, uint32_t nwaves)

@@ -2,8 +2,8 @@
 // fingerprint is.  An open-addressing table in global memory, one slot = {row, count} (two 32-bit words, 8 bytes, side by side so
 // that a probe touches one line):
 //   rowhash_init_kernel       every slot {GSIM_ROW_NONE, 0}
-//   rowhash_x4_kernel<LPR>    INSERT: one streaming pass over the table (16 B per lane, non-temporal, the loader of
-//                             popindex_popc_kernel): the LPR lanes that share a row hash their own four words and add (group_sum),
+//   rowhash_x4_kernel<LPR>    INSERT: one streaming pass over the table (walk_rows_x4, gsim_row_units.h: 16 B per lane,
+//                             non-temporal): the LPR lanes that share a row hash their own four words and add (group_sum),
 //                             then probe from the row's first slot -- compare-and-swap the row's own number into an empty slot, or
 //                             gather the occupant's row, compare all words, and on equality atomicMin the slot's row and add one to
 //                             its count; on a difference go to the next slot.  The occupant of a slot only ever changes to a row with
@@ -11,7 +11,8 @@
 //                             whatever the interleaving, and that slot ends up holding the group's lowest row and its size.  The
 //                             row's slot is recorded (8 bytes per row: slot numbers pass 2^32 above 2^31 rows).
 //                             FIND: the same loader over the left rows, the probe read-only.
-//   rowhash_strided_kernel<G> every other width: one row per lane (rows of fewer than 32 words) or per wave, word by word
+//   rowhash_strided_kernel<G> every other width (walk_rows_strided): one row per lane (rows of fewer than 32 words) or per wave,
+//                             word by word
 //   rowhash_finish_kernel     every row's {first, size} from its slot, the bitmap of the first rows, the counts
 // Memory model (MI355X: the L2s of the XCDs are not coherent with one another): slots are touched ONLY through agent-scope atomics
 // (load, compare-and-swap, min, add); the table's rows are immutable during a call and are read with plain loads; what one launch
@@ -26,8 +27,8 @@
 
 #include "../../include/gpusim_hip.h"
 #include "gsim_device_common.h"
+#include "gsim_row_units.h"
 #include "gsim_rowhash_hash.h"
-#include "gsim_scan_inl.h"
 
 namespace gsim
 {
@@ -125,72 +126,53 @@ __global__ __launch_bounds__(kRhBlock) void rowhash_init_kernel(u64* __restrict_
     for (u64 i = static_cast<u64>(blockIdx.x) * kRhBlock + threadIdx.x; i < nslots; i += stride) slots[i] = static_cast<u64>(kRhNone);
 }
 
-// Rows of LPR sixteen-byte units, LPR a power of two up to 64: chunks of kRhUnroll x 64 / LPR rows, wave w takes chunks w,
-// w + nwaves, ...  `src` rows [r0, r1) are hashed; INSERT: they are the table's rows of those numbers, rec[row] = slot;
-// FIND: they are the left rows, rec[row] = the answer.
+// Rows of LPR sixteen-byte units, LPR a power of two up to 64 (walk_rows_x4: chunks of kRhUnroll x 64 / LPR rows).  `src` rows
+// [r0, r1) are hashed; INSERT: they are the table's rows of those numbers, rec[row] = slot; FIND: they are the left rows,
+// rec[row] = the answer.
 template <int LPR, bool INSERT>
 __global__ __launch_bounds__(kRhBlock) void rowhash_x4_kernel(const u32x4* __restrict__ src, u64 r0, u64 r1, const u32x4* __restrict__ table, RhTable t,
                                                               u64* __restrict__ rec)
 {
-    constexpr int RPL = 64 / LPR;
-    constexpr int CH = kRhUnroll * RPL;
     const int lane = threadIdx.x & 63;
-    const int sub = lane % LPR, grp = lane / LPR;
+    const int sub = lane % LPR;
     const u64 w = static_cast<u64>(blockIdx.x) * (kRhBlock / 64) + (threadIdx.x >> 6);
     const u64 nwaves = static_cast<u64>(gridDim.x) * (kRhBlock / 64);
-    const u64 nchunks = (r1 - r0 + CH - 1) / CH;
     const uint32_t k0 = rowhash_key(4u * sub), k1 = rowhash_key(4u * sub + 1u), k2 = rowhash_key(4u * sub + 2u), k3 = rowhash_key(4u * sub + 3u);
-    for (u64 c = w; c < nchunks; c += nwaves) {
-        u32x4 d[kRhUnroll];
-#pragma unroll
-        for (int j = 0; j < kRhUnroll; j++) {
-            const u64 row = r0 + c * CH + static_cast<u64>(j * RPL + grp);
-            d[j] = row < r1 ? stream_load(src + row * LPR + sub) : u32x4{0, 0, 0, 0};
-        }
-#pragma unroll
-        for (int j = 0; j < kRhUnroll; j++) {
-            const u64 row = r0 + c * CH + static_cast<u64>(j * RPL + grp);
-            uint32_t A = 0, B = 0;
-            rowhash_word(d[j].x, k0, A, B);
-            rowhash_word(d[j].y, k1, A, B);
-            rowhash_word(d[j].z, k2, A, B);
-            rowhash_word(d[j].w, k3, A, B);
-            A = group_sum<LPR>(A);
-            B = group_sum<LPR>(B);
-            const u32x4 mine = d[j];
-            auto match = [&](bool ask, uint32_t occ) {
-                uint32_t ne = 0;
-                if (ask) {
-                    const u32x4 o = table[static_cast<u64>(occ) * LPR + sub];
-                    ne = ((o.x ^ mine.x) | (o.y ^ mine.y) | (o.z ^ mine.z) | (o.w ^ mine.w)) != 0 ? 1u : 0u;
-                }
-                return ask && group_sum<LPR>(ne) == 0;
-            };
-            uint32_t out_row;
-            u64 out_slot;
-            probe<LPR, INSERT>(t, row < r1, rowhash_final(A, B), static_cast<uint32_t>(row), lane, match, out_row, out_slot);
-            record<INSERT>(t, sub == 0 && row < r1, row, out_row, out_slot, rec);
-        }
-    }
+    walk_rows_x4<LPR, kRhUnroll>(src, r0, r1, w, nwaves, lane, [&](u64 row, bool in, const u32x4& mine) {
+        uint32_t A = 0, B = 0;
+        rowhash_word(mine.x, k0, A, B);
+        rowhash_word(mine.y, k1, A, B);
+        rowhash_word(mine.z, k2, A, B);
+        rowhash_word(mine.w, k3, A, B);
+        A = group_sum<LPR>(A);
+        B = group_sum<LPR>(B);
+        auto match = [&](bool ask, uint32_t occ) {
+            uint32_t ne = 0;
+            if (ask) {
+                const u32x4 o = table[static_cast<u64>(occ) * LPR + sub];
+                ne = ((o.x ^ mine.x) | (o.y ^ mine.y) | (o.z ^ mine.z) | (o.w ^ mine.w)) != 0 ? 1u : 0u;
+            }
+            return ask && group_sum<LPR>(ne) == 0;
+        };
+        uint32_t out_row;
+        u64 out_slot;
+        probe<LPR, INSERT>(t, in, rowhash_final(A, B), static_cast<uint32_t>(row), lane, match, out_row, out_slot);
+        record<INSERT>(t, sub == 0 && in, row, out_row, out_slot, rec);
+    });
 }
 
-// Every other width, G lanes per row striding over its words: G = 1 (rows of fewer than 32 words: 64 rows per wave trip) or
-// G = 64 (one row per wave trip).  Word loads: no width needs padding.
+// Every other width, G lanes per row striding over its words (walk_rows_strided): G = 1 or 64.
 template <int G, bool INSERT>
 __global__ __launch_bounds__(kRhBlock) void rowhash_strided_kernel(const uint32_t* __restrict__ src, u64 r0, u64 r1, uint32_t W,
                                                                    const uint32_t* __restrict__ table, RhTable t, u64* __restrict__ rec)
 {
-    constexpr int RPW = 64 / G;
     const int lane = threadIdx.x & 63;
     const uint32_t sub = static_cast<uint32_t>(lane % G);
     const u64 w = static_cast<u64>(blockIdx.x) * (kRhBlock / 64) + (threadIdx.x >> 6);
     const u64 nwaves = static_cast<u64>(gridDim.x) * (kRhBlock / 64);
-    for (u64 b = r0 + w * RPW; b < r1; b += nwaves * RPW) {
-        const u64 row = b + static_cast<u64>(lane / G);
-        const bool active = row < r1;
-        const uint32_t* mine = src + row * W;
+    walk_rows_strided<G>(src, r0, r1, W, w, nwaves, lane, [&](u64 row, bool in, const uint32_t* mine) {
         uint32_t A = 0, B = 0;
-        if (active)
+        if (in)
             for (uint32_t i = sub; i < W; i += G) rowhash_word(mine[i], rowhash_key(i), A, B);
         A = group_sum<G>(A);
         B = group_sum<G>(B);
@@ -204,9 +186,9 @@ __global__ __launch_bounds__(kRhBlock) void rowhash_strided_kernel(const uint32_
         };
         uint32_t out_row;
         u64 out_slot;
-        probe<G, INSERT>(t, active, rowhash_final(A, B), static_cast<uint32_t>(row), lane, match, out_row, out_slot);
-        record<INSERT>(t, sub == 0 && active, row, out_row, out_slot, rec);
-    }
+        probe<G, INSERT>(t, in, rowhash_final(A, B), static_cast<uint32_t>(row), lane, match, out_row, out_slot);
+        record<INSERT>(t, sub == 0 && in, row, out_row, out_slot, rec);
+    });
 }
 
 // rec[row]: the row's slot -> {first, size} of its group (first in the low word, without a row base); bit `row` of `bits` says
@@ -293,17 +275,8 @@ hipError_t launch_rows_t(const void* src, uint64_t r0, uint64_t r1, uint32_t W, 
 {
     if (r0 >= r1) return hipSuccess;
     if (W == 0 || !src || !table || !t.slots || !t.flag || !rec || t.nslots == 0 || (t.nslots & (t.nslots - 1)) != 0) return hipErrorInvalidValue;
-    const uint32_t lpr = (W % 4 == 0 && (W / 4 & (W / 4 - 1)) == 0 && W / 4 <= 64) ? W / 4 : 0;
-    switch (lpr) {
-    case 1: return launch_x4_t<1, INSERT>(src, r0, r1, table, t, rec, num_cus, s);
-    case 2: return launch_x4_t<2, INSERT>(src, r0, r1, table, t, rec, num_cus, s);
-    case 4: return launch_x4_t<4, INSERT>(src, r0, r1, table, t, rec, num_cus, s);
-    case 8: return launch_x4_t<8, INSERT>(src, r0, r1, table, t, rec, num_cus, s);
-    case 16: return launch_x4_t<16, INSERT>(src, r0, r1, table, t, rec, num_cus, s);
-    case 32: return launch_x4_t<32, INSERT>(src, r0, r1, table, t, rec, num_cus, s);
-    case 64: return launch_x4_t<64, INSERT>(src, r0, r1, table, t, rec, num_cus, s);
-    default: break;
-    }
+    if (const uint32_t lpr = pow2_lanes_per_row(W))
+        return dispatch_lpr(lpr, [&](auto l) { return launch_x4_t<decltype(l)::value, INSERT>(src, r0, r1, table, t, rec, num_cus, s); });
     if (W < 32u) return launch_strided_t<1, INSERT>(src, r0, r1, W, table, t, rec, num_cus, s);
     return launch_strided_t<64, INSERT>(src, r0, r1, W, table, t, rec, num_cus, s);
 }

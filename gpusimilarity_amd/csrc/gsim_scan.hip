@@ -515,11 +515,6 @@ template <int LPR, int U> hipError_t launch_scan_t(const ScanArgs& a, const Scan
 // host-side launchers
 // ---------------------------------------------------------------------------
 
-static bool is_pow2(uint32_t x)
-{
-    return x && !(x & (x - 1));
-}
-
 // loads per chunk of scan_ragged_kernel for rows of L sixteen-byte units: the odd part of L when that is 3, 5, ... 15, a
 // chunk holds at least one whole row (64 P / L >= 1) and a row's bits fit the packed counts' 16-bit fields, else 0
 static uint32_t ragged_loads_of(uint32_t L)
@@ -534,7 +529,7 @@ static uint32_t ragged_loads_of(uint32_t L)
 ScanGeometry scan_geometry(uint64_t nrows, uint32_t W, int num_cus, int waves_per_cu, int unroll)
 {
     ScanGeometry g{};
-    const uint32_t lpr = (W % 4 == 0 && is_pow2(W / 4) && W / 4 <= 64) ? W / 4 : 0;
+    const uint32_t lpr = pow2_lanes_per_row(W);
     g.lanes_per_row = lpr;
     if (lpr) {
         unroll = 8; // (the only unroll built: 4 loads per chunk cost 12 %, 16 bought nothing -- profiles/r01_sweeps.txt)

@@ -3,7 +3,7 @@
 // A row set on the device is a bitmap (one bit per table row, bit r % 32 of word r / 32) and the ascending list of the selected
 // rows (4 B each, without the row base).  Both are built here: the caller's rows are marked with atomic ORs (duplicates
 // collapse), or the caller's bitmap is copied; GSIM_ROWSET_EXCLUDE inverts; the bits past the last row are cleared; the list
-// is the bitmap expanded at the exclusive prefix sums (rocPRIM) of its words' popcounts -- ascending by construction.
+// is the bitmap expanded at the exclusive prefix sums (launch_scan_u32) of its words' popcounts -- ascending by construction.
 //
 // Two scans feed the four-kernel pipeline's tail (compact_kernel -> select_kernel, or the large-k select and sort) with exactly
 // what scan_kernel leaves: per-wave candidate segments, seg_count, QueryState::ghist / kept / ncand, the gate convention.
@@ -15,20 +15,19 @@
 //                        with no selected row issues nothing.
 //   subset_gather_kernel (sparse sets) a wave walks the list: every group of LPR lanes loads one selected row (16 B per lane,
 //                        rows + list[i] * LPR + sub), U loads per lane per chunk, the next chunk's loads and the indices of the
-//                        one after it in flight while the current one is reduced (v_and + v_bcnt + group_sum, as reduce_chunk);
-//                        rows are offered under their real numbers.  Widths without a power-of-two number of 16-byte units: one
-//                        row per lane (scan_rows_lane's arithmetic over the list).
+//                        one after it in flight while the current one is reduced (reduce_listed, gsim_row_units.h); rows are
+//                        offered under their real numbers.  Widths without a power-of-two number of 16-byte units: one row per
+//                        lane (listed_lane_kernel<false>, gsim_row_units.h).
 // Seeding: none.  Both scans start from gtau = 0 ("emit everything") and raise the threshold through ghist, which only ever
 // counts selected rows; sample_kernel's seed counts rows of the whole table and may lie above the subset's k-th best.
 #include "gsim_device.h"
 
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "../../include/gpusim_hip.h"
 #include "gsim_device_common.h"
 #include "gsim_filter_inl.h"
+#include "gsim_row_units.h"
 #include "gsim_scan_inl.h"
 
 namespace gsim
@@ -194,39 +193,6 @@ hipError_t launch_scan_t(const ScanArgs& a, const ScanGeometry& g, const uint32_
 // gather route
 // ---------------------------------------------------------------------------
 
-// reduce_chunk for gathered rows: load j of lane (grp, sub) holds unit `sub` of the row list[e0 + j * RPL + grp] = ix[j]
-template <int LPR, int U, bool FULL, typename Filter>
-__device__ __forceinline__ void gather_reduce(const u32x4 (&d)[U], const uint32_t (&ix)[U], const u32x4& q, u64 e0, uint32_t nsel,
-                                              const ScanArgs& a, Filter& f, int lane)
-{
-    constexpr int RPL = 64 / LPR;
-    constexpr int ROUNDS = (U + LPR - 1) / LPR;
-    const int sub = lane % LPR;
-    const int grp = lane / LPR;
-    uint32_t v[U];
-#pragma unroll
-    for (int j = 0; j < U; j++) {
-        const uint32_t cc = __popc(d[j].x & q.x) + __popc(d[j].y & q.y) + __popc(d[j].z & q.z) + __popc(d[j].w & q.w);
-        const uint32_t bb = __popc(d[j].x) + __popc(d[j].y) + __popc(d[j].z) + __popc(d[j].w);
-        v[j] = group_sum<LPR>((cc << 16) + bb);
-    }
-#pragma unroll
-    for (int r = 0; r < ROUNDS; r++) {
-        // lane (grp, sub) takes the row of load j = r * LPR + sub
-        uint32_t val = 0, row = 0;
-#pragma unroll
-        for (int jj = 0; jj < U; jj++) {
-            if (jj / LPR == r) {
-                val = (sub == jj % LPR) ? v[jj] : val;
-                row = (sub == jj % LPR) ? ix[jj] : row;
-            }
-        }
-        const int j = r * LPR + sub;
-        const bool active = (j < U) && (FULL || e0 + static_cast<u64>(j * RPL + grp) < nsel);
-        f.template offer_counts<LPR>(active, row, val, a, lane);
-    }
-}
-
 // One wavefront over the list: chunks w, w + nwaves, ... of CH = U * 64 / LPR list entries.  Per trip, in this order: the
 // indices of the chunk after next (U 4-byte loads, one cache line per wave), the rows of the next chunk (their indices
 // arrived a trip ago), then the current chunk is reduced -- waiting for a chunk's indices never waits for the rows issued
@@ -282,13 +248,8 @@ __device__ __forceinline__ void gather_rows(const ScanArgs& a, const ScanGeometr
                 ix[j] = ixn[j];
                 ixn[j] = ixnn[j];
             }
-            f.refresh(gt, lane);
-            { // the threshold poll of scan_rows
-                const uint32_t period = trip < 64u ? 8u : (trip < 512u ? 32u : 128u);
-                if ((trip & (period - 1u)) == 0 && ((trip / period) & (kScanBlock / 64 - 1)) == wib) gt = f.load_gtau();
-                trip++;
-            }
-            gather_reduce<LPR, U, true>(d, ixc, q, c * CH, nsel, a, f, lane);
+            poll_threshold(f, gt, trip, wib, lane);
+            reduce_listed<LPR, U, true>(d, ixc, q, c * CH, nsel, a, f, lane);
             if (c == last) break;
         }
     }
@@ -307,7 +268,7 @@ __device__ __forceinline__ void gather_rows(const ScanArgs& a, const ScanGeometr
             d[j] = e < nsel ? stream_load(db + static_cast<u64>(ix[j]) * LPR + sub) : u32x4{0, 0, 0, 0};
         }
         f.refresh(f.load_gtau(), lane);
-        gather_reduce<LPR, U, false>(d, ix, q, e0, nsel, a, f, lane);
+        reduce_listed<LPR, U, false>(d, ix, q, e0, nsel, a, f, lane);
     }
 }
 
@@ -323,37 +284,6 @@ __global__ __launch_bounds__(kScanBlock) void subset_gather_kernel(ScanArgs a, S
     WaveFilter f;
     f.init(&s_filter, a.state, a.cand + static_cast<u64>(w) * g.seg_cap, a.cand_cb + static_cast<u64>(w) * g.seg_cap, a.k, a.cutoff);
     gather_rows<LPR, U>(a, g, f, q, list, nsel, w, lane);
-    f.finish(w, a, lane);
-    block_filter_flush(&s_filter, a);
-}
-
-// Every other width: one selected row per lane, word by word (scan_rows_lane's arithmetic over the list), 64 entries per trip.
-__global__ __launch_bounds__(kScanBlock) void subset_gather_lane_kernel(ScanArgs a, ScanGeometry g, const uint32_t* list, uint32_t nsel)
-{
-    __shared__ BlockFilter s_filter;
-    if (a.gate && *a.gate == 0) return;
-    const int lane = threadIdx.x & 63;
-    const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * (kScanBlock / 64) + (threadIdx.x >> 6));
-    block_filter_init(&s_filter, a.k, a.state->gtau);
-    WaveFilter f;
-    f.init(&s_filter, a.state, a.cand + static_cast<u64>(w) * g.seg_cap, a.cand_cb + static_cast<u64>(w) * g.seg_cap, a.k, a.cutoff);
-    const uint32_t* db = static_cast<const uint32_t*>(a.rows);
-    for (u64 c = w; c < g.nchunks; c += g.nwaves) {
-        const u64 e = c * 64u + static_cast<uint32_t>(lane);
-        const bool active = e < nsel;
-        const uint32_t row = active ? list[e] : 0u;
-        uint32_t cc = 0, bb = 0;
-        if (active) {
-            const uint32_t* r = db + static_cast<u64>(row) * a.W;
-            for (uint32_t i = 0; i < a.W; i++) {
-                const uint32_t x = r[i];
-                cc += __popc(x & a.query[i]);
-                bb += __popc(x);
-            }
-        }
-        f.refresh((c / g.nwaves) % 8 == 0 ? f.load_gtau() : 0u, lane);
-        f.template offer_counts<64>(active, row, (cc << 16) + bb, a, lane);
-    }
     f.finish(w, a, lane);
     block_filter_flush(&s_filter, a);
 }
@@ -391,19 +321,6 @@ hipError_t launch_rowset_finish(uint32_t* bits, const uint32_t* src, uint64_t nr
     hipLaunchKernelGGL(rowset_finish_kernel, dim3(static_cast<uint32_t>((nalloc + 255) / 256)), dim3(256), 0, s, bits, src, static_cast<u64>(nrows),
                        static_cast<u64>(rowset_words(nrows)), static_cast<u64>(nalloc), invert, popc);
     return hipGetLastError();
-}
-
-hipError_t rowset_scan_bytes(uint64_t n, size_t* bytes)
-{
-    *bytes = 0;
-    return rocprim::exclusive_scan(nullptr, *bytes, static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), 0u,
-                                   static_cast<size_t>(n), rocprim::plus<uint32_t>());
-}
-
-hipError_t launch_rowset_offsets(void* tmp, size_t tmp_bytes, const uint32_t* popc, uint32_t* offs, uint64_t n, hipStream_t s)
-{
-    size_t bytes = tmp_bytes;
-    return rocprim::exclusive_scan(tmp, bytes, popc, offs, 0u, static_cast<size_t>(n), rocprim::plus<uint32_t>(), s);
 }
 
 hipError_t launch_rowset_list(const uint32_t* bits, const uint32_t* offs, uint64_t nwords, uint32_t* list, hipStream_t s)
@@ -481,18 +398,11 @@ hipError_t launch_subset_scan(const ScanArgs& a, const ScanGeometry& g, const ui
 
 hipError_t launch_subset_gather(const ScanArgs& a, const ScanGeometry& g, const uint32_t* list, uint32_t nsel, hipStream_t s)
 {
-#define GSIM_CASE(L) \
-    if (g.lanes_per_row == L && g.unroll == 8) return launch_gather_t<L, 8>(a, g, list, nsel, s);
-    GSIM_CASE(1)
-    GSIM_CASE(2)
-    GSIM_CASE(4)
-    GSIM_CASE(8)
-    GSIM_CASE(16)
-    GSIM_CASE(32)
-    GSIM_CASE(64)
-#undef GSIM_CASE
-    if (g.lanes_per_row != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(subset_gather_lane_kernel, dim3(g.nwaves / (kScanBlock / 64)), dim3(kScanBlock), 0, s, a, g, list, nsel);
+    if (g.lanes_per_row != 0) {
+        if (g.unroll != 8) return hipErrorInvalidValue;
+        return dispatch_lpr(g.lanes_per_row, [&](auto lpr) { return launch_gather_t<decltype(lpr)::value, 8>(a, g, list, nsel, s); });
+    }
+    hipLaunchKernelGGL(listed_lane_kernel<false>, dim3(g.nwaves / (kScanBlock / 64)), dim3(kScanBlock), 0, s, a, g, list, nsel);
     return hipGetLastError();
 }
 
